@@ -11,9 +11,12 @@
 A "step" is one ply of every concurrent game on the GPU: MCTS.run (mcts.py:101-183) for each of the
 `slots` games = 1 root evaluation + `sims` simulations, i.e. (sims + 1) lock-step batches of
 {tree kernel, conv-trunk kernel, FC kernel}.  Inputs (weights, RNG tapes) are resident in HBM before
-the timed region.  After the K timed steps the same games are played as ONE whole episode in one az_selfplay call
-(timed separately) so that self-play games/s is a measured number, then a steady-state episode (games >> slots), and the
-episode-end record exchange is timed.
+the timed region.  A plain run sets up, warms up, times the K steps and prints the line.
+--full adds what the headline does not need: a profiled calibration ply for the roofline figures, then after the K timed
+steps the same games played as ONE whole episode in one az_selfplay call (timed separately) so that self-play games/s is a
+measured number, a steady-state episode (games >> slots), the timed episode-end record exchange, short runs of the opt-in
+emulated trunks and the CPU baseline.
+--dump-outputs DIR writes the records of the last timed step (what a caller of the self-play path receives) as .npy files.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -145,10 +148,35 @@ def device_name(index):
         return f"cuda:{index} {getattr(pr, 'uuid', '')}"
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(eng, out_dir, ply, suffix=""):
+    """--dump-outputs: what the self-play path hands its caller for the last timed step, read from the records of the
+    episode after az_selfplay_end.  All games of a block start together and play in lock step, so that step is record `ply`
+    of every game still playing then (a game that had ended has none).  One float32 .npy per array; above DUMP_BYTES in
+    all, a fixed seeded sample of those games."""
+    nply, result = eng.games()
+    rec = eng.records()
+    first = np.concatenate([[0], np.cumsum(nply)[:-1]]).astype(np.int64)
+    games = np.nonzero(nply > ply)[0]
+    per_game = 4 * (3 * eng.nn + 6)
+    room = (DUMP_BYTES - 8 * len(nply)) // per_game
+    if len(games) > room:
+        games = np.sort(np.random.RandomState(0).choice(games, room, replace=False))
+    r = first[games] + ply
+    arrays = {"game": games, "board": rec["boards"][r], "mover": rec["movers"][r], "last_move": rec["lasts"][r],
+              "action": rec["actions"][r], "visits": rec["visits"][r], "pi": rec["pis"][r], "z": rec["z"][r],
+              "plies_per_game": nply, "result_per_game": result}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.asarray(v, np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--share", action="store_true", help="rehearsal on a node with fewer GPUs than ranks: ranks share devices (rank % devices) and "
+    ap.add_argument("--share", action="store_true", help="rehearsal on a node with fewer GPUs than ranks: ranks share devices (rank %% devices) and "
                     "the collectives run on gloo; without it fewer GPUs than ranks is an error")
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=1)
@@ -171,6 +199,11 @@ def main():
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-emul", action="store_true", help="skip the short runs of the two opt-in fp32-emulating trunks that the default f32 line reports beside itself")
     ap.add_argument("--pmc-run", action="store_true", help="counter-collection run: 8 sims per move so the pass stays short")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the roofline calibration ply, the "
+                    "whole and steady-state episodes, the opt-in emulated trunks and the CPU baseline (--no-episode / --no-emul / --no-cpu "
+                    "leave parts out); without it the run only warms up, times --steps plies and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the records of the last timed ply (position, "
+                    "move, visit counts, pi of every game still playing) and the per-game ply counts and results as DIR/<name>.npy")
     a = ap.parse_args()
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
@@ -231,26 +264,48 @@ def main():
 
     if a.warmup > 0:
         eng.selfplay_step(a.warmup)
-    # roofline calibration: one ply with az_set_profiling on -- the lanes then play one after another, so the HIP
-    # events around every launch time the kernel alone on the GPU (normally the launches of different lanes overlap)
+    # roofline calibration (--full): one ply with az_set_profiling on -- the lanes then play one after another, so the HIP
+    # events around every launch time the kernel alone on the GPU (normally the launches of different lanes overlap).
+    # A plain run plays that ply unprofiled, so that both time the same plies of the same games.
     barrier()
-    _, k0 = eng.selfplay_step(0)
-    eng.set_profiling(True)
-    _, k1 = eng.selfplay_step(1)
-    eng.set_profiling(False)
-    cal = {key: k1[key] - k0[key] for key in k1}
+    cal = None
+    if a.full:
+        _, k0 = eng.selfplay_step(0)
+        eng.set_profiling(True)
+        _, k1 = eng.selfplay_step(1)
+        eng.set_profiling(False)
+        cal = {key: k1[key] - k0[key] for key in k1}
+    else:
+        eng.selfplay_step(1)
     barrier()
+    # the timed region: --steps plies in lock step.  Should every game end first (more steps than the longest game lasts),
+    # the plies left are played on the next block of games (fresh seeds), so that exactly --steps plies are timed.
     _, c0 = eng.selfplay_step(0)
+    d = dict.fromkeys(c0, 0)
+    left, ply0, block, ended = a.steps, a.warmup + 1, 0, False
     t0 = time.perf_counter()
-    active, c1 = eng.selfplay_step(a.steps)
+    while True:
+        active, c1 = eng.selfplay_step(left)
+        for key in c1:
+            d[key] += c1[key] - c0[key]
+        if active > 0 or left == 0:
+            break
+        eng.selfplay_end()
+        played = max(int(eng.games()[0].max()) - ply0, 0)
+        if played >= left:
+            ended = True
+            break
+        left, ply0, block = left - played, 0, block + 1
+        eng.selfplay_begin(B, seed0=3_000_000 + ((block - 1) * world + rank) * B)
+        _, c0 = eng.selfplay_step(0)
     barrier()
     dt = dt_local = time.perf_counter() - t0
+    last_ply = ply0 + left - 1          # ply index, in the open block of games, of the last timed step
     if dist:
         tmax = torch.tensor([dt], dtype=torch.float64, device=cdev)
         td.all_reduce(tmax, op=td.ReduceOp.MAX)
         dt = float(tmax.item())
 
-    d = {key: c1[key] - c0[key] for key in c1}
     exp_local = d["expansions"] + (d["plies"])           # leaf expansions + root expansions (mcts.py:120,136-138)
     sums = torch.tensor([exp_local, d["simulations"], d["plies"], d["depth_sum"], d["terminal_hits"]],
                         dtype=torch.float64, device=cdev)
@@ -266,13 +321,17 @@ def main():
         ranks = [None] * world
         td.all_gather_object(ranks, mine)
 
-    # ---- one whole episode: measured games/s, then the episode-end record exchange ----
+    if not ended:
+        eng.selfplay_end()
+    if a.dump_outputs:
+        dump_outputs(eng, a.dump_outputs, last_ply, "" if world == 1 else f"_rank{rank}")
+
+    # ---- --full: one whole episode: measured games/s, then the episode-end record exchange ----
     # The instrumented episode above (warm-up, calibration ply with serialised lanes and HIP events, K timed plies) is put
     # aside and the SAME games (same seeds) are played again in one uninstrumented az_selfplay call -- what
     # SelfPlayManager.generate_self_play(B) costs.
     episode = None
-    eng.selfplay_end()
-    if not a.no_episode:
+    if a.full and not a.no_episode:
         cend = eng.selfplay(B, seed0=1_000_000 + rank * B)
         torch.cuda.synchronize()
         ep_local = cend["seconds"]
@@ -312,7 +371,7 @@ def main():
     persist = eng.persistent()
     # ---- beside the headline (never instead of it): the same shard on the two opt-in fp32-emulating trunks, a few plies each ----
     emul = None
-    if a.trunk == "f32" and world == 1 and not a.no_emul and not a.pmc_run:
+    if a.full and a.trunk == "f32" and world == 1 and not a.no_emul and not a.pmc_run:
         emul = {}
         for mode in ("bf16x3", "f16x2"):
             try:
@@ -336,63 +395,80 @@ def main():
         eng.set_trunk_mode("f32")
 
     if rank == 0:
-        trunk_f, fc_f = net_flops(n, a.model)
-        boards = cal["expansions"] + cal["plies"]        # boards the trunk kernel evaluated in the calibration ply
-        launches = max(cal["trunk_launches"], 1)
-        avg_ms = cal["trunk_seconds"] * 1e3 / launches
-        achieved = (boards / launches) * trunk_f / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
-        # f32 MFMA spec peak; the emulated trunks issue 6 (bf16x3) or 3 (f16x2) 16-bit MFMA products per float32 product: dense peak / 6 or / 3
-        peak = 157.3 if a.trunk == "f32" else 2500.0 / (6.0 if a.trunk == "bf16x3" else 3.0)
-        agg = (d["expansions"] + d["plies"]) * trunk_f / dt / 1e12   # trunk FLOPs of this rank per wall second, timed region
-        # HBM bytes per launch from the committed PMC passes (FETCH_SIZE doubled per the gfx950 note, WRITE_SIZE as is)
-        traffic, traffic_src = None, None
-        try:
-            if a.model != "plain":
-                raise KeyError("no PMC pass for this kernel yet")
-            key = f"k_trunk<{n}>" if a.trunk == "f32" else f"k_trunk_emul<{n}, {1 if a.trunk == 'bf16x3' else 2}>"
-            # the newest committed PMC passes of this kernel (round 3 re-collected the float32 trunk; the emulated trunks' kernels
-            # are unchanged since round 2)
-            pm, src = None, None
-            for rnd in ("r03", "r02"):
-                f = os.path.join(ROOT, "profiles", f"{rnd}_pmc_{a.trunk}_summary.json")
-                if os.path.exists(f) and key in json.load(open(f)):
-                    pm, src = json.load(open(f))[key], f"profiles/{rnd}_pmc_{a.trunk}_summary.json"
-                    break
-            # FETCH_SIZE / WRITE_SIZE in KiB per dispatch; FETCH_SIZE doubled per the gfx950 note (16-B-per-lane streams count half)
-            per_board = (2.0 * pm["FETCH_SIZE"] + pm["WRITE_SIZE"]) * 1024.0 / (pm["grid"] / pm["workgroup"])
-            traffic = per_board * boards / launches
-            traffic_src = f"{src} (separate --pmc passes, per board x boards per launch)"
-        except Exception:
-            pass
-        # the rest of the path, priced against HBM with SURVEY 8(d)'s algorithmic bytes (reference semantics, fp32 edges):
-        # per simulation  d*(12A+16) [P,N,W of A children per descended level + backup RMW] + 12A [expand]
-        # + 2*ceil(n^2/8)+2 [leaf board] + 4n^2+4 [logits+value read]; A = legal cells at the calibration ply
-        nn_cells = n * n
-        ply_index = a.warmup                                  # plies already played when the calibration ply starts
-        A = nn_cells - ply_index
-        games_cal = max(cal["plies"] / max(a.engines, 1), 1)  # games per launch: every lane plays its own slots (one ply each)
-        dbar = cal["depth_sum"] / max(cal["simulations"], 1)
-        step_launches = max(cal["steps"], 1)
-        bytes_sim = dbar * (12 * A + 16) + 12 * A + (2 * ((nn_cells + 7) // 8) + 2) + (4 * nn_cells + 4)
-        step_ms = cal["step_seconds"] * 1e3 / step_launches
-        step_gbs = games_cal * bytes_sim / (step_ms * 1e-3) / 1e9 if step_ms > 0 else 0.0
-        # k_fc: the three FC layers; bytes = FC weights once per launch + per board (6n^2 head features in, n^2 logits + value out)
-        fc_w_bytes = 4 * (4 * nn_cells * nn_cells + nn_cells + 2 * nn_cells * 64 + 64 + 64 + 1) if a.model == "plain" \
-            else 4 * (2 * nn_cells * nn_cells + nn_cells + nn_cells * 64 + 64 + 64 + 1)
-        feat_in = (6 if a.model == "plain" else 3) * nn_cells * 4
-        fc_ms = (cal["nn_seconds"] - cal["trunk_seconds"]) * 1e3 / launches
-        fc_bytes = fc_w_bytes + (boards / launches) * (feat_in + 4 * nn_cells + 4)
-        fc_gbs = fc_bytes / (fc_ms * 1e-3) / 1e9 if fc_ms > 0 else 0.0
-        rest = [] if persist else [
-            {"kernel": f"k_step<{n}> (softmax/value tail, backup, PUCT select, expand; one wavefront per game)", "bound": "hbm",
-             "achieved": step_gbs, "peak": 8000.0, "unit": "GB/s", "frac": step_gbs / 8000.0, "avg_launch_ms": step_ms,
-             "games_per_launch": games_cal, "bytes_per_simulation": bytes_sim, "mean_select_depth": dbar,
-             "note": "latency-bound: a serial select->backup chain per game, ~2 MB per 256-game launch; runs underneath another engine's trunk"},
-            {"kernel": f"k_fc (policy_fc, value_fc1 on 16-board x 16-output MFMA tiles, four k-chains per output)", "bound": "hbm",
-             "achieved": fc_gbs, "peak": 8000.0, "unit": "GB/s", "frac": fc_gbs / 8000.0, "avg_launch_ms": fc_ms,
-             "bytes_per_launch": fc_bytes,
-             "note": "FC weights are re-read per 16-board row from L2; ~1% of the net's FLOPs; what it costs the pipeline is CU slots, not bandwidth"},
-        ]
+        roofline = None            # --full: priced from the calibration ply
+        if cal is not None:
+            trunk_f, fc_f = net_flops(n, a.model)
+            boards = cal["expansions"] + cal["plies"]        # boards the trunk kernel evaluated in the calibration ply
+            launches = max(cal["trunk_launches"], 1)
+            avg_ms = cal["trunk_seconds"] * 1e3 / launches
+            achieved = (boards / launches) * trunk_f / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
+            # f32 MFMA spec peak; the emulated trunks issue 6 (bf16x3) or 3 (f16x2) 16-bit MFMA products per float32 product: dense peak / 6 or / 3
+            peak = 157.3 if a.trunk == "f32" else 2500.0 / (6.0 if a.trunk == "bf16x3" else 3.0)
+            agg = (d["expansions"] + d["plies"]) * trunk_f / dt / 1e12   # trunk FLOPs of this rank per wall second, timed region
+            # HBM bytes per launch from the committed PMC passes (FETCH_SIZE doubled per the gfx950 note, WRITE_SIZE as is)
+            traffic, traffic_src = None, None
+            try:
+                if a.model != "plain":
+                    raise KeyError("no PMC pass for this kernel yet")
+                key = f"k_trunk<{n}>" if a.trunk == "f32" else f"k_trunk_emul<{n}, {1 if a.trunk == 'bf16x3' else 2}>"
+                # the newest committed PMC passes of this kernel (round 3 re-collected the float32 trunk; the emulated trunks' kernels
+                # are unchanged since round 2)
+                pm, src = None, None
+                for rnd in ("r03", "r02"):
+                    f = os.path.join(ROOT, "profiles", f"{rnd}_pmc_{a.trunk}_summary.json")
+                    if os.path.exists(f) and key in json.load(open(f)):
+                        pm, src = json.load(open(f))[key], f"profiles/{rnd}_pmc_{a.trunk}_summary.json"
+                        break
+                # FETCH_SIZE / WRITE_SIZE in KiB per dispatch; FETCH_SIZE doubled per the gfx950 note (16-B-per-lane streams count half)
+                per_board = (2.0 * pm["FETCH_SIZE"] + pm["WRITE_SIZE"]) * 1024.0 / (pm["grid"] / pm["workgroup"])
+                traffic = per_board * boards / launches
+                traffic_src = f"{src} (separate --pmc passes, per board x boards per launch)"
+            except Exception:
+                pass
+            # the rest of the path, priced against HBM with SURVEY 8(d)'s algorithmic bytes (reference semantics, fp32 edges):
+            # per simulation  d*(12A+16) [P,N,W of A children per descended level + backup RMW] + 12A [expand]
+            # + 2*ceil(n^2/8)+2 [leaf board] + 4n^2+4 [logits+value read]; A = legal cells at the calibration ply
+            nn_cells = n * n
+            ply_index = a.warmup                                  # plies already played when the calibration ply starts
+            A = nn_cells - ply_index
+            games_cal = max(cal["plies"] / max(a.engines, 1), 1)  # games per launch: every lane plays its own slots (one ply each)
+            dbar = cal["depth_sum"] / max(cal["simulations"], 1)
+            step_launches = max(cal["steps"], 1)
+            bytes_sim = dbar * (12 * A + 16) + 12 * A + (2 * ((nn_cells + 7) // 8) + 2) + (4 * nn_cells + 4)
+            step_ms = cal["step_seconds"] * 1e3 / step_launches
+            step_gbs = games_cal * bytes_sim / (step_ms * 1e-3) / 1e9 if step_ms > 0 else 0.0
+            # k_fc: the three FC layers; bytes = FC weights once per launch + per board (6n^2 head features in, n^2 logits + value out)
+            fc_w_bytes = 4 * (4 * nn_cells * nn_cells + nn_cells + 2 * nn_cells * 64 + 64 + 64 + 1) if a.model == "plain" \
+                else 4 * (2 * nn_cells * nn_cells + nn_cells + nn_cells * 64 + 64 + 64 + 1)
+            feat_in = (6 if a.model == "plain" else 3) * nn_cells * 4
+            fc_ms = (cal["nn_seconds"] - cal["trunk_seconds"]) * 1e3 / launches
+            fc_bytes = fc_w_bytes + (boards / launches) * (feat_in + 4 * nn_cells + 4)
+            fc_gbs = fc_bytes / (fc_ms * 1e-3) / 1e9 if fc_ms > 0 else 0.0
+            rest = [] if persist else [
+                {"kernel": f"k_step<{n}> (softmax/value tail, backup, PUCT select, expand; one wavefront per game)", "bound": "hbm",
+                 "achieved": step_gbs, "peak": 8000.0, "unit": "GB/s", "frac": step_gbs / 8000.0, "avg_launch_ms": step_ms,
+                 "games_per_launch": games_cal, "bytes_per_simulation": bytes_sim, "mean_select_depth": dbar,
+                 "note": "latency-bound: a serial select->backup chain per game, ~2 MB per 256-game launch; runs underneath another engine's trunk"},
+                {"kernel": f"k_fc (policy_fc, value_fc1 on 16-board x 16-output MFMA tiles, four k-chains per output)", "bound": "hbm",
+                 "achieved": fc_gbs, "peak": 8000.0, "unit": "GB/s", "frac": fc_gbs / 8000.0, "avg_launch_ms": fc_ms,
+                 "bytes_per_launch": fc_bytes,
+                 "note": "FC weights are re-read per 16-board row from L2; ~1% of the net's FLOPs; what it costs the pipeline is CU slots, not bandwidth"},
+            ]
+            roofline = {"kernel": (f"k_search<{n},{persist}> (persistent: one launch per ply = {S + 1} x [encode+conv trunk+heads (MFMA), FC layers, tree step], "
+                                   f"{persist} games per workgroup, trees in LDS; priced with the trunk FLOPs only)" if persist
+                                   else f"k_trunk_res_emul<{n}, {a.trunk}> (encode+stem+3 residual blocks+head convs, LDS-resident; the 64->64 convs = {6 if a.trunk == 'bf16x3' else 3} x v_mfma_f32_16x16x32_{'bf16' if a.trunk == 'bf16x3' else 'f16'} per tile and 32 k; peak = 16-bit dense peak / {6 if a.trunk == 'bf16x3' else 3})" if a.trunk != "f32" and a.model == "resnet"
+                                   else f"k_trunk_emul<{n}, {a.trunk}> (encode+conv1+conv2+conv3+head convs, LDS-resident; conv2/conv3 = {6 if a.trunk == 'bf16x3' else 3} x v_mfma_f32_16x16x32_{'bf16' if a.trunk == 'bf16x3' else 'f16'} per tile and 32 k; peak = 16-bit dense peak / {6 if a.trunk == 'bf16x3' else 3})" if a.trunk != "f32"
+                                   else f"k_trunk<{n}> (encode+conv1+conv2+conv3+head convs, LDS-resident, v_mfma_f32_16x16x4_f32)" if a.model == "plain"
+                                   else f"k_trunk_res<{n}> (encode+stem+3 residual blocks+head convs, LDS-resident, v_mfma_f32_16x16x4_f32)"),
+                        "bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
+                        "traffic": traffic, "traffic_source": traffic_src, "avg_launch_ms": avg_ms, "boards_per_launch": boards / launches,
+                        "flops_per_board": trunk_f,
+                        "measured": "HIP events around every k_trunk launch of one calibration ply (az_set_profiling: the lanes play "
+                                    "one after another, every launch alone on the GPU), between warmup and the timed region",
+                        "rest": rest,
+                        "aggregate": {"achieved": agg, "frac": agg / peak, "unit": "TFLOP/s",
+                                      "what": "trunk FLOPs per wall second over the timed region, all engines/streams overlapping "
+                                              "(includes the time the FC and tree kernels take)"}}
         out = {
             "metric": "mcts_node_expansions_per_sec", "value": exp_all / dt, "unit": "node-expansions/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt * 1e3 / max(a.steps, 1),
@@ -415,23 +491,10 @@ def main():
             "self_play_games_per_sec_steady_state": None if episode is None or "steady_state" not in episode else episode["steady_state"]["games_per_sec"],
             "episode": episode,
             "opt_in_emulated_trunks": emul,
-            "roofline": {"kernel": (f"k_search<{n},{persist}> (persistent: one launch per ply = {S + 1} x [encode+conv trunk+heads (MFMA), FC layers, tree step], "
-                                    f"{persist} games per workgroup, trees in LDS; priced with the trunk FLOPs only)" if persist
-                                    else f"k_trunk_res_emul<{n}, {a.trunk}> (encode+stem+3 residual blocks+head convs, LDS-resident; the 64->64 convs = {6 if a.trunk == 'bf16x3' else 3} x v_mfma_f32_16x16x32_{'bf16' if a.trunk == 'bf16x3' else 'f16'} per tile and 32 k; peak = 16-bit dense peak / {6 if a.trunk == 'bf16x3' else 3})" if a.trunk != "f32" and a.model == "resnet"
-                                    else f"k_trunk_emul<{n}, {a.trunk}> (encode+conv1+conv2+conv3+head convs, LDS-resident; conv2/conv3 = {6 if a.trunk == 'bf16x3' else 3} x v_mfma_f32_16x16x32_{'bf16' if a.trunk == 'bf16x3' else 'f16'} per tile and 32 k; peak = 16-bit dense peak / {6 if a.trunk == 'bf16x3' else 3})" if a.trunk != "f32"
-                                    else f"k_trunk<{n}> (encode+conv1+conv2+conv3+head convs, LDS-resident, v_mfma_f32_16x16x4_f32)" if a.model == "plain"
-                                    else f"k_trunk_res<{n}> (encode+stem+3 residual blocks+head convs, LDS-resident, v_mfma_f32_16x16x4_f32)"),
-                         "bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
-                         "traffic": traffic, "traffic_source": traffic_src, "avg_launch_ms": avg_ms, "boards_per_launch": boards / launches,
-                         "flops_per_board": trunk_f,
-                         "measured": "HIP events around every k_trunk launch of one calibration ply (az_set_profiling: the lanes play "
-                                     "one after another, every launch alone on the GPU), between warmup and the timed region",
-                         "rest": rest,
-                         "aggregate": {"achieved": agg, "frac": agg / peak, "unit": "TFLOP/s",
-                                       "what": "trunk FLOPs per wall second over the timed region, all engines/streams overlapping "
-                                               "(includes the time the FC and tree kernels take)"}},
+            "roofline": roofline,
+            "full": a.full,
         }
-        if not a.no_cpu and world == 1 and a.model == "plain":          # reported at N = 1 only
+        if a.full and not a.no_cpu and world == 1 and a.model == "plain":          # reported at N = 1 only
             out["cpu_baseline"] = cpu_baseline(n, k, S, sd, 0)
         else:
             out["cpu_baseline"] = None

@@ -94,7 +94,7 @@ def test_bench_under_torch_distributed_run_with_one_rank_agrees_with_plain_run()
     max/sum all-reduces and the record gather through RCCL; the deterministic quantities of the line (expansions and
     simulations played in the timed region are functions of the seeds alone) equal the plain N = 1 run's."""
     args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--board", "5", "--win", "4", "--sims", "40", "--slots", "64",
-            "--no-cpu"]
+            "--full", "--no-cpu"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
@@ -124,7 +124,7 @@ def test_bench_gpus_n_launches_n_ranks_by_itself():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
-    args = ["--steps", "2", "--warmup", "1", "--board", "9", "--win", "5", "--sims", "24", "--slots", "128", "--steady-games", "0", "--no-cpu"]
+    args = ["--steps", "2", "--warmup", "1", "--board", "9", "--win", "5", "--sims", "24", "--slots", "128", "--steady-games", "0", "--full", "--no-cpu"]
     p = subprocess.run([sys.executable, "bench.py", "--gpus", "2"] + args, env=env, timeout=600, capture_output=True, text=True, cwd=ROOT)
     assert p.returncode != 0 and "--share" in p.stderr and not [l for l in p.stdout.splitlines() if l.startswith("{")]
     line = _bench([sys.executable, "bench.py", "--gpus", "4", "--share"] + args, env)

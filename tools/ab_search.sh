@@ -6,6 +6,6 @@ for v in "$@"; do
   export AZ_ENGINE_LIB=$PWD/alphazero-piskvorky_amd/libaz_engine_$v.so
   case $v in
     *s) python tools/stamps_search.py 5 4 100 2>&1 | grep -v amdgpu.ids ;;
-    *) for rep in 1 2; do python bench.py --board 5 --win 4 --sims 100 --slots 1024 --engines 1 --steps 6 --warmup 2 --no-cpu --no-episode 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', 'exp/s', round(d['value']), 'ms/ply', round(d['ms_per_step'], 3), 'frac', round(d['roofline']['frac'], 3))"; done ;;
+    *) for rep in 1 2; do python bench.py --full --board 5 --win 4 --sims 100 --slots 1024 --engines 1 --steps 6 --warmup 2 --no-cpu --no-episode 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', 'exp/s', round(d['value']), 'ms/ply', round(d['ms_per_step'], 3), 'frac', round(d['roofline']['frac'], 3))"; done ;;
   esac
 done
