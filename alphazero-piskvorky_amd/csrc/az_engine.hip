@@ -996,26 +996,38 @@ static void launch_step(const az_engine *e, const LaunchCtx &lc, int idx)
     }
 }
 
-// the kernel sequence of one ply
-static void launch_ply(az_engine *e, const LaunchCtx &lc, bool use_split, int nnets, bool net)
+// the kernel sequence of one ply.  ev (eager profiling runs only): four events per evaluation batch, recorded in front of the
+// trunk, between trunk and FC, between FC and tree step and after the tree step; the persistent search kernel is timed as
+// a whole by the first four (it contains the trunk, the FC layers and the tree steps of every batch).  A failed event record
+// returns its error at once, with the rest of the ply not enqueued.
+static hipError_t launch_ply(az_engine *e, const LaunchCtx &lc, bool use_split, int nnets, bool net, const hipEvent_t *ev = nullptr)
 {
     const DevState &d = lc.d;
+    hipError_t rc = hipSuccess;
+    auto record = [&](int i) { if (ev) rc = hipEventRecord(ev[i], lc.stream); return rc == hipSuccess; };
     hipLaunchKernelGGL(k_begin, dim3((d.B + 255) / 256), dim3(256), 0, lc.stream, d);
     if (e->persist_gp) {               // small boards: the whole search of the ply in one persistent kernel (az_search.h)
+        if (!record(0)) return rc;
         e->ops->search(lc, e->persist_gp);
+        if (!record(1) || !record(2) || !record(3)) return rc;
         e->ops->move(lc);
-        return;
+        return rc;
     }
     if (net && d.cache) e->ops->root_cache(lc);
     const int nb = ply_batches(e);
     for (int idx = 0; idx < nb; idx++) {
         if (net) {
+            if (!record(4 * idx)) return rc;
             for (int id = 0; id < nnets; id++) { if (use_split) e->ops->trunk_split(lc, id); else e->ops->trunk(lc, id); }
+            if (!record(4 * idx + 1)) return rc;
             for (int id = 0; id < nnets; id++) e->ops->fc(lc, id);
+            if (!record(4 * idx + 2)) return rc;
         }
         launch_step(e, lc, idx);
+        if (!record(4 * idx + 3)) return rc;
     }
     e->ops->move(lc);
+    return rc;
 }
 
 static std::mutex g_capture_mutex;     // lanes of one process capture one at a time (instantiate is not cheap, and rare)
@@ -1029,7 +1041,7 @@ static int ply_graph(az_engine *e, Lane &L, const LaunchCtx &lc, bool use_split,
     if (g.exec) { HIPCHECK_L(L, hipGraphExecDestroy(g.exec)); g.exec = nullptr; }
     hipGraph_t graph = nullptr;
     HIPCHECK_L(L, hipStreamBeginCapture(lc.stream, hipStreamCaptureModeThreadLocal));
-    launch_ply(e, lc, use_split, nnets, net);
+    (void)launch_ply(e, lc, use_split, nnets, net);     // no events: nothing in it can fail
     HIPCHECK_L(L, hipStreamEndCapture(lc.stream, &graph));
     hipError_t rc = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
@@ -1056,9 +1068,6 @@ static int lane_plies(az_engine *e, Lane &L, int max_steps)
     }
     const int nnets = r.arena ? 2 : 1;
     const LaunchCtx lc_full = ctx_of_impl(e, L);
-    // timing-only diagnostics (results are wrong): AZ_DIAG_SKIP=fc | step | fcstep
-    const char *skip = getenv("AZ_DIAG_SKIP");
-    const bool skip_fc = skip && strstr(skip, "fc"), skip_step = skip && strstr(skip, "step");
     for (int step = 0; step < max_steps && L.active > 0; step++) {
         // this ply runs over the first L.cur slots: all of them, or -- after a compacting refill -- exactly the active ones
         LaunchCtx lc = lc_full;
@@ -1079,45 +1088,16 @@ static int lane_plies(az_engine *e, Lane &L, int max_steps)
             L.tape_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count();
             if (ev) HIPCHECK_L(L, hipStreamWaitEvent(L.stream, ev, 0));
         }
-        if (e->use_graph && !prof && !skip && full) {
+        if (e->use_graph && !prof && full) {
             hipGraphExec_t exec = nullptr;
             int rcg = ply_graph(e, L, lc, use_split, nnets, net, &exec);
             if (rcg) return rcg;
             HIPCHECK_L(L, hipGraphLaunch(exec, L.stream));
-            if (net) L.trunk_launches += e->persist_gp ? 1 : (int64_t)nnets * nbat;
-            L.steps += nbat;
         } else {
-            hipLaunchKernelGGL(k_begin, dim3((d.B + 255) / 256), dim3(256), 0, L.stream, d);
-            if (net && d.cache && !e->persist_gp) e->ops->root_cache(lc);
-            if (e->persist_gp) {
-                // one launch does the whole search; the events time it as a whole (it contains the conv trunk, the FC
-                // layers and the tree steps of S + 1 evaluation batches)
-                if (prof) HIPCHECK_L(L, hipEventRecord(L.ev[0], L.stream));
-                e->ops->search(lc, e->persist_gp);
-                if (prof) {
-                    HIPCHECK_L(L, hipEventRecord(L.ev[1], L.stream));
-                    HIPCHECK_L(L, hipEventRecord(L.ev[2], L.stream));
-                    HIPCHECK_L(L, hipEventRecord(L.ev[3], L.stream));
-                }
-                if (net) L.trunk_launches += 1;
-                L.steps += nbat;
-            }
-            for (int idx = 0; idx < nbat && !e->persist_gp; idx++) {
-                if (net) {
-                    const int ei = 4 * idx;
-                    if (prof) HIPCHECK_L(L, hipEventRecord(L.ev[ei], L.stream));
-                    for (int id = 0; id < nnets; id++) { if (use_split) e->ops->trunk_split(lc, id); else e->ops->trunk(lc, id); }
-                    if (prof) HIPCHECK_L(L, hipEventRecord(L.ev[ei + 1], L.stream));
-                    if (!skip_fc) for (int id = 0; id < nnets; id++) e->ops->fc(lc, id);
-                    if (prof) HIPCHECK_L(L, hipEventRecord(L.ev[ei + 2], L.stream));
-                    L.trunk_launches += nnets;
-                }
-                if (!skip_step || idx == 0) launch_step(e, lc, idx);
-                if (prof) HIPCHECK_L(L, hipEventRecord(L.ev[4 * idx + 3], L.stream));
-                L.steps++;
-            }
-            e->ops->move(lc);
+            HIPCHECK_L(L, launch_ply(e, lc, use_split, nnets, net, prof ? L.ev.data() : nullptr));
         }
+        if (net) L.trunk_launches += e->persist_gp ? 1 : (int64_t)nnets * nbat;
+        L.steps += nbat;
         L.plies += L.active;
         if (r.preset) {
             L.active = 0;

@@ -1,6 +1,5 @@
 // az_kernels.hip -- the size-templated kernels instantiated for ONE board size (compile with -DAZ_N=n).
 #include <hip/hip_runtime.h>
-#include <cstdlib>
 #include "az_launch.h"
 
 #ifndef AZ_N
@@ -11,99 +10,61 @@
 
 namespace {
 constexpr int N = AZ_N;
-const bool g_tile_split = !(getenv("AZ_TILE_SPLIT") && getenv("AZ_TILE_SPLIT")[0] == '0');
 
 void trunk(const LaunchCtx &c, int net_id)
 {
     if (c.model == 1) {
         typedef ResGeo<N> G;
         dim3 gt((c.dv.B + G::G - 1) / G::G), bt(G::NW * 64);
-#ifndef AZ_EXPERIMENT     // experiment builds (another wave count for the float32 trunk) leave the emulated trunks out
         if (c.emul == EMUL_BF16X3) hipLaunchKernelGGL((k_trunk_res_emul<N, EMUL_BF16X3>), gt, dim3(ResGeoEmul<N>::NW * 64), 0, c.stream, c.dv, c.rw[net_id], net_id, c.feat);
         else if (c.emul == EMUL_F16X2) hipLaunchKernelGGL((k_trunk_res_emul<N, EMUL_F16X2>), gt, dim3(ResGeoEmul<N>::NW * 64), 0, c.stream, c.dv, c.rw[net_id], net_id, c.feat);
-        else
-#endif
-        hipLaunchKernelGGL(k_trunk_res<N>, gt, bt, 0, c.stream, c.dv, c.rw[net_id], net_id, c.feat);
+        else hipLaunchKernelGGL(k_trunk_res<N>, gt, bt, 0, c.stream, c.dv, c.rw[net_id], net_id, c.feat);
     } else {
         typedef NetGeo<N> G;
-        const int ngroups = (c.dv.B + G::G - 1) / G::G;
-#ifndef AZ_EXPERIMENT
-        if (c.emul == EMUL_BF16X3) {
-            hipLaunchKernelGGL((k_trunk_emul<N, EMUL_BF16X3>), dim3(ngroups), dim3(G::NW * 64), 0, c.stream, c.dv, c.w[net_id], net_id, c.feat, c.dbg);
-            return;
-        }
-        if (c.emul == EMUL_F16X2) {
-            hipLaunchKernelGGL((k_trunk_emul<N, EMUL_F16X2>), dim3(ngroups), dim3(G::NW * 64), 0, c.stream, c.dv, c.w[net_id], net_id, c.feat, c.dbg);
-            return;
-        }
-#endif
-        dim3 gt(AZ_SEQ == 0 ? (ngroups < 256 ? ngroups : 256) : (ngroups + AZ_SEQ - 1) / AZ_SEQ), bt(G::NW * 64);
-        hipLaunchKernelGGL(k_trunk<N>, gt, bt, 0, c.stream, c.dv, c.w[net_id], net_id, c.feat, c.dbg);
+        dim3 gt((c.dv.B + G::G - 1) / G::G), bt(G::NW * 64);      // one board group per workgroup
+        if (c.emul == EMUL_BF16X3) hipLaunchKernelGGL((k_trunk_emul<N, EMUL_BF16X3>), gt, bt, 0, c.stream, c.dv, c.w[net_id], net_id, c.feat, c.dbg);
+        else if (c.emul == EMUL_F16X2) hipLaunchKernelGGL((k_trunk_emul<N, EMUL_F16X2>), gt, bt, 0, c.stream, c.dv, c.w[net_id], net_id, c.feat, c.dbg);
+        else hipLaunchKernelGGL(k_trunk<N>, gt, bt, 0, c.stream, c.dv, c.w[net_id], net_id, c.feat, c.dbg);
     }
 }
 
+// by cell tiles (az_net.h k_tile / k_tile_res): two launches of grid (groups, MT) for the plain net, six of 4-wave workgroups
+// for the ResidualBlock net
 void trunk_split(const LaunchCtx &c, int net_id)
 {
     if (c.model == 1) {
         typedef ResGeo<N> G;
-        const int ngroups = (c.dv.B + G::G - 1) / G::G;
-        dim3 bt(G::NW * 64);
+        const dim3 gt((c.dv.B + G::G - 1) / G::G, G::MT), b4(256);
         const ResWeights &w = c.rw[net_id];
-        if (g_tile_split) {    // by cell tiles: six launches of 4-wave workgroups (az_net.h k_tile_res)
-            const dim3 gt(ngroups, G::MT), b4(256);
-            hipLaunchKernelGGL((k_tile_res<N, 0>), gt, b4, 0, c.stream, c.dv, w.stem, w.stemb, w.blk[0], w.blkb[0], net_id, c.scratch, c.feat);
-            hipLaunchKernelGGL((k_tile_res<N, 1>), gt, b4, 0, c.stream, c.dv, w.blk[1], w.blkb[1], nullptr, nullptr, net_id, c.scratch, c.feat);
-            hipLaunchKernelGGL((k_tile_res<N, 2>), gt, b4, 0, c.stream, c.dv, w.blk[2], w.blkb[2], nullptr, nullptr, net_id, c.scratch, c.feat);
-            hipLaunchKernelGGL((k_tile_res<N, 1>), gt, b4, 0, c.stream, c.dv, w.blk[3], w.blkb[3], nullptr, nullptr, net_id, c.scratch, c.feat);
-            hipLaunchKernelGGL((k_tile_res<N, 2>), gt, b4, 0, c.stream, c.dv, w.blk[4], w.blkb[4], nullptr, nullptr, net_id, c.scratch, c.feat);
-            hipLaunchKernelGGL((k_tile_res<N, 3>), gt, b4, 0, c.stream, c.dv, w.blk[5], w.blkb[5], w.hd, w.hdb, net_id, c.scratch, c.feat);
-            return;
-        }
-        hipLaunchKernelGGL((k_split_res<N, 0>), dim3(ngroups, 4), bt, 0, c.stream, c.dv, w.stem, w.stemb, net_id, c.scratch, c.feat);
-        for (int blk = 0; blk < 3; blk++) {
-            hipLaunchKernelGGL((k_split_res<N, 1>), dim3(ngroups, 4), bt, 0, c.stream, c.dv, w.blk[2 * blk], w.blkb[2 * blk], net_id, c.scratch, c.feat);
-            hipLaunchKernelGGL((k_split_res<N, 2>), dim3(ngroups, 4), bt, 0, c.stream, c.dv, w.blk[2 * blk + 1], w.blkb[2 * blk + 1], net_id, c.scratch, c.feat);
-        }
-        hipLaunchKernelGGL((k_split_res<N, 3>), dim3(ngroups), bt, 0, c.stream, c.dv, w.hd, w.hdb, net_id, c.scratch, c.feat);
+        hipLaunchKernelGGL((k_tile_res<N, 0>), gt, b4, 0, c.stream, c.dv, w.stem, w.stemb, w.blk[0], w.blkb[0], net_id, c.scratch, c.feat);
+        hipLaunchKernelGGL((k_tile_res<N, 1>), gt, b4, 0, c.stream, c.dv, w.blk[1], w.blkb[1], nullptr, nullptr, net_id, c.scratch, c.feat);
+        hipLaunchKernelGGL((k_tile_res<N, 2>), gt, b4, 0, c.stream, c.dv, w.blk[2], w.blkb[2], nullptr, nullptr, net_id, c.scratch, c.feat);
+        hipLaunchKernelGGL((k_tile_res<N, 1>), gt, b4, 0, c.stream, c.dv, w.blk[3], w.blkb[3], nullptr, nullptr, net_id, c.scratch, c.feat);
+        hipLaunchKernelGGL((k_tile_res<N, 2>), gt, b4, 0, c.stream, c.dv, w.blk[4], w.blkb[4], nullptr, nullptr, net_id, c.scratch, c.feat);
+        hipLaunchKernelGGL((k_tile_res<N, 3>), gt, b4, 0, c.stream, c.dv, w.blk[5], w.blkb[5], w.hd, w.hdb, net_id, c.scratch, c.feat);
         return;
     }
     typedef NetGeo<N> G;
-    const int ngroups = (c.dv.B + G::G - 1) / G::G;
-    dim3 bt(G::NW * 64);
-    if (g_tile_split) {        // by cell tiles: two launches (az_net.h k_tile); AZ_TILE_SPLIT=0 keeps the channel-tile stages
-        hipLaunchKernelGGL((k_tile<N, 1>), dim3(ngroups, G::MT), bt, 0, c.stream, c.dv, c.w[net_id], net_id, c.scratch, c.feat);
-        hipLaunchKernelGGL((k_tile<N, 2>), dim3(ngroups, G::MT), bt, 0, c.stream, c.dv, c.w[net_id], net_id, c.scratch, c.feat);
-        return;
-    }
-    hipLaunchKernelGGL((k_split<N, 1>), dim3(ngroups, 2), bt, 0, c.stream, c.dv, c.w[net_id], net_id, c.scratch, c.feat);
-    hipLaunchKernelGGL((k_split<N, 2>), dim3(ngroups, 4), bt, 0, c.stream, c.dv, c.w[net_id], net_id, c.scratch, c.feat);
-    hipLaunchKernelGGL((k_split<N, 3>), dim3(ngroups, 8), bt, 0, c.stream, c.dv, c.w[net_id], net_id, c.scratch, c.feat);
-    hipLaunchKernelGGL((k_split<N, 4>), dim3(ngroups), bt, 0, c.stream, c.dv, c.w[net_id], net_id, c.scratch, c.feat);
+    const dim3 gt((c.dv.B + G::G - 1) / G::G, G::MT), bt(G::NW * 64);
+    hipLaunchKernelGGL((k_tile<N, 1>), gt, bt, 0, c.stream, c.dv, c.w[net_id], net_id, c.scratch, c.feat);
+    hipLaunchKernelGGL((k_tile<N, 2>), gt, bt, 0, c.stream, c.dv, c.w[net_id], net_id, c.scratch, c.feat);
 }
 
 long long split_scratch_floats(int slots, int model)
 {
-    if (model == 1) return (long long)((slots + ResGeo<N>::G - 1) / ResGeo<N>::G) * ResSplitGeo<N>::PER_GROUP;
-    typedef NetGeo<N> G;
-    return (long long)((slots + G::G - 1) / G::G) * SplitGeo<N>::PER_GROUP;
+    if (model == 1) return (long long)((slots + ResGeo<N>::G - 1) / ResGeo<N>::G) * ResTileGeo<N>::SCRATCH;
+    return (long long)((slots + NetGeo<N>::G - 1) / NetGeo<N>::G) * TileGeo<N>::SCRATCH;
 }
 
 template <class G>
 void fc_t(const LaunchCtx &c, int net_id, const NetWeights &w, unsigned long long *dbgfc)
 {
     // few board rows: one tile per workgroup (the latency shape); many: eight per workgroup in four rounds of two (the
-    // throughput shape: 3 workgroups per board row at n = 15).  AZ_FC_SHAPE=1|8 forces one of them.
+    // throughput shape: 3 workgroups per board row at n = 15)
     const int rows = (c.dv.B + 15) / 16;
-    static const int forced = getenv("AZ_FC_SHAPE") ? atoi(getenv("AZ_FC_SHAPE")) : 0;
-    if (forced == 1 || (forced < 8 && rows <= 4)) {
+    if (rows <= 4) {
         dim3 gf(rows, G::NTP + 4), bf(256);
         hipLaunchKernelGGL((k_fc<G, 1, 1>), gf, bf, 0, c.stream, c.dv, w, net_id, (const float *)c.feat, dbgfc);
-    } else if (forced == 16) {      // experiment: 16 tiles per workgroup, 4 rounds of 4 (16 waves)
-        dim3 gf(rows, (G::NTP + 15) / 16 + 1), bf(1024);
-        hipLaunchKernelGGL((k_fc<G, 4, 4>), gf, bf, 0, c.stream, c.dv, w, net_id, (const float *)c.feat, dbgfc);
-    } else if (forced == 17) {      // experiment: 16 tiles per workgroup, 8 rounds of 2 (8 waves)
-        dim3 gf(rows, (G::NTP + 15) / 16 + 1), bf(512);
-        hipLaunchKernelGGL((k_fc<G, 2, 8>), gf, bf, 0, c.stream, c.dv, w, net_id, (const float *)c.feat, dbgfc);
     } else {
         dim3 gf(rows, (G::NTP + 7) / 8 + 1), bf(512);
         hipLaunchKernelGGL((k_fc<G, 2, 4>), gf, bf, 0, c.stream, c.dv, w, net_id, (const float *)c.feat, dbgfc);
@@ -119,7 +80,7 @@ void fc(const LaunchCtx &c, int net_id)
 
 void step(const LaunchCtx &c, int rootN, int do_select)
 {
-    dim3 g((c.d.B + AZ_STEP_WAVES - 1) / AZ_STEP_WAVES), b(AZ_STEP_WAVES * 64);
+    dim3 g((c.d.B + STEP_WAVES - 1) / STEP_WAVES), b(STEP_WAVES * 64);
     const size_t lds = (size_t)(c.d.S + 2) * sizeof(double);   // sqrt table
     if (c.synthetic)
         hipLaunchKernelGGL((k_step<N, true>), g, b, lds, c.stream, c.d, rootN, do_select);
@@ -181,10 +142,9 @@ template <int GP>
 void search_t(const LaunchCtx &c)
 {
     if constexpr (HAS_SEARCH) {
-        dim3 g((c.d.B + GP - 1) / GP), b(AZ_NW * 64);
+        dim3 g((c.d.B + GP - 1) / GP), b(NetGeo<N>::NW * 64);
         const size_t dyn = (size_t)GP * c.d.R * N * N * sizeof(Edge);
-        static const int ts_env = getenv("AZ_SEARCH_TS") ? atoi(getenv("AZ_SEARCH_TS")) : -1;      // experiment: force the variant
-        const bool ts = GP == 2 && (ts_env >= 0 ? ts_env != 0 : (c.d.cache || c.d.reuse));      // many iterations with one game waiting for the net: compute its tiles only
+        const bool ts = GP == 2 && (c.d.cache || c.d.reuse);      // many iterations with one game waiting for the net: compute its tiles only
         if (c.synthetic)
             hipLaunchKernelGGL((k_search<N, GP, true, false, false>), g, b, dyn, c.stream, c.d, c.w[0], c.w[1], c.dbg, NoWeights{}, NoWeights{});
         else if (c.model == 1) {

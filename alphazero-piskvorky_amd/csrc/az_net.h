@@ -26,23 +26,6 @@
 #define AZ_STAMP(k) do { } while (0)
 #endif
 
-#ifndef AZ_NW
-#define AZ_NW 8          // waves per trunk workgroup
-#endif
-#ifndef AZ_SEQ
-#define AZ_SEQ 1         // board groups per trunk workgroup (0 = persistent grid stride); all variants measure the same
-#endif
-#ifndef AZ_PRIO_ALT
-#define AZ_PRIO_ALT 2    // the waves sharing a SIMD take turns with the issue priority in the conv main loops: 2 = per tap (default), 1 = per
-                         // 16-channel group (the same speed, two VGPRs over the budget at n = 15), 0 = off
-#endif
-#ifndef AZ_UNROLL_TAPS
-#define AZ_UNROLL_TAPS 1     // the conv main loops with all nine taps unrolled (constant fragment offsets, no per-tap address arithmetic)
-#endif
-#ifndef AZ_NTW
-#define AZ_NTW 1         // channel tiles per wave in the conv layers (1: 15 cell tiles per wave, no surplus tile)
-#endif
-
 struct NetWeights {
     // MFMA-fragment packed (see pack_* in az_engine.hip): [ntile][kstep/4][lane][4]
     const float *c1, *c2, *c3, *hd, *pf, *vf;
@@ -68,9 +51,7 @@ __host__ __device__ constexpr int trunk_lds_floats(int n, int g, int chan)
     const int a = chan * cs, b = chan == 96 ? 128 * up16(mr) : 0;     // plain net: the conv3 image overlays the inputs
     return a > b ? a : b;
 }
-#ifndef AZ_G_BUDGET
-#define AZ_G_BUDGET 36500      // LDS floats the packed images of one trunk workgroup may take (146 KB)
-#endif
+constexpr int TRUNK_LDS_BUDGET = 36500;     // LDS floats the packed images of one trunk workgroup may take (146 KB)
 __host__ __device__ constexpr int pick_boards(int n, int chan, int budget)
 {
     // powers of two only: 1024 x k games then split into whole rounds of 256 workgroups (3 boards per workgroup left
@@ -84,7 +65,7 @@ __host__ __device__ constexpr int pick_boards(int n, int chan, int budget)
 template <int N>
 struct NetGeo {
     static constexpr int n = N, nn = N * N, PW = N + 2, PP = PW * PW;
-    static constexpr int G = pick_boards(N, 96, AZ_G_BUDGET);            // boards per workgroup: 1 at n >= 12, 2 at 8-11, 4 below
+    static constexpr int G = pick_boards(N, 96, TRUNK_LDS_BUDGET);       // boards per workgroup: 1 at n >= 12, 2 at 8-11, 4 below
     static constexpr int M = G * nn;                               // real GEMM columns (board cells)
     // 16-cell MFMA tiles.  n = 15: one tile = one board row + its right padding cell (contiguous in the padded
     // image, so the 16 lanes of a fragment hit 16 consecutive LDS banks); other sizes: 16 consecutive cells.
@@ -94,7 +75,7 @@ struct NetGeo {
     static constexpr int CS3 = up16(MR);                           // channel stride of the conv3 output image
     static constexpr int LDSF = (96 * CS > 128 * CS3) ? 96 * CS : 128 * CS3;
     static constexpr int RW = ((nn + 63) / 64) * 64;
-    static constexpr int NW = AZ_NW;                               // waves per trunk workgroup
+    static constexpr int NW = 8;                                   // waves per trunk workgroup
     // FC kernel
     static constexpr int PC = 4, VC = 2;                           // policy_conv / value_conv output channels (net.py:46,52)
     static constexpr int NTP = (nn + 15) / 16;                     // policy N-tiles
@@ -156,12 +137,10 @@ enum { CONV_OUT_PACKED = 0, CONV_OUT3 = 1, CONV_OUT_RESIDUAL = 2,    // RESIDUAL
 // One conv layer on the workgroup's LDS image, computed as D[co][cell] = sum_k W[co][k] * X[k][cell]:
 // the weight fragment is the MFMA A operand (row = output channel), the activation fragment the B operand
 // (column = board cell), so an accumulator register holds 16 consecutive cells of one channel per 16 lanes.
-// A wave owns NTW channel tiles x MTW cell tiles; every activation fragment read from LDS feeds NTW MFMAs.
+// A wave owns one channel tile x MTW cell tiles.
 // CIN == 4 (conv1) reads plain planes [ci][pos]; CIN >= 32 reads the packed image above.
 // OUT3=false: relu(acc+bias) -> packed image of the next layer.  OUT3=true (conv3): barrier, then the
 // [co][cell] image that overlays the (now dead) inputs.
-// NTL / nt_base: the split (low-latency) kernels give one workgroup only NTL of the layer's channel tiles, starting
-// at tile nt_base; the fused kernels use all of them.
 // MTL / mt_base / mt_cnt: the tile-split kernels (k_tile) give one workgroup only the cell tiles mt_base .. mt_base + mt_cnt - 1
 // (mt_cnt <= MTL); GO / out_pos_off: their packed output goes to an image of another geometry (the full board image in
 // global memory) at positions shifted by out_pos_off; O3S: row stride of the [co][cell] output of CONV_OUT3, whose columns
@@ -169,35 +148,31 @@ enum { CONV_OUT_PACKED = 0, CONV_OUT3 = 1, CONV_OUT_RESIDUAL = 2,    // RESIDUAL
 // The first weight fragments of a layer (the ones conv_layer asks for at its top), requested by the caller ahead of the layer.
 // The persistent search kernel of the small boards does that one layer early: there a layer lasts 0.3-8 us, and the L2 round
 // trip in front of its first MFMA was a visible part of it.  Same registers, same values: results cannot change.
-template <int CIN, int NT>
+template <int CIN>
 struct ConvPre {
-    static constexpr int NTW = (AZ_NTW <= NT) ? AZ_NTW : NT;
     static constexpr int NF = CIN == 4 ? 3 : CIN / 16;       // float4 fragments per channel tile: conv1's whole weights, one tap's otherwise
-    float4 bw[NTW][NF];
+    float4 bw[NF];
 };
-template <class G, int CIN, int COUT, int NTL = COUT / 16>
-__device__ __forceinline__ ConvPre<CIN, NTL> conv_prefetch(const float *__restrict__ wp, int wave, int lane, int nt_base = 0)
+template <class G, int CIN, int COUT>
+__device__ __forceinline__ ConvPre<CIN> conv_prefetch(const float *__restrict__ wp, int wave, int lane)
 {
-    typedef ConvPre<CIN, NTL> P;
-    constexpr int NG = NTL / P::NTW;
+    typedef ConvPre<CIN> P;
+    constexpr int NG = COUT / 16;
     constexpr int KS4 = (9 * (CIN / 4) + 3) / 4;
     const int ng = wave % NG;
     P r;
+    const float4 *w4 = reinterpret_cast<const float4 *>(wp) + (size_t)ng * KS4 * 64 + lane;
 #pragma unroll
-    for (int t = 0; t < P::NTW; t++) {
-        const float4 *w4 = reinterpret_cast<const float4 *>(wp) + (size_t)(nt_base + ng * P::NTW + t) * KS4 * 64 + lane;
-#pragma unroll
-        for (int j = 0; j < P::NF; j++) r.bw[t][j] = w4[(size_t)j * 64];
-    }
+    for (int j = 0; j < P::NF; j++) r.bw[j] = w4[(size_t)j * 64];
     return r;
 }
 
-template <class G, int CIN, int COUT, int MODE, int NTL = COUT / 16, int MTL = G::MT, class GO = G, int O3S = G::CS3>
+template <class G, int CIN, int COUT, int MODE, int MTL = G::MT, class GO = G, int O3S = G::CS3>
 __device__ __forceinline__ void conv_layer(const float *in, float *out, const float *__restrict__ wp,
                                            const float *__restrict__ bias, const unsigned short *wpos,
-                                           const unsigned short *cellof, int wave, int lane, int nt_base = 0,
+                                           const unsigned short *cellof, int wave, int lane,
                                            int mt_base = 0, int mt_cnt = MTL, int out_pos_off = 0, const float *res = nullptr,
-                                           unsigned long long *lst = nullptr, const ConvPre<CIN, NTL> *pre = nullptr)
+                                           unsigned long long *lst = nullptr, const ConvPre<CIN> *pre = nullptr)
 {
     // diagnostic builds only (-DAZ_STAMPS): per-wave time stamps of a layer's phases into lst[wave * 4 + k]
 #ifdef AZ_STAMPS
@@ -207,9 +182,7 @@ __device__ __forceinline__ void conv_layer(const float *in, float *out, const fl
 #endif
     constexpr bool OUT3 = MODE == CONV_OUT3 || MODE == CONV_OUT3_RESIDUAL || MODE == CONV_OUT3_PK;
     constexpr bool SUBSET = MTL < G::MT;                       // a tile-split kernel: waves without a tile skip the layer
-    constexpr int NT = NTL;                                    // channel tiles handled by this workgroup
-    constexpr int NTW = (AZ_NTW <= NT) ? AZ_NTW : NT;          // channel tiles per wave
-    constexpr int NG = NT / NTW;                               // channel-tile groups
+    constexpr int NG = COUT / 16;                              // channel tiles
     constexpr int MG = (G::NW / NG) > 0 ? (G::NW / NG) : 1;    // cell-tile groups
     // cell tiles per wave: the first MTL % MG cell-tile groups take one more than the others.  The layer's body is
     // instantiated for both counts and a wave runs the one that is its own (until round 3 every wave ran the larger count and
@@ -227,21 +200,15 @@ __device__ __forceinline__ void conv_layer(const float *in, float *out, const fl
         if constexpr (OUT3) __syncthreads();       // a wave without a tile still meets the layer's barrier
     } else {
     AZ_LSTAMP(0);
-    f32x4 acc[NTW][MTW];
+    f32x4 acc[MTW];
 #pragma unroll
-    for (int t = 0; t < NTW; t++)
-#pragma unroll
-        for (int i = 0; i < MTW; i++) acc[t][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < MTW; i++) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const float4 *wp4[NTW];
-#pragma unroll
-    for (int t = 0; t < NTW; t++) wp4[t] = reinterpret_cast<const float4 *>(wp) + (size_t)(nt_base + ng * NTW + t) * KS4 * 64 + lane;
+    const float4 *wp4 = reinterpret_cast<const float4 *>(wp) + (size_t)ng * KS4 * 64 + lane;
     // the epilogue's biases are requested before the main loop, so that their L2 round trip is not paid between two layers
-    float bias_pre[NTW][4];
+    float bias_pre[4];
 #pragma unroll
-    for (int t = 0; t < NTW; t++)
-#pragma unroll
-        for (int rg = 0; rg < 4; rg++) bias_pre[t][rg] = bias[(nt_base + ng * NTW + t) * 16 + q * 4 + rg];
+    for (int rg = 0; rg < 4; rg++) bias_pre[rg] = bias[ng * 16 + q * 4 + rg];
     if (!SUBSET || mg < mt_cnt) {
     if constexpr (CIN == 4) {
         // conv1: 9 k-steps (one per tap), channels = {mover, opponent, last move, zero plane}, planes [ci][pos]
@@ -252,29 +219,22 @@ __device__ __forceinline__ void conv_layer(const float *in, float *out, const fl
             int m = (mt_base + (mt < mt_cnt ? mt : 0)) * 16 + r16;       // a surplus tile aliases the first one (computed, never written back)
             rb[i] = (int)wpos[m] - (G::PW + 1) + q * G::CS;
         }
-        float bk[NTW][12];
-#pragma unroll
-        for (int t = 0; t < NTW; t++) {
-            float4 b0, b1, b2;
-            if (pre) { b0 = pre->bw[t][0]; b1 = pre->bw[t][1]; b2 = pre->bw[t][2]; }
-            else { b0 = wp4[t][0]; b1 = wp4[t][64]; b2 = wp4[t][128]; }
-            const float tmp[12] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w};
-#pragma unroll
-            for (int j = 0; j < 12; j++) bk[t][j] = tmp[j];
-        }
+        float4 b0, b1, b2;
+        if (pre) { b0 = pre->bw[0]; b1 = pre->bw[1]; b2 = pre->bw[2]; }
+        else { b0 = wp4[0]; b1 = wp4[64]; b2 = wp4[128]; }
+        const float bk[12] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w};
 #pragma unroll
         for (int tap = 0; tap < 9; tap++) {
             const int toff = (tap / 3) * G::PW + (tap % 3);
 #pragma unroll
             for (int i = 0; i < MTW; i++) {
                 const float a = in[rb[i] + toff];
-#pragma unroll
-                for (int t = 0; t < NTW; t++) acc[t][i] = mfma4(bk[t][tap], a, acc[t][i]);
+                acc[i] = mfma4(bk[tap], a, acc[i]);
             }
         }
     } else {
         constexpr int NQ = KST / 4;        // weight groups (= 16-channel groups) per tap: 2 for conv2, 4 for conv3
-        // Software pipeline pinned with sched_group_barrier: while the 4*MTW*NTW MFMAs of group g issue, the MTW
+        // Software pipeline pinned with sched_group_barrier: while the 4*MTW MFMAs of group g issue, the MTW
         // ds_read_b128 of group g+1 are interleaved between them; the weight fragments of tap t+1 are fetched (L2)
         // at the top of tap t.
         const float4 *in4 = reinterpret_cast<const float4 *>(in);
@@ -286,44 +246,34 @@ __device__ __forceinline__ void conv_layer(const float *in, float *out, const fl
             ra[i] = (int)wpos[m] - (G::PW + 1) + q * G::CS;
         }
         float4 a0[MTW], a1[MTW];
-        float4 bw[NTW][NQ], bnx[NTW][NQ];
-#if AZ_PRIO_ALT
+        float4 bw[NQ], bnx[NQ];
         const int prio_turn = (wave >> 2) % (G::NW / 4);        // scalar: which of the waves sharing a SIMD this one is
-#endif
 #pragma unroll
-        for (int t = 0; t < NTW; t++)
-#pragma unroll
-            for (int j = 0; j < NQ; j++) bw[t][j] = pre ? pre->bw[t][j] : wp4[t][(size_t)j * 64];
+        for (int j = 0; j < NQ; j++) bw[j] = pre ? pre->bw[j] : wp4[(size_t)j * 64];
 #pragma unroll
         for (int i = 0; i < MTW; i++) a0[i] = in4[ra[i]];
-        // AZ_UNROLL_TAPS: the nine taps unrolled, so that every fragment address is the tile's base register + a constant (the
-        // ds_read's 16-bit immediate: at most ((NQ - 1) 4 CS + 2 PW + 2) x 16 B = 58.9 KB at n = 15) and the weight registers
-        // of consecutive taps are renamed instead of copied.  The rolled loop kept a running index per tile and recomputed
+        // The nine taps unrolled, so that every fragment address is the tile's base register + a constant (the ds_read's
+        // 16-bit immediate: at most ((NQ - 1) 4 CS + 2 PW + 2) x 16 B = 58.9 KB at n = 15) and the weight registers of
+        // consecutive taps are renamed instead of copied.  The rolled loop kept a running index per tile and recomputed
         // the bases every tap: 0.82 vector instructions per MFMA in conv3 -- and the float32 MFMA leaves the SIMD's vector
         // issue so little room that those showed one for one: 35.2 cycles per MFMA instead of 32 (measured with the LDS
         // reads AND the weight fetches taken out: still 35).
-#if AZ_UNROLL_TAPS
 #pragma unroll
-#endif
         for (int tap = 0; tap < 9; tap++) {
             const int tn = tap + 1 < 9 ? tap + 1 : tap;
 #pragma unroll
-            for (int t = 0; t < NTW; t++)
-#pragma unroll
-                for (int j = 0; j < NQ; j++) bnx[t][j] = wp4[t][(size_t)(tn * NQ + j) * 64];
+            for (int j = 0; j < NQ; j++) bnx[j] = wp4[(size_t)(tn * NQ + j) * 64];
 #pragma unroll
             for (int sq = 0; sq < NQ; sq++) {
-#if AZ_PRIO_ALT
                 // The waves that share a SIMD (w, w + 4, ...) run the same program; left alone, one of them wins the issue
                 // arbitration every time, finishes the layer early and leaves its partner to run the rest alone -- and ONE
                 // wave issues an MFMA only every ~44 cycles (measured: conv3 at n = 15, waves 4-7 done after 102.6 k cycles,
-                // waves 0-3 after 151.6 k; the matrix pipe needs 138.2 k).  Taking turns with the priority keeps them
-                // level, so that the pipe has two streams to draw from until the end.
-                if (AZ_PRIO_ALT == 1 || sq == 0) {      // 1: turns change every 16-channel group, 2: every tap
-                    if (((AZ_PRIO_ALT == 1 ? tap * NQ + sq : tap) % (G::NW / 4)) == prio_turn) __builtin_amdgcn_s_setprio(1);
+                // waves 0-3 after 151.6 k; the matrix pipe needs 138.2 k).  Taking turns with the priority, tap by tap, keeps
+                // them level, so that the pipe has two streams to draw from until the end.
+                if (sq == 0) {
+                    if ((tap % (G::NW / 4)) == prio_turn) __builtin_amdgcn_s_setprio(1);
                     else __builtin_amdgcn_s_setprio(0);
                 }
-#endif
                 float4 *cur = (sq & 1) ? a1 : a0;
                 float4 *nxt = (sq & 1) ? a0 : a1;
                 // float4 offset of the NEXT group's fragments from the tile's base: next 16-channel group of this tap, or the
@@ -335,66 +285,56 @@ __device__ __forceinline__ void conv_layer(const float *in, float *out, const fl
 #pragma unroll
                 for (int e = 0; e < 4; e++)
 #pragma unroll
-                    for (int i = 0; i < MTW; i++)
-#pragma unroll
-                        for (int t = 0; t < NTW; t++) {
-                            const float4 wv = bw[t][sq];
-                            const float we = e == 0 ? wv.x : e == 1 ? wv.y : e == 2 ? wv.z : wv.w;
-                            const float ae = e == 0 ? cur[i].x : e == 1 ? cur[i].y : e == 2 ? cur[i].z : cur[i].w;
-                            acc[t][i] = mfma4(we, ae, acc[t][i]);
-                        }
+                    for (int i = 0; i < MTW; i++) {
+                        const float4 wv = bw[sq];
+                        const float we = e == 0 ? wv.x : e == 1 ? wv.y : e == 2 ? wv.z : wv.w;
+                        const float ae = e == 0 ? cur[i].x : e == 1 ? cur[i].y : e == 2 ? cur[i].z : cur[i].w;
+                        acc[i] = mfma4(we, ae, acc[i]);
+                    }
 #pragma unroll
                 for (int i = 0; i < MTW; i++) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 4 * NTW, 0);   // 4*NTW MFMAs
+                    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);         // 4 MFMAs
                     __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);         // 1 LDS read (b128)
                 }
             }
 #pragma unroll
-            for (int t = 0; t < NTW; t++)
-#pragma unroll
-                for (int j = 0; j < NQ; j++) bw[t][j] = bnx[t][j];
+            for (int j = 0; j < NQ; j++) bw[j] = bnx[j];
         }
-#if AZ_PRIO_ALT
         __builtin_amdgcn_s_setprio(0);
-#endif
     }
     }
     AZ_LSTAMP(1);
     if constexpr (OUT3) __syncthreads();   // every wave has finished reading the conv3 input image
     AZ_LSTAMP(2);
+    float bco[4];
 #pragma unroll
-    for (int t = 0; t < NTW; t++) {
-        const int nt = nt_base + ng * NTW + t;
-        float bco[4];
+    for (int rg = 0; rg < 4; rg++) bco[rg] = bias_pre[rg];
 #pragma unroll
-        for (int rg = 0; rg < 4; rg++) bco[rg] = bias_pre[t][rg];
+    for (int i = 0; i < MTW; i++) {
+        const int mt = mg + i * MG;
+        if (mt < mt_cnt) {
+            const int m = (mt_base + mt) * 16 + r16;
+            const bool valid = cellof[m] != 0xFFFFu;
+            const int pos = (int)wpos[m] + out_pos_off;
 #pragma unroll
-        for (int i = 0; i < MTW; i++) {
-            const int mt = mg + i * MG;
-            if (mt < mt_cnt) {
-                const int m = (mt_base + mt) * 16 + r16;
-                const bool valid = cellof[m] != 0xFFFFu;
-                const int pos = (int)wpos[m] + out_pos_off;
-#pragma unroll
-                for (int rg = 0; rg < 4; rg++) {
-                    const int co = nt * 16 + q * 4 + rg;      // = 16*cg + 4*e + q' with cg = nt, e = q, q' = rg
-                    float v = acc[t][i][rg] + bco[rg];
-                    v = v > 0.0f ? v : 0.0f;
-                    if constexpr (MODE == CONV_OUT3_PK) {
-                        // co = 16 nt + 4 q + rg  ->  plane (nt, rg), component q: the 64 lanes of a store cover 256 contiguous bytes
-                        out[(((nt * 4 + rg) * G::MR + m) << 2) + q] = v;
-                    } else if constexpr (MODE == CONV_OUT3_RESIDUAL) {
-                        float r = acc[t][i][rg] + bco[rg] + (valid ? res[pk_index<GO>(co, pos)] : 0.0f);
-                        out[co * O3S + mt * 16 + r16 + (SUBSET ? 0 : mt_base * 16)] = r > 0.0f ? r : 0.0f;
-                    } else if constexpr (OUT3) out[co * O3S + mt * 16 + r16 + (SUBSET ? 0 : mt_base * 16)] = v;
-                    else if constexpr (MODE == CONV_OUT_RESIDUAL) {
-                        if (valid) {                          // net block: relu(bn2(conv2(h)) + x), x updated in place
-                            const int oi = pk_index<GO>(co, pos);
-                            float r = acc[t][i][rg] + bco[rg] + out[oi];
-                            out[oi] = r > 0.0f ? r : 0.0f;
-                        }
-                    } else if (valid) out[pk_index<GO>(co, pos)] = v;
-                }
+            for (int rg = 0; rg < 4; rg++) {
+                const int co = ng * 16 + q * 4 + rg;      // = 16*cg + 4*e + q' with cg = ng, e = q, q' = rg
+                float v = acc[i][rg] + bco[rg];
+                v = v > 0.0f ? v : 0.0f;
+                if constexpr (MODE == CONV_OUT3_PK) {
+                    // co = 16 ng + 4 q + rg  ->  plane (ng, rg), component q: the 64 lanes of a store cover 256 contiguous bytes
+                    out[(((ng * 4 + rg) * G::MR + m) << 2) + q] = v;
+                } else if constexpr (MODE == CONV_OUT3_RESIDUAL) {
+                    float r = acc[i][rg] + bco[rg] + (valid ? res[pk_index<GO>(co, pos)] : 0.0f);
+                    out[co * O3S + mt * 16 + r16 + (SUBSET ? 0 : mt_base * 16)] = r > 0.0f ? r : 0.0f;
+                } else if constexpr (OUT3) out[co * O3S + mt * 16 + r16 + (SUBSET ? 0 : mt_base * 16)] = v;
+                else if constexpr (MODE == CONV_OUT_RESIDUAL) {
+                    if (valid) {                          // net block: relu(bn2(conv2(h)) + x), x updated in place
+                        const int oi = pk_index<GO>(co, pos);
+                        float r = acc[i][rg] + bco[rg] + out[oi];
+                        out[oi] = r > 0.0f ? r : 0.0f;
+                    }
+                } else if (valid) out[pk_index<GO>(co, pos)] = v;
             }
         }
     }
@@ -417,14 +357,14 @@ __device__ __forceinline__ void trunk_heads(const DevState &d, const NetWeights 
     float hb[4];
 #pragma unroll
     for (int rg = 0; rg < 4; rg++) hb[rg] = (q * 4 + rg) < 6 ? w.hdb[q * 4 + rg] : 0.0f;
-    constexpr int HT = (G::MT + AZ_NW - 1) / AZ_NW;     // tiles per wave
+    constexpr int HT = (G::MT + G::NW - 1) / G::NW;     // tiles per wave
     f32x4 acc[HT];
     // the conv3 image is packed by tile cell (CONV_OUT3_PK): lane (q, r16) reads the float4 of plane (s4, q) at its cell -- the B
     // operands of k-steps 4 s4 .. 4 s4 + 3 (channels 16 s4 + 4 e + q)
     const float4 *ip[HT];
 #pragma unroll
     for (int i = 0; i < HT; i++) {
-        const int mt = wave + AZ_NW * i;
+        const int mt = wave + G::NW * i;
         acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
         ip[i] = reinterpret_cast<const float4 *>(lds) + q * G::MR + (mt < G::MT ? mt : 0) * 16 + r16;
     }
@@ -442,7 +382,7 @@ __device__ __forceinline__ void trunk_heads(const DevState &d, const NetWeights 
     }
 #pragma unroll
     for (int i = 0; i < HT; i++) {
-        const int mt = wave + AZ_NW * i;
+        const int mt = wave + G::NW * i;
         if (mt < G::MT) {
             const int cell = cellof[mt * 16 + r16];
             if (cell != 0xFFFF) {
@@ -463,10 +403,7 @@ __device__ __forceinline__ void trunk_heads(const DevState &d, const NetWeights 
     }
 }
 
-// The work of one board group.  When this is inlined into a loop over groups the compiler hoists the layers'
-// loop-invariant address arithmetic across iterations, runs out of VGPRs (256 + scratch) and the kernel slows down by
-// 20 %; callers in a loop therefore pass a thread id made opaque per iteration (asm volatile), which pins that
-// arithmetic inside the iteration.  (Out-of-line calls are worse: the call ABI forces spills.)
+// The work of one board group: one k_trunk workgroup (several groups per workgroup measured the same).
 template <int N>
 __device__ __forceinline__ void trunk_group(const DevState &d, const NetWeights &w, int net_id, float *__restrict__ feat,
                                                       unsigned long long *dbg, int grp, float *lds, unsigned short *wpos,
@@ -493,12 +430,12 @@ __device__ __forceinline__ void trunk_group(const DevState &d, const NetWeights 
     // Every thread requests the leaf words of its cells (games.py:86-129 encode: ch0 = side to move, ch1 = opponent, ch2 = last
     // action, ch3 = zeros) before it is known whether the group has anything to evaluate: the loads are in flight while both
     // padded images are zeroed (the padding ring must read as 0).
-    constexpr int EPT = (G::MR + AZ_NW * 64 - 1) / (AZ_NW * 64);
+    constexpr int EPT = (G::MR + G::NW * 64 - 1) / (G::NW * 64);
     int e_pos[EPT];
     bool e_me[EPT], e_op[EPT], e_last[EPT];
 #pragma unroll
     for (int e = 0; e < EPT; e++) {
-        const int m = tid + e * AZ_NW * 64;
+        const int m = tid + e * G::NW * 64;
         int pos = G::PW + 1, cell = 0xFFFF;
         if (m < G::MR) {
             if constexpr (G::ROWT) {
@@ -529,7 +466,7 @@ __device__ __forceinline__ void trunk_group(const DevState &d, const NetWeights 
     }
     {
         float4 *z = reinterpret_cast<float4 *>(lds);
-        for (int i = tid; i < (96 * G::CS) / 4; i += AZ_NW * 64) z[i] = float4{0.f, 0.f, 0.f, 0.f};
+        for (int i = tid; i < (96 * G::CS) / 4; i += G::NW * 64) z[i] = float4{0.f, 0.f, 0.f, 0.f};
     }
     __syncthreads();
     if (!any_active) return;
@@ -545,7 +482,7 @@ __device__ __forceinline__ void trunk_group(const DevState &d, const NetWeights 
     __syncthreads();
     // the input planes lived in the first 3 planes of inB; clear them before conv2's packed output lands there
     // (in packed coordinates some of those floats are padding-ring cells that conv2 never writes)
-    for (int i = tid; i < 3 * G::CS; i += AZ_NW * 64) inB[i] = 0.0f;
+    for (int i = tid; i < 3 * G::CS; i += G::NW * 64) inB[i] = 0.0f;
     __syncthreads();
     AZ_STAMP(2);
     conv_layer<G, 32, 64, CONV_OUT_PACKED>(inA, inB, w.c2, w.c2b, wpos, cellof, wave, lane);
@@ -556,7 +493,7 @@ __device__ __forceinline__ void trunk_group(const DevState &d, const NetWeights 
 #else
     unsigned long long *lst3 = nullptr;
 #endif
-    conv_layer<G, 64, 128, CONV_OUT3_PK>(inB, lds, w.c3, w.c3b, wpos, cellof, wave, lane, 0, 0, G::MT, 0, nullptr, lst3);
+    conv_layer<G, 64, 128, CONV_OUT3_PK>(inB, lds, w.c3, w.c3b, wpos, cellof, wave, lane, 0, G::MT, 0, nullptr, lst3);
     __syncthreads();
     AZ_STAMP(4);
     trunk_heads<G>(d, w, net_id, feat, lds, cellof, b0, wave, lane);
@@ -564,7 +501,7 @@ __device__ __forceinline__ void trunk_group(const DevState &d, const NetWeights 
 }
 
 template <int N>
-__global__ __launch_bounds__(AZ_NW * 64) void k_trunk(DevState d, NetWeights w, int net_id, float *__restrict__ feat,
+__global__ __launch_bounds__(NetGeo<N>::NW * 64) void k_trunk(DevState d, NetWeights w, int net_id, float *__restrict__ feat,
                                                unsigned long long *dbg)
 {
     typedef NetGeo<N> G;
@@ -573,175 +510,29 @@ __global__ __launch_bounds__(AZ_NW * 64) void k_trunk(DevState d, NetWeights w, 
     __shared__ unsigned short cellof[G::MR];   // g*nn + cell index, 0xFFFF for a junk lane
     __shared__ int any_active;
     const int ngroups = (d.B + G::G - 1) / G::G;
-#if AZ_SEQ == 0
-    // persistent: one workgroup per CU walks the groups with a grid stride
-    for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
-        int tid = threadIdx.x;
-        asm volatile("" : "+v"(tid));
-        trunk_group<N>(d, w, net_id, feat, dbg, grp, lds, wpos, cellof, &any_active, tid);
-        __syncthreads();
-    }
-#else
+    // One board group per workgroup.  The body stays inside a one-trip loop on purpose: the compiler schedules trunk_group
+    // differently without the loop (at n = 15, 34 more instructions, 23 more VALU between the MFMAs of conv1, conv2 and the
+    // heads), and the loop form is the code every measurement in DESIGN.md was taken on.
 #pragma unroll 1
-    for (int it = 0; it < AZ_SEQ; it++) {
-        const int grp = blockIdx.x * AZ_SEQ + it;
+    for (int it = 0; it < 1; it++) {
+        const int grp = blockIdx.x + it;
         if (grp >= ngroups) break;
         int tid = threadIdx.x;
-        if (AZ_SEQ > 1) asm volatile("" : "+v"(tid));
         trunk_group<N>(d, w, net_id, feat, dbg, grp, lds, wpos, cellof, &any_active, tid);
-        if (it + 1 < AZ_SEQ) __syncthreads();      // the LDS image is reused by the next group
-    }
-#endif
-}
-
-// ------------------------------------------------------------------------------------------------
-// Split trunk (GomokuNet): the low-latency path for launches with few pending boards (episode tails, the arena,
-// single-position search).  The fused k_trunk keeps a board on ONE CU (~95 us of paced MFMAs at n = 15); here every
-// layer is its own launch and a board's channel tiles are spread over 2 / 4 / 8 workgroups, the activations crossing
-// HBM/L2 in the same packed images (scratch per board group, padding ring zeroed once at allocation).  Same fma
-// chains, so the results are bit-identical to k_trunk.
-//   stage 1: encode + conv1   grid (groups, 2)      -> img1  (32 channels, packed)
-//   stage 2: conv2            grid (groups, 4)      -> img2  (64 channels, packed)
-//   stage 3: conv3            grid (groups, 8)      -> img3  ([co][cell], stride CS3)
-//   stage 4: 1x1 heads        grid (groups)         -> feature rows
-// ------------------------------------------------------------------------------------------------
-template <int N>
-struct SplitGeo {
-    typedef NetGeo<N> G;
-    static constexpr int IMG1 = 32 * G::CS, IMG2 = 64 * G::CS, IMG3 = 128 * G::CS3;
-    static constexpr int PER_GROUP = IMG1 + IMG2 + IMG3;      // floats of scratch per board group
-};
-
-template <int N>
-__device__ __forceinline__ bool split_prologue(const DevState &d, int net_id, int b0, unsigned short *wpos,
-                                               unsigned short *cellof, int *any_active, int tid)
-{
-    typedef NetGeo<N> G;
-    if (tid == 0) *any_active = 0;
-    __syncthreads();
-    if (tid < G::G) {
-        int b = b0 + tid;
-        if (b < d.B) {
-            int kind = d.leaf_kind[b];
-            if ((kind == LEAF_ROOT || kind == LEAF_EXPAND) && d.s_status[b] == SLOT_ACTIVE && d.s_net[b] == net_id)
-                atomicOr(any_active, 1);
-        }
-    }
-    for (int m = tid; m < G::MR; m += G::NW * 64) {
-        int pos, cell;
-        if constexpr (G::ROWT) {
-            const int t = m >> 4, c = m & 15, g = t / N, r = t - g * N;
-            pos = g * G::PP + (r + 1) * G::PW + (c + 1);
-            cell = c < N ? g * G::nn + r * N + c : 0xFFFF;
-        } else {
-            const int g = m / G::nn, p = m - g * G::nn, r = p / N, c = p - r * N;
-            pos = m < G::M ? g * G::PP + (r + 1) * G::PW + (c + 1) : G::PW + 1;
-            cell = m < G::M ? m : 0xFFFF;
-        }
-        wpos[m] = (unsigned short)pos;
-        cellof[m] = (unsigned short)cell;
-    }
-    __syncthreads();
-    return *any_active != 0;
-}
-
-template <int N, int STAGE>
-__global__ __launch_bounds__(AZ_NW * 64) void k_split(DevState d, NetWeights w, int net_id, float *__restrict__ scratch,
-                                                      float *__restrict__ feat)
-{
-    typedef NetGeo<N> G;
-    typedef SplitGeo<N> SG;
-    constexpr int NTH = G::NW * 64;
-    constexpr int LDSF = STAGE == 1 ? 4 * G::CS : (STAGE == 2 ? 32 * G::CS : (STAGE == 3 ? 64 * G::CS : 128 * G::CS3));
-    __shared__ __attribute__((aligned(16))) float lds[LDSF];
-    __shared__ unsigned short wpos[G::MR];
-    __shared__ unsigned short cellof[G::MR];
-    __shared__ int any_active;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = blockIdx.x, b0 = grp * G::G;
-    if (!split_prologue<N>(d, net_id, b0, wpos, cellof, &any_active, tid)) return;
-    float *img1 = scratch + (size_t)grp * SG::PER_GROUP, *img2 = img1 + SG::IMG1, *img3 = img2 + SG::IMG2;
-    if constexpr (STAGE == 1) {
-        for (int i = tid; i < LDSF; i += NTH) lds[i] = 0.0f;
-        __syncthreads();
-        for (int m = tid; m < G::MR; m += NTH) {          // games.py:86-129 encode
-            const int cell = cellof[m];
-            if (cell != 0xFFFF) {
-                const int g = cell / G::nn, p = cell - g * G::nn;
-                const int b = b0 + g;
-                if (b < d.B) {
-                    const u64 *lf = d.leaf + (size_t)b * 8;
-                    const int pos = wpos[m];
-                    const int ps = sym_cell(d.leaf_sym, b, p, G::n);
-                    if ((lf[ps >> 6] >> (ps & 63)) & 1ull) lds[pos] = 1.0f;
-                    if ((lf[4 + (ps >> 6)] >> (ps & 63)) & 1ull) lds[G::CS + pos] = 1.0f;
-                    if (d.leaf_last[b] == ps) lds[2 * G::CS + pos] = 1.0f;
-                }
-            }
-        }
-        __syncthreads();
-        conv_layer<G, 4, 32, CONV_OUT_PACKED, 1>(lds, img1, w.c1, w.c1b, wpos, cellof, wave, lane, blockIdx.y);
-    } else if constexpr (STAGE == 2 || STAGE == 3) {
-        const float4 *src = reinterpret_cast<const float4 *>(STAGE == 2 ? img1 : img2);
-        float4 *dst = reinterpret_cast<float4 *>(lds);
-        for (int i = tid; i < LDSF / 4; i += NTH) dst[i] = src[i];
-        __syncthreads();
-        if constexpr (STAGE == 2) conv_layer<G, 32, 64, CONV_OUT_PACKED, 1>(lds, img2, w.c2, w.c2b, wpos, cellof, wave, lane, blockIdx.y);
-        else conv_layer<G, 64, 128, CONV_OUT3, 1>(lds, img3, w.c3, w.c3b, wpos, cellof, wave, lane, blockIdx.y);
-    } else {
-        const float4 *src = reinterpret_cast<const float4 *>(img3);
-        float4 *dst = reinterpret_cast<float4 *>(lds);
-        for (int i = tid; i < LDSF / 4; i += NTH) dst[i] = src[i];
-        __syncthreads();
-        const int q = lane >> 4, r16 = lane & 15;
-        const float4 *wp4 = reinterpret_cast<const float4 *>(w.hd) + lane;
-        float hb[4];
-#pragma unroll
-        for (int rg = 0; rg < 4; rg++) hb[rg] = (q * 4 + rg) < 6 ? w.hdb[q * 4 + rg] : 0.0f;
-        for (int mt = wave; mt < G::MT; mt += G::NW) {
-            f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-            const float *ip = lds + q * G::CS3 + mt * 16 + r16;
-#pragma unroll
-            for (int s4 = 0; s4 < 8; s4++) {
-                const float4 bq = wp4[s4 * 64];
-                acc = mfma4(bq.x, ip[(s4 * 16 + 0) * G::CS3], acc);
-                acc = mfma4(bq.y, ip[(s4 * 16 + 4) * G::CS3], acc);
-                acc = mfma4(bq.z, ip[(s4 * 16 + 8) * G::CS3], acc);
-                acc = mfma4(bq.w, ip[(s4 * 16 + 12) * G::CS3], acc);
-            }
-            const int cell = cellof[mt * 16 + r16];
-            if (cell != 0xFFFF) {
-                const int g = cell / G::nn, p = cell - g * G::nn;
-                const int b = b0 + g;
-                if (b < d.B && d.s_net[b] == net_id) {
-#pragma unroll
-                    for (int rg = 0; rg < 4; rg++) {
-                        const int j = q * 4 + rg;
-                        if (j < 6) {
-                            float v = acc[rg] + hb[rg];
-                            feat[(size_t)b * G::FROW + j * G::nn + p] = v > 0.0f ? v : 0.0f;
-                        }
-                    }
-                }
-            }
-        }
     }
 }
 
 // ------------------------------------------------------------------------------------------------
-// Tile-split trunk (GomokuNet): the low-latency path, round 3.  k_split above spreads a board over workgroups by CHANNEL
-// tiles, so every layer is a launch (each needs all channels of its input), conv3 runs 2 x 144 MFMAs per wave and the
-// 1x1 heads need a fourth launch that reads the whole 123 KB conv3 image back.  Measured at one pending board
-// (profiles/r03_*): 4.6 + 9.0 + 15.2 + 8.6 us of kernels per evaluation, launch gaps ~0.3 us each -- the gaps are not the
-// cost, the kernels are.  Here a board is spread by CELL tiles (one 16-cell MFMA tile = one board row at n = 15):
+// Tile-split trunk (GomokuNet): the low-latency path for launches with few pending boards (episode tails, the arena,
+// single-position search).  The fused k_trunk keeps a board on ONE CU (~95 us of paced MFMAs at n = 15); here a board is
+// spread over workgroups by CELL tiles (one 16-cell MFMA tile = one board row at n = 15):
 //   stage A  grid (groups, MT): encode the rows around tile t, conv1 on the <= 4 tiles conv2 needs (recomputed per
 //            workgroup: 9 k-steps), conv2 on tile t (4 waves x 72 MFMAs)        -> img2, the packed 64-channel board image
 //   stage B  grid (groups, MT): the rows of img2 around tile t -> conv3 on tile t (8 waves x 144 MFMAs: all 128 channels of
 //            the tile's cells are in THIS workgroup) -> 1x1 heads of the tile (32 MFMAs) -> feature rows
-// Two launches instead of four, no conv3 image, 16-24 KB of LDS per workgroup (several per CU).  Every output element is
-// the same k-ordered fma chain as in k_trunk -- which workgroup computes it does not enter -- so the results are
-// bit-identical (every parity test runs on this path too).
+// img2 crosses HBM/L2 in scratch, one image per board group (padding ring zeroed once at allocation, never written); 16-24 KB
+// of LDS per workgroup (several per CU).  Every output element is the same k-ordered fma chain as in k_trunk -- which
+// workgroup computes it does not enter -- so the results are bit-identical.
 // ------------------------------------------------------------------------------------------------
 template <class F, int NWT>
 struct TileGeoT {
@@ -872,18 +663,18 @@ struct TileGeoT {
     }
 };
 template <int N>
-struct TileGeo : TileGeoT<NetGeo<N>, AZ_NW> {
-    typedef TileGeoT<NetGeo<N>, AZ_NW> T;
+struct TileGeo : TileGeoT<NetGeo<N>, NetGeo<N>::NW> {
+    typedef TileGeoT<NetGeo<N>, NetGeo<N>::NW> T;
     static constexpr int LDSA = 36 * T::CSA, LDSB = 64 * T::CSB + 128 * 16;
+    static constexpr int SCRATCH = 64 * NetGeo<N>::CS;        // floats of scratch per board group: img2
 };
 
 template <int N, int STAGE>
-__global__ __launch_bounds__(AZ_NW * 64) void k_tile(DevState d, NetWeights w, int net_id, float *__restrict__ scratch,
+__global__ __launch_bounds__(NetGeo<N>::NW * 64) void k_tile(DevState d, NetWeights w, int net_id, float *__restrict__ scratch,
                                                      float *__restrict__ feat)
 {
     typedef NetGeo<N> F;
     typedef TileGeo<N> TG;
-    typedef SplitGeo<N> SG;
     constexpr int NTH = F::NW * 64;
     __shared__ __attribute__((aligned(16))) float lds[STAGE == 1 ? TG::LDSA : TG::LDSB];
     __shared__ unsigned short wpos[F::MR];      // centre of tile lane m RELATIVE to this workgroup's image origin
@@ -898,20 +689,20 @@ __global__ __launch_bounds__(AZ_NW * 64) void k_tile(DevState d, NetWeights w, i
         for (int i = tid; i < TG::LDSA / 4; i += NTH) z[i] = float4{0.f, 0.f, 0.f, 0.f};
     }
     if (!TG::prologue(d, net_id, b0, org, STAGE == 1 ? TG::CSA : TG::CSB, wpos, cellof, &any_active, tid, NTH)) return;
-    float *img2 = scratch + (size_t)grp * SG::PER_GROUP + SG::IMG1;      // the packed 64-channel board image (padding ring zeroed once)
+    float *img2 = scratch + (size_t)grp * TG::SCRATCH;      // the packed 64-channel board image (padding ring zeroed once)
     if constexpr (STAGE == 1) {
         float *planes = lds, *img1 = lds + 4 * TG::CSA;
         TG::encode(d, b0, org, TG::CSA, planes, cellof, tid, NTH);
         __syncthreads();
         const int tlo = TG::c1_lo(t), cnt = TG::c1_hi(t) - tlo + 1;
-        conv_layer<typename TG::A, 4, 32, CONV_OUT_PACKED, 2, TG::MTL1>(planes, img1, w.c1, w.c1b, wpos, cellof, wave, lane, 0, tlo, cnt);
+        conv_layer<typename TG::A, 4, 32, CONV_OUT_PACKED, TG::MTL1>(planes, img1, w.c1, w.c1b, wpos, cellof, wave, lane, tlo, cnt);
         __syncthreads();
-        conv_layer<typename TG::A, 32, 64, CONV_OUT_PACKED, 4, 1, F>(img1, img2, w.c2, w.c2b, wpos, cellof, wave, lane, 0, t, 1, org);
+        conv_layer<typename TG::A, 32, 64, CONV_OUT_PACKED, 1, F>(img1, img2, w.c2, w.c2b, wpos, cellof, wave, lane, t, 1, org);
     } else {
         TG::load_rows(img2, org, lds, tid, NTH);              // the rows of the conv2 image this tile's windows touch
         __syncthreads();
         float *out3 = lds + 64 * TG::CSB;                     // [co][16 cells of the tile]
-        conv_layer<typename TG::B, 64, 128, CONV_OUT3, 8, 1, typename TG::B, 16>(lds, out3, w.c3, w.c3b, wpos, cellof, wave, lane, 0, t, 1);
+        conv_layer<typename TG::B, 64, 128, CONV_OUT3, 1, typename TG::B, 16>(lds, out3, w.c3, w.c3b, wpos, cellof, wave, lane, t, 1);
         __syncthreads();
         if (wave == 0) {                                      // policy_conv (128->4) and value_conv (128->2) of the tile's cells
             const int q = lane >> 4, r16 = lane & 15;
@@ -1071,140 +862,10 @@ __global__ __launch_bounds__(ResGeo<N>::NW * 64) void k_trunk_res(DevState d, Re
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Split trunk for the ResidualBlock net: the low-latency path (few pending boards: the arena, episode tails, single
-// searches), like k_split for GomokuNet.  Every conv is its own launch and a board group's four 16-channel tiles go to
-// four workgroups; the 64-channel packed images A (block input/output) and B (intermediate) cross HBM/L2 in the scratch
-// of the group (padding ring zeroed once at allocation, never written).  Same fma chains as k_trunk_res: bit-identical.
-//   KIND 0: encode + stem             grid (groups, 4) -> A
-//   KIND 1: block conv1               grid (groups, 4)    A -> B
-//   KIND 2: block conv2 + skip, ReLU  grid (groups, 4)    B -> A (in place: a workgroup reads and writes only its own channel tile of A)
-//   KIND 3: 1x1 heads                 grid (groups)       A -> feature rows
-// ------------------------------------------------------------------------------------------------
-template <int N>
-struct ResSplitGeo {
-    typedef ResGeo<N> G;
-    static constexpr int IMG = 64 * G::CS;
-    static constexpr int PER_GROUP = 2 * IMG;                 // floats of scratch per board group
-};
-
-template <class G>
-__device__ __forceinline__ bool split_prologue_g(const DevState &d, int net_id, int b0, unsigned short *wpos,
-                                                 unsigned short *cellof, int *any_active, int tid)
-{
-    if (tid == 0) *any_active = 0;
-    __syncthreads();
-    if (tid < G::G) {
-        int b = b0 + tid;
-        if (b < d.B) {
-            int kind = d.leaf_kind[b];
-            if (leaf_needs_net(kind) && d.s_status[b] == SLOT_ACTIVE && d.s_net[b] == net_id) atomicOr(any_active, 1);
-        }
-    }
-    for (int m = tid; m < G::MR; m += G::NW * 64) {
-        int pos, cell;
-        if constexpr (G::ROWT) {
-            const int t = m >> 4, c = m & 15, g = t / G::n, r = t - g * G::n;
-            pos = g * G::PP + (r + 1) * G::PW + (c + 1);
-            cell = c < G::n ? g * G::nn + r * G::n + c : 0xFFFF;
-        } else {
-            const int g = m / G::nn, p = m - g * G::nn, r = p / G::n, c = p - r * G::n;
-            pos = m < G::M ? g * G::PP + (r + 1) * G::PW + (c + 1) : G::PW + 1;
-            cell = m < G::M ? m : 0xFFFF;
-        }
-        wpos[m] = (unsigned short)pos;
-        cellof[m] = (unsigned short)cell;
-    }
-    __syncthreads();
-    return *any_active != 0;
-}
-
-template <int N, int KIND>
-__global__ __launch_bounds__(ResGeo<N>::NW * 64) void k_split_res(DevState d, const float *__restrict__ wp, const float *__restrict__ bias,
-                                                                  int net_id, float *__restrict__ scratch, float *__restrict__ feat)
-{
-    typedef ResGeo<N> G;
-    constexpr int NTH = G::NW * 64;
-    constexpr int LDSF = KIND == 0 ? 4 * G::CS : 64 * G::CS;
-    __shared__ __attribute__((aligned(16))) float lds[LDSF];
-    __shared__ unsigned short wpos[G::MR];
-    __shared__ unsigned short cellof[G::MR];
-    __shared__ int any_active;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = blockIdx.x, b0 = grp * G::G;
-    if (!split_prologue_g<G>(d, net_id, b0, wpos, cellof, &any_active, tid)) return;
-    float *A = scratch + (size_t)grp * ResSplitGeo<N>::PER_GROUP, *B = A + ResSplitGeo<N>::IMG;
-    if constexpr (KIND == 0) {
-        for (int i = tid; i < LDSF; i += NTH) lds[i] = 0.0f;
-        __syncthreads();
-        for (int m = tid; m < G::MR; m += NTH) {          // games.py:86-129 encode
-            const int cell = cellof[m];
-            if (cell != 0xFFFF) {
-                const int g = cell / G::nn, p = cell - g * G::nn;
-                const int b = b0 + g;
-                if (b < d.B) {
-                    const u64 *lf = d.leaf + (size_t)b * 8;
-                    const int pos = wpos[m];
-                    const int ps = sym_cell(d.leaf_sym, b, p, G::n);
-                    if ((lf[ps >> 6] >> (ps & 63)) & 1ull) lds[pos] = 1.0f;
-                    if ((lf[4 + (ps >> 6)] >> (ps & 63)) & 1ull) lds[G::CS + pos] = 1.0f;
-                    if (d.leaf_last[b] == ps) lds[2 * G::CS + pos] = 1.0f;
-                }
-            }
-        }
-        __syncthreads();
-        conv_layer<G, 4, 64, CONV_OUT_PACKED, 1>(lds, A, wp, bias, wpos, cellof, wave, lane, blockIdx.y);
-    } else {
-        const float4 *src = reinterpret_cast<const float4 *>(KIND == 2 ? B : A);
-        float4 *dst = reinterpret_cast<float4 *>(lds);
-        for (int i = tid; i < LDSF / 4; i += NTH) dst[i] = src[i];
-        __syncthreads();
-        if constexpr (KIND == 1) conv_layer<G, 64, 64, CONV_OUT_PACKED, 1>(lds, B, wp, bias, wpos, cellof, wave, lane, blockIdx.y);
-        else if constexpr (KIND == 2) conv_layer<G, 64, 64, CONV_OUT_RESIDUAL, 1>(lds, A, wp, bias, wpos, cellof, wave, lane, blockIdx.y);
-        else {
-            // heads: D[head channel][cell] over the packed trunk image, 16 k-steps (64 channels); wp = packed head rows, bias = folded biases [3]
-            const int q = lane >> 4, r16 = lane & 15;
-            const float4 *wp4 = reinterpret_cast<const float4 *>(wp) + lane;
-            const float4 *in4 = reinterpret_cast<const float4 *>(lds);
-            float hb[4];
-#pragma unroll
-            for (int rg = 0; rg < 4; rg++) hb[rg] = (q * 4 + rg) < (G::PC + G::VC) ? bias[q * 4 + rg] : 0.0f;
-            for (int mt = wave; mt < G::MT; mt += G::NW) {
-                f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-                const int base = q * G::CS + (int)wpos[mt * 16 + r16];
-#pragma unroll
-                for (int cg = 0; cg < 4; cg++) {
-                    const float4 a = in4[base + cg * 4 * G::CS];
-                    const float4 wq = wp4[cg * 64];
-                    acc = mfma4(wq.x, a.x, acc);
-                    acc = mfma4(wq.y, a.y, acc);
-                    acc = mfma4(wq.z, a.z, acc);
-                    acc = mfma4(wq.w, a.w, acc);
-                }
-                const int cell = cellof[mt * 16 + r16];
-                if (cell != 0xFFFF) {
-                    const int g = cell / G::nn, p = cell - g * G::nn;
-                    const int b = b0 + g;
-                    if (b < d.B && d.s_net[b] == net_id) {
-#pragma unroll
-                        for (int rg = 0; rg < 4; rg++) {
-                            const int j = q * 4 + rg;     // 0-1 policy_conv, 2 value_conv
-                            if (j < G::PC + G::VC) {
-                                float v = acc[rg] + hb[rg];
-                                feat[(size_t)b * G::FROW + j * G::nn + p] = v > 0.0f ? v : 0.0f;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-    }
-}
-
 // Tile-split trunk of the ResidualBlock variant: like k_tile, a board spread by CELL tiles, 4 waves per workgroup (the four
-// 16-channel tiles of a 64-channel conv on one 16-cell tile: 144 dependent MFMAs each), grid (groups, MT).  Six launches
-// instead of k_split_res's eight:
+// 16-channel tiles of a 64-channel conv on one 16-cell tile: 144 dependent MFMAs each), grid (groups, MT), six launches.
+// The 64-channel packed images A (block input/output) and B (intermediate) cross HBM/L2 in the scratch of the board group
+// (padding ring zeroed once at allocation, never written):
 //   KIND 0  encode + stem on the tiles around t (recomputed per workgroup: 9 k-steps) -> x of tile t to image A; res1.conv1 on tile t -> image B
 //   KIND 1  rows of B around t -> conv2 of a block on tile t, relu(. + x) with x read and written in place in A
 //   KIND 2  rows of A around t -> conv1 of the next block on tile t -> B
@@ -1214,6 +875,8 @@ template <int N>
 struct ResTileGeo : TileGeoT<ResGeo<N>, 4> {
     typedef TileGeoT<ResGeo<N>, 4> T;
     static constexpr int LDS0 = 68 * T::CSA, LDSC = 64 * T::CSB + 64 * 16;
+    static constexpr int IMG = 64 * ResGeo<N>::CS;            // floats of one packed 64-channel board image
+    static constexpr int SCRATCH = 2 * IMG;                   // floats of scratch per board group: images A and B
 };
 
 template <int N, int KIND>
@@ -1237,13 +900,13 @@ __global__ __launch_bounds__(256) void k_tile_res(DevState d, const float *__res
         for (int i = tid; i < TG::LDS0 / 4; i += NTH) z[i] = float4{0.f, 0.f, 0.f, 0.f};
     }
     if (!TG::prologue(d, net_id, b0, org, KIND == 0 ? TG::CSA : TG::CSB, wpos, cellof, &any_active, tid, NTH)) return;
-    float *A = scratch + (size_t)grp * ResSplitGeo<N>::PER_GROUP, *B = A + ResSplitGeo<N>::IMG;
+    float *A = scratch + (size_t)grp * TG::SCRATCH, *B = A + TG::IMG;
     if constexpr (KIND == 0) {
         float *planes = lds, *x = lds + 4 * TG::CSA;          // x: the stem's output around tile t, packed, local geometry
         TG::encode(d, b0, org, TG::CSA, planes, cellof, tid, NTH);
         __syncthreads();
         const int tlo = TG::c1_lo(t), cnt = TG::c1_hi(t) - tlo + 1;
-        conv_layer<typename TG::A, 4, 64, CONV_OUT_PACKED, 4, TG::MTL1>(planes, x, wp, bias, wpos, cellof, wave, lane, 0, tlo, cnt);
+        conv_layer<typename TG::A, 4, 64, CONV_OUT_PACKED, TG::MTL1>(planes, x, wp, bias, wpos, cellof, wave, lane, tlo, cnt);
         __syncthreads();
         // x of tile t also goes to the board image A: the skip operand of res1 (read in place by KIND 1)
         for (int i = tid; i < 64 * 16; i += NTH) {
@@ -1253,15 +916,15 @@ __global__ __launch_bounds__(256) void k_tile_res(DevState d, const float *__res
                 A[pk_index<F>(co, rel + org)] = x[pk_index<typename TG::A>(co, rel)];
             }
         }
-        conv_layer<typename TG::A, 64, 64, CONV_OUT_PACKED, 4, 1, F>(x, B, wp2, bias2, wpos, cellof, wave, lane, 0, t, 1, org);
+        conv_layer<typename TG::A, 64, 64, CONV_OUT_PACKED, 1, F>(x, B, wp2, bias2, wpos, cellof, wave, lane, t, 1, org);
     } else {
         TG::load_rows(KIND == 2 ? A : B, org, lds, tid, NTH);
         __syncthreads();
-        if constexpr (KIND == 1) conv_layer<typename TG::B, 64, 64, CONV_OUT_RESIDUAL, 4, 1, F>(lds, A, wp, bias, wpos, cellof, wave, lane, 0, t, 1, org);
-        else if constexpr (KIND == 2) conv_layer<typename TG::B, 64, 64, CONV_OUT_PACKED, 4, 1, F>(lds, B, wp, bias, wpos, cellof, wave, lane, 0, t, 1, org);
+        if constexpr (KIND == 1) conv_layer<typename TG::B, 64, 64, CONV_OUT_RESIDUAL, 1, F>(lds, A, wp, bias, wpos, cellof, wave, lane, t, 1, org);
+        else if constexpr (KIND == 2) conv_layer<typename TG::B, 64, 64, CONV_OUT_PACKED, 1, F>(lds, B, wp, bias, wpos, cellof, wave, lane, t, 1, org);
         else {
             float *xt = lds + 64 * TG::CSB;                   // [channel][16 cells of the tile]: the trunk's output
-            conv_layer<typename TG::B, 64, 64, CONV_OUT3_RESIDUAL, 4, 1, F, 16>(lds, xt, wp, bias, wpos, cellof, wave, lane, 0, t, 1, org, A);
+            conv_layer<typename TG::B, 64, 64, CONV_OUT3_RESIDUAL, 1, F, 16>(lds, xt, wp, bias, wpos, cellof, wave, lane, t, 1, org, A);
             __syncthreads();
             if (wave == 0) {                                  // policy_conv (64->2) and value_conv (64->1), BatchNorm folded: wp2 = packed head rows, bias2[3]
                 const int q = lane >> 4, r16 = lane & 15;

@@ -279,7 +279,6 @@ __device__ __forceinline__ void conv_layer_emul(const uint4 *in, void *out, cons
 #pragma unroll
         for (int sq = 0; sq < KBT; sq++) {
             const int kb = tap * KBT + sq;
-#if AZ_PRIO_ALT
             // the waves sharing a SIMD take turns with the issue priority, K-block by K-block (az_net.h conv_layer: left alone,
             // one of them wins every arbitration and leaves its partner to finish the layer alone); measured: f16x2 8.24 -> 8.52 M
             // expansions/s, bf16x3 unchanged
@@ -287,7 +286,6 @@ __device__ __forceinline__ void conv_layer_emul(const uint4 *in, void *out, cons
                 if ((kb % (G::NW / 4)) == ((wave >> 2) % (G::NW / 4))) __builtin_amdgcn_s_setprio(1);
                 else __builtin_amdgcn_s_setprio(0);
             }
-#endif
             emul_weights<KB, NS>(wp, ng, kb + 1 < KB ? kb + 1 : kb, lane, wn);
             __builtin_amdgcn_sched_barrier(0);         // the next K-block's weights are requested before this block's MFMAs, not after
             const int off = sq * 4 * NS * G::CS + toff;    // a K-block = 4 channel groups x NS part planes
@@ -310,9 +308,7 @@ __device__ __forceinline__ void conv_layer_emul(const uint4 *in, void *out, cons
             for (int s = 0; s < NS; s++) wc[s] = wn[s];
         }
     }
-#if AZ_PRIO_ALT
     if constexpr (emul_prio_turns<G>::value) __builtin_amdgcn_s_setprio(0);
-#endif
     // relu(acc + bias [+ skip]) of the wave's tiles
     float v[MTW][4];
 #pragma unroll
@@ -366,18 +362,16 @@ __device__ __forceinline__ void conv_layer_emul(const uint4 *in, void *out, cons
 }
 
 template <int N, int SCH>
-__global__ __launch_bounds__(AZ_NW * 64) void k_trunk_emul(DevState d, NetWeights w, int net_id, float *__restrict__ feat,
+__global__ __launch_bounds__(NetGeo<N>::NW * 64) void k_trunk_emul(DevState d, NetWeights w, int net_id, float *__restrict__ feat,
                                                            unsigned long long *dbg)
 {
     typedef NetGeo<N> G;
     typedef Emul<SCH> E;
-    constexpr int NTH = AZ_NW * 64, NS = E::NS;
+    constexpr int NTH = G::NW * 64, NS = E::NS;
     constexpr int XF = 32 * NS * G::CS;          // floats of the 64-channel image: 8 channel groups x NS planes of CS 16-byte slots
     static_assert(XF <= G::LDSF, "the split image does not fit the trunk's LDS");
-#ifndef AZ_EXPERIMENT     // experiment builds of the float32 trunk with another wave count never run this kernel
-    static_assert(AZ_NW == 8, "the emulated trunk is laid out for 8 waves: 2 / 4 / 8 channel tiles in conv1 / conv2 / conv3");
-    static_assert(AZ_NW * 6 * G::MR <= G::LDSF, "head-conv partial sums do not fit the trunk's LDS");
-#endif
+    static_assert(G::NW == 8, "the emulated trunk is laid out for 8 waves: 2 / 4 / 8 channel tiles in conv1 / conv2 / conv3");
+    static_assert(G::NW * 6 * G::MR <= G::LDSF, "head-conv partial sums do not fit the trunk's LDS");
     __shared__ __attribute__((aligned(16))) float lds[G::LDSF];
     __shared__ unsigned short wpos[G::MR];
     __shared__ unsigned short cellof[G::MR];
@@ -486,7 +480,7 @@ __global__ __launch_bounds__(AZ_NW * 64) void k_trunk_emul(DevState d, NetWeight
             if (b < d.B && d.s_net[b] == net_id) {
                 float v = lds[o];
 #pragma unroll
-                for (int wv = 1; wv < AZ_NW; wv++) v = v + lds[wv * 6 * G::MR + o];
+                for (int wv = 1; wv < G::NW; wv++) v = v + lds[wv * 6 * G::MR + o];
                 v = v + w.hdb[j];
                 feat[(size_t)b * G::FROW + j * G::nn + p] = v > 0.0f ? v : 0.0f;      // net.py:64,69 flatten order
             }
@@ -503,14 +497,11 @@ __global__ __launch_bounds__(AZ_NW * 64) void k_trunk_emul(DevState d, NetWeight
 // float32 registers (`keep`) from the epilogue that produced them to the epilogue that adds them (relu(conv2(h) + b + x)).
 // First K-block fragments and biases of layer l + 1 are requested before layer l runs.
 // ------------------------------------------------------------------------------------------------
-#ifndef AZ_RES_EMUL_NW
-#define AZ_RES_EMUL_NW 8       // waves per workgroup of the emulated ResidualBlock trunk (0 = as k_trunk_res: 12 at n = 15).  Measured at n = 15:
-                              // 8 waves (4 channel tiles x 2 cell groups of 8 / 7 tiles, 256 VGPRs) 107.3 us per 256 boards, 12 waves (x 3 groups
-                              // of 5, no surplus tile, 168 VGPRs and a 5-dword spill) 109.6 us
-#endif
 template <int N>
 struct ResGeoEmul : ResGeo<N> {
-    static constexpr int NW = AZ_RES_EMUL_NW ? AZ_RES_EMUL_NW : ResGeo<N>::NW;
+    // 8 waves at every size (k_trunk_res: 12 at n = 15).  Measured at n = 15: 8 waves (4 channel tiles x 2 cell groups of 8 / 7
+    // tiles, 256 VGPRs) 107.3 us per 256 boards, 12 waves (x 3 groups of 5, no surplus tile, 168 VGPRs and a 5-dword spill) 109.6 us
+    static constexpr int NW = 8;
     static constexpr bool EMUL_PRIO_TURNS = false;    // measured: the turns cost this kernel 4 % (f16x2 is at the register limit: they spill)
 };
 

@@ -44,7 +44,7 @@ struct PersistGeo {
     // plain net: conv1 / conv2 outputs (32 + 64 channels) with conv3's [co][cell] image on top; ResidualBlock net: two 64-channel images
     static constexpr int LDSF = RES ? 128 * CS : ((96 * CS > 128 * CS3) ? 96 * CS : 128 * CS3);
     static constexpr int RW = ((nn + 63) / 64) * 64;
-    static constexpr int NW = AZ_NW;
+    static constexpr int NW = NetGeo<N>::NW;
     static constexpr int PC = RES ? 2 : 4, VC = RES ? 1 : 2;
     static constexpr int FROW = (((PC + VC) * nn + 3) / 4) * 4;
     static constexpr int PATH = nn + 1;
@@ -322,7 +322,7 @@ __device__ __forceinline__ void fc_mfma(const FcPre<NG> &pre, const float *featl
 // weights, w0 / w1 only the FC layers'.  The reference's trained ResidualBlock checkpoints are 5x5 nets.
 struct NoWeights { };
 template <int N, int GP, bool SYNTH, bool TS = false, bool RES = false>
-__global__ __launch_bounds__(AZ_NW * 64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search(DevState d, NetWeights w0, NetWeights w1, unsigned long long *dbg,
+__global__ __launch_bounds__(NetGeo<N>::NW * 64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search(DevState d, NetWeights w0, NetWeights w1, unsigned long long *dbg,
                                                                                                   std::conditional_t<RES, ResWeights, NoWeights> r0,
                                                                                                   std::conditional_t<RES, ResWeights, NoWeights> r1)
 {
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(AZ_NW * 64) __attribute__((amdgpu_waves_per_eu(1, 2
     typedef TreeGeo<N> TG;
     constexpr int HK = RES ? 4 : 8;                      // k-groups of 16 channels the head convs run over (64 / 128 input channels)
     constexpr int HC = PG::PC + PG::VC;                  // head channels
-    constexpr int NTH = AZ_NW * 64;
+    constexpr int NTH = PG::NW * 64;
     static_assert(NTH == 512, "hd_lds is filled by one float4 per thread");
     __shared__ __attribute__((aligned(16))) float lds[PG::LDSF];
     __shared__ unsigned short wpos[PG::MR];
@@ -476,7 +476,7 @@ __global__ __launch_bounds__(AZ_NW * 64) __attribute__((amdgpu_waves_per_eu(1, 2
                 w.pf = o ? w1.pf : w0.pf; w.vf = o ? w1.vf : w0.vf; w.c1b = o ? w1.c1b : w0.c1b; w.c2b = o ? w1.c2b : w0.c2b;
                 w.c3b = o ? w1.c3b : w0.c3b; w.hdb = o ? w1.hdb : w0.hdb; w.pfb = o ? w1.pfb : w0.pfb; w.vfb = o ? w1.vfb : w0.vfb;
             }
-            ConvPre<32, 4> pre2;
+            ConvPre<32> pre2;
             if constexpr (!RES) pre2 = conv_prefetch<PG, 32, 64>(w.c2, wave, lane);     // conv2's first weights: asked for three phases early
             // ---- leaf encode + conv trunk, as trunk_group (az_net.h) on the LDS-resident leaves ----
             for (int i = tid; i < 3 * PG::CS; i += NTH) {       // games.py:86-129 encode: every position of the three planes, padding = 0
@@ -506,28 +506,28 @@ __global__ __launch_bounds__(AZ_NW * 64) __attribute__((amdgpu_waves_per_eu(1, 2
                     // never written, so it needs no clearing between evaluations
                     const bool o = wg_net != 0;
                     float *A = lds, *B = lds + 64 * PG::CS;
-                    conv_layer<PG, 4, 64, CONV_OUT_PACKED, 4, MTL>(planes, A, o ? r1.stem : r0.stem, o ? r1.stemb : r0.stemb, wpos, cellof, wave, lane, 0, mt_base, MTL);
+                    conv_layer<PG, 4, 64, CONV_OUT_PACKED, MTL>(planes, A, o ? r1.stem : r0.stem, o ? r1.stemb : r0.stemb, wpos, cellof, wave, lane, mt_base, MTL);
                     __syncthreads();
                     KS_STAMP(3);
 #pragma unroll 1
                     for (int blk = 0; blk < 3; blk++) {        // (asking for a conv's first weights a layer early measured equal here: not done)
-                        conv_layer<PG, 64, 64, CONV_OUT_PACKED, 4, MTL>(A, B, o ? r1.blk[2 * blk] : r0.blk[2 * blk], o ? r1.blkb[2 * blk] : r0.blkb[2 * blk], wpos,
-                                                                        cellof, wave, lane, 0, mt_base, MTL);
+                        conv_layer<PG, 64, 64, CONV_OUT_PACKED, MTL>(A, B, o ? r1.blk[2 * blk] : r0.blk[2 * blk], o ? r1.blkb[2 * blk] : r0.blkb[2 * blk], wpos,
+                                                                     cellof, wave, lane, mt_base, MTL);
                         __syncthreads();
-                        conv_layer<PG, 64, 64, CONV_OUT_RESIDUAL, 4, MTL>(B, A, o ? r1.blk[2 * blk + 1] : r0.blk[2 * blk + 1],
-                                                                          o ? r1.blkb[2 * blk + 1] : r0.blkb[2 * blk + 1], wpos, cellof, wave, lane, 0, mt_base, MTL);
+                        conv_layer<PG, 64, 64, CONV_OUT_RESIDUAL, MTL>(B, A, o ? r1.blk[2 * blk + 1] : r0.blk[2 * blk + 1],
+                                                                       o ? r1.blkb[2 * blk + 1] : r0.blkb[2 * blk + 1], wpos, cellof, wave, lane, mt_base, MTL);
                         __syncthreads();
                     }
                     KS_STAMP(5);
                 } else {
-                    conv_layer<PG, 4, 32, CONV_OUT_PACKED, 2, MTL>(planes, inA, w.c1, w.c1b, wpos, cellof, wave, lane, 0, mt_base, MTL);
+                    conv_layer<PG, 4, 32, CONV_OUT_PACKED, MTL>(planes, inA, w.c1, w.c1b, wpos, cellof, wave, lane, mt_base, MTL);
                     __syncthreads();
                     KS_STAMP(3);
-                    const ConvPre<64, 8> pre3 = conv_prefetch<PG, 64, 128>(w.c3, wave, lane);    // ... conv3's while conv2 runs
-                    conv_layer<PG, 32, 64, CONV_OUT_PACKED, 4, MTL>(inA, inB, w.c2, w.c2b, wpos, cellof, wave, lane, 0, mt_base, MTL, 0, nullptr, nullptr, &pre2);
+                    const ConvPre<64> pre3 = conv_prefetch<PG, 64, 128>(w.c3, wave, lane);    // ... conv3's while conv2 runs
+                    conv_layer<PG, 32, 64, CONV_OUT_PACKED, MTL>(inA, inB, w.c2, w.c2b, wpos, cellof, wave, lane, mt_base, MTL, 0, nullptr, nullptr, &pre2);
                     __syncthreads();
                     KS_STAMP(4);
-                    conv_layer<PG, 64, 128, CONV_OUT3, 8, MTL>(inB, lds, w.c3, w.c3b, wpos, cellof, wave, lane, 0, mt_base, MTL, 0, nullptr, nullptr, &pre3);
+                    conv_layer<PG, 64, 128, CONV_OUT3, MTL>(inB, lds, w.c3, w.c3b, wpos, cellof, wave, lane, mt_base, MTL, 0, nullptr, nullptr, &pre3);
                     __syncthreads();
                     KS_STAMP(5);
                 }
@@ -539,7 +539,7 @@ __global__ __launch_bounds__(AZ_NW * 64) __attribute__((amdgpu_waves_per_eu(1, 2
                 float hb[4];
 #pragma unroll
                 for (int rg = 0; rg < 4; rg++) hb[rg] = (q * 4 + rg) < HC ? hdb_lds[q * 4 + rg] : 0.0f;
-                for (int lt = wave; lt < MTL; lt += AZ_NW) {
+                for (int lt = wave; lt < MTL; lt += PG::NW) {
                     const int mt = mt_base + lt;
                     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
                     if constexpr (RES) {

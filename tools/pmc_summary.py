@@ -13,7 +13,7 @@ meta = {}
 for path in args:
     for r in csv.DictReader(open(path)):
         k = r["Kernel_Name"].split("(")[0].replace("void ", "")
-        if not any(t in k for t in ("k_trunk", "k_fc", "k_step", "k_search", "k_split")):
+        if not any(t in k for t in ("k_trunk", "k_fc", "k_step", "k_search")):
             continue
         acc[k][r["Counter_Name"]].append(float(r["Counter_Value"]))
         meta[k] = {"grid": int(r["Grid_Size"]), "workgroup": int(r["Workgroup_Size"]), "lds_bytes": int(r["LDS_Block_Size"]),
