@@ -16,9 +16,13 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // ---------------------------------------------------------------------------------------
 // canonical math (same operation sequence as the reference restatement used for testing)
 // ---------------------------------------------------------------------------------------
+// az_expf underflows gradually, as torch.softmax's exp does: on [-104, -87) the result is a subnormal
+// (or 0 below 2^-150), formed as (p * 2^(k+64)) * 2^-64 so that it is rounded once.  The first product
+// is an exact normal; the second is the only rounding.  For x >= -87 the operations are unchanged.
+// The CPU oracle restates the same sequence.  Needs f32 denormals kept (hipcc's default mode).
 __device__ __forceinline__ float az_expf(float x)
 {
-    if (x < -87.0f) return 0.0f;
+    if (x < -104.0f) return 0.0f;
     if (x > 88.0f) x = 88.0f;
     float t = x * 1.44269504088896341f;
     float kf = __builtin_rintf(t);
@@ -33,6 +37,7 @@ __device__ __forceinline__ float az_expf(float x)
     p = __builtin_fmaf(p, r, 1.0f);
     p = __builtin_fmaf(p, r, 1.0f);
     int k = (int)kf;
+    if (x < -87.0f) return (p * __uint_as_float((unsigned)(k + 64 + 127) << 23)) * 0x1p-64f;
     return p * __uint_as_float((unsigned)(k + 127) << 23);
 }
 
@@ -44,6 +49,8 @@ __device__ __forceinline__ float az_tanhf(float x)
     return x < 0.0f ? -r : r;
 }
 
+// The float64 form keeps its hard clamp at -708 (no gradual underflow): it only feeds the tempered
+// visit-count softmax of pi, whose float32 records cannot hold anything below e^-708 relative to 1.
 __device__ __forceinline__ double az_exp(double x)
 {
     if (x < -708.0) return 0.0;

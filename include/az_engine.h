@@ -324,7 +324,10 @@ int az_set_leaf_symmetry(az_engine *e, int on);
  *   AZ_TRUNK_F16X2   two float16 parts per operand (the low part scaled by 2^11), three cross products in two accumulators:
  *                    5.3 x ceiling; float16's range -- activations saturate at 65504 and a weight set with |w| >= 65504 is
  *                    refused (AZ_ERR_INVALID from this call or from the next az_load_weights*, which puts the engine back on
- *                    AZ_TRUNK_F32).
+ *                    AZ_TRUNK_F32).  The saturation is silent: a net whose weights pass that check but whose activations
+ *                    exceed 65504 gets clipped logits with no error.  At the low end the split resolves an operand to an
+ *                    absolute ~2^-36 below |x| = 2^-14 (float16 subnormals) instead of the relative 2^-22 above it
+ *                    (tests/numeric.py derives both terms of the bound).
  * Both give float32-like accuracy (|logit| 2e-5, |P| 1e-6, |value| 2e-6 against the oracle, the tolerances already granted
  * against the Python reference's torch numbers), NOT bit-identical results, so visit counts can differ from the reference's
  * on near-tied PUCT scores (measured: DESIGN.md section 4).  One kernel for every occupancy (no split / persistent variants),

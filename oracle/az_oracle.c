@@ -41,9 +41,12 @@
 enum { RES_NONE = 0, RES_X = 1, RES_O = 2, RES_DRAW = 3 };
 
 /* ------------------------------------------------------------------ deterministic math */
+/* Gradual underflow like torch.softmax's exp: on [-104, -87) the result is (p * 2^(k+64)) * 2^-64, an exact
+ * normal product and then ONE rounding into the subnormal range (0 below 2^-150).  x >= -87 is unchanged.
+ * Same sequence as az_expf in csrc/az_device.h. */
 static float orc_expf(float x)
 {
-    if (x < -87.0f) return 0.0f;
+    if (x < -104.0f) return 0.0f;
     if (x > 88.0f) x = 88.0f;
     float t = x * 1.44269504088896341f;
     float kf = rintf(t);
@@ -59,6 +62,10 @@ static float orc_expf(float x)
     p = fmaf(p, r, 1.0f);
     int k = (int)kf;
     union { uint32_t u; float f; } s;
+    if (x < -87.0f) {
+        s.u = (uint32_t)(k + 64 + 127) << 23;
+        return (p * s.f) * 0x1p-64f;
+    }
     s.u = (uint32_t)(k + 127) << 23;
     return p * s.f;
 }
@@ -71,6 +78,8 @@ static float orc_tanhf(float x)
     return x < 0.0f ? -r : r;
 }
 
+/* The float64 form keeps its hard clamp at -708 (no gradual underflow): it only feeds the tempered visit-count
+ * softmax of pi, whose float32 records cannot hold anything below e^-708 relative to 1. */
 static double orc_exp(double x)
 {
     if (x < -708.0) return 0.0;

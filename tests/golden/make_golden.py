@@ -20,6 +20,8 @@ Fixture families:
   G7 zlabels.json           the z truth table of alphazero/tests/tests.py:11-22
   G4-full netgame_full_{n}x{k}.npz  real-net plies at the BASELINE search sizes: 15x15/400 sims (7 plies), 9x9/200 sims (24 plies)
   G4-complete netgame_complete_15x5.npz  ONE whole reference game at 15x15 / 400 sims (python make_golden.py complete)
+  G10 netgame_confident_5x4.npz  G4 with the trained 5x5 checkpoint under C_{5,4}: zero / subnormal priors, values of +-1
+                                 (python make_golden.py edge; writes this file only)
   G8 resnet_ckpt_5.npz      the VALUES of one historical ResidualBlock checkpoint of the reference (weights-only load of
                             alphazero/models/old/model_20250728_225053.pt: data, no code) + the outputs of the BUILD's torch module
                             loaded with them (the reference ships no forward for this variant)  (python make_golden.py resnet)
@@ -539,7 +541,130 @@ def worker_resnet_checkpoint():
     print("resnet_ckpt_5.npz written:", len(sd), "tensors,", float(v.abs().max()), "max |value|")
 
 
+def confidence(sd, p, v):
+    """C_{p,v} (tests/numeric.py restates it): policy_fc times 2^p, value_fc2 times 2^v, weight and bias alike."""
+    out = {k: np.array(w, np.float32, copy=True) for k, w in sd.items()}
+    for k in ("policy_fc.weight", "policy_fc.bias"):
+        out[k] = out[k] * np.float32(2.0 ** p)
+    for k in ("value_fc2.weight", "value_fc2.bias"):
+        out[k] = out[k] * np.float32(2.0 ** v)
+    return out
+
+
+EDGE_CONF, EDGE_GAMES = (5, 4), 8        # C_{5,4}: the first of its 8 games with a flush-sensitive ply is the 8th
+
+
+def worker_edge():
+    """G10 netgame_confident_5x4.npz: the reference's self-play (as G4) with the trained 5x5 checkpoint under C_{5,4}, a
+    net whose priors reach 0 and float32 subnormals and whose values saturate to exactly +-1.  Asserts the fixture is worth
+    having: a legal prior in (0, 2^-126), a value of exactly +-1, and a ply whose visit counts change when the subnormal
+    priors are flushed to 0 (that ply searched again from the same RNG state with a flushing policy_value_fn)."""
+    n, k = 5, 4
+    sys.path.insert(0, REF)
+    import constants
+    constants.BOARD_SIZE, constants.WIN_LENGTH = n, k
+    import torch
+    torch.set_num_threads(1)
+    import mcts as mcts_mod
+    from games import Gomoku
+    from mcts import MCTS
+    from net import GomokuNet
+    from controller import NeuralNetworkController, make_policy_value_fn
+    from self_play import default_temperature_schedule
+    X, DRAW = constants.X, constants.DRAW
+    nn = n * n
+    res_code = {None: 0, X: 1, constants.O: 2, DRAW: 3}
+
+    def abs_board(state):
+        b = np.zeros(nn, dtype=np.uint8)
+        for r in range(n):
+            for q in range(n):
+                if state.board[r][q] is not None:
+                    b[r * n + q] = 1 if state.board[r][q] == X else 2
+        return b
+
+    class Capture:
+        root = None
+    class RecNode(mcts_mod.Node):
+        def __init__(self, state, parent=None, prior=1.0):
+            super().__init__(state, parent, prior)
+            if parent is None:
+                Capture.root = self
+    mcts_mod.Node = RecNode
+
+    sd = torch.load(os.path.join(REF, "models/saved/5x5_4_in_a_row.pt"), map_location="cpu", weights_only=True)
+    sd = confidence({kk: v.numpy().astype(np.float32) for kk, v in sd.items()}, *EDGE_CONF)
+    net = GomokuNet(device="cpu")
+    net.load_state_dict({kk: torch.tensor(v) for kk, v in sd.items()})
+    net.eval()
+    pvf = make_policy_value_fn(NeuralNetworkController(net, device="cpu"))
+    stats = dict(sub_legal=0, sat=0)
+
+    def pvf_seen(state):
+        P, v = pvf(state)
+        legal = np.array([[state.board[r][q] is None for q in range(n)] for r in range(n)])
+        stats["sub_legal"] += int(((P > 0) & (P < 2.0 ** -126) & legal).sum())
+        stats["sat"] += int(abs(v) == 1.0)
+        return P, v
+
+    def pvf_flush(state):
+        P, v = pvf(state)
+        return np.where(P < 2.0 ** -126, np.float32(0), P).astype(P.dtype), v
+
+    def root_N():
+        N = np.zeros(nn, dtype=np.int32)
+        for (r, c), ch in Capture.root.children.items():
+            N[r * n + c] = ch.N
+        return N
+
+    S, seed0, gcount = 100, 950, EDGE_GAMES
+    recs, flushed = [], []
+    for g in range(gcount):
+        np.random.seed(seed0 + g)
+        m = MCTS(pvf_seen, num_simulations=S, c_puct=2.0)
+        s = Gomoku(); mv = 0; hist = []
+        while not s.is_terminal():
+            T = default_temperature_schedule(mv)
+            rng_state = np.random.get_state()
+            pi, a = m.run(s, temperature=T, add_root_noise=True)
+            root = Capture.root
+            N = root_N(); W = np.zeros(nn, dtype=np.float64); P = np.zeros(nn, dtype=np.float32)
+            for (r, c), ch in root.children.items():
+                W[r * n + c] = ch.W; P[r * n + c] = np.float32(ch.prior)
+            after = np.random.get_state()
+            np.random.set_state(rng_state)
+            MCTS(pvf_flush, num_simulations=S, c_puct=2.0).run(s, temperature=T, add_root_noise=True)
+            if not np.array_equal(root_N(), N):
+                flushed.append(len(recs))
+            np.random.set_state(after)
+            recs.append(dict(game=g, ply=mv, board=abs_board(s), player=1 if s.current_player == X else 2,
+                             last=-1 if s.last_action is None else s.last_action[0] * n + s.last_action[1],
+                             pi=pi.astype(np.float32).reshape(nn), N=N, W=W, P=P, action=a[0] * n + a[1], T=float(T)))
+            hist.append(s.current_player)
+            s = s.apply_action(a); mv += 1
+        fin = s.get_game_result()
+        for j, pl in enumerate(hist):
+            recs[len(recs) - len(hist) + j]["z"] = 0 if fin == DRAW else 1 if pl == fin else -1
+        recs[-1]["final"] = res_code[fin]
+    for r_ in recs:
+        r_.setdefault("final", 255)
+    assert stats["sub_legal"] > 0, "no legal prior in (0, 2^-126)"
+    assert stats["sat"] > 0, "no value of exactly +-1"
+    assert flushed, "no ply whose visit counts depend on the subnormal priors"
+    print("netgame_confident_5x4:", len(recs), "plies;", stats, "; plies that change when subnormals are flushed:", flushed)
+    np.savez_compressed(
+        os.path.join(HERE, "netgame_confident_5x4.npz"), n=n, k=k, S=S, seed0=seed0, maxply=nn, weights="ckpt_saved",
+        confidence=np.array([5, 4], np.int32), flush_sensitive=np.array(flushed, np.int32),
+        **{key: np.array([c[key] for c in recs]) for key in recs[0]})
+
+
 if __name__ == "__main__":
+    if len(sys.argv) == 2 and sys.argv[1] == "edge":
+        env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
+        sys.exit(subprocess.call([sys.executable, os.path.abspath(__file__), "edge", "worker"], env=env, cwd="/tmp"))
+    if len(sys.argv) == 3 and sys.argv[1:] == ["edge", "worker"]:
+        worker_edge()
+        sys.exit(0)
     if len(sys.argv) == 2 and sys.argv[1] == "resnet":
         worker_resnet_checkpoint()
     elif len(sys.argv) == 4 and sys.argv[3] in ("full", "complete"):

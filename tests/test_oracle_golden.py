@@ -236,6 +236,10 @@ def test_math_helpers():
     xs = np.linspace(-80, 5, 2001).astype(np.float32)
     got = np.array([L.orc_test_expf(float(x)) for x in xs])
     np.testing.assert_allclose(got, np.exp(xs.astype(np.float64)), rtol=3e-7)
+    # gradual underflow below -87 (the subnormal range, zero below 2^-150), as float64 exp rounded to float32
+    xs = np.linspace(-110, -80, 3001).astype(np.float32)
+    got = np.array([L.orc_test_expf(float(x)) for x in xs])
+    np.testing.assert_allclose(got, np.exp(xs.astype(np.float64)).astype(np.float32), rtol=3e-7, atol=2.0 ** -149)
     xs = np.linspace(-700, 0, 3001)
     got = np.array([L.orc_test_exp(float(x)) for x in xs])
     np.testing.assert_allclose(got, np.exp(xs), rtol=4e-16)
