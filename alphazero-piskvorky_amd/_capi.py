@@ -24,9 +24,11 @@ AZ_RES_NONE, AZ_RES_X, AZ_RES_O, AZ_RES_DRAW = 0, 1, 2, 3
 AZ_AUG_NONE, AZ_AUG_REFERENCE4, AZ_AUG_DIHEDRAL8 = 1, 4, 8
 AZ_MODEL_PLAIN, AZ_MODEL_RESNET = 0, 1
 AZ_TRUNK_F32, AZ_TRUNK_BF16X3, AZ_TRUNK_F16X2 = 0, 1, 2
+AZ_MAX_SIMULATIONS, AZ_DEEP_MAX_SIMULATIONS = 1024, 65534      # az_create | az_create_deep
+REUSE_MAX_SIMULATIONS = 1023                                   # az_set_subtree_reuse
 
 EXPORTS = [
-    "az_create", "az_destroy", "az_last_error", "az_load_weights", "az_load_weights_resnet", "az_net_eval", "az_search", "az_search_callback", "az_selfplay",
+    "az_create", "az_create_deep", "az_destroy", "az_last_error", "az_load_weights", "az_load_weights_resnet", "az_net_eval", "az_search", "az_search_callback", "az_selfplay",
     "az_selfplay_begin", "az_selfplay_step", "az_selfplay_end", "az_selfplay_games", "az_selfplay_records", "az_record_bytes", "az_selfplay_pack", "az_examples_from_packed",
     "az_examples_gather", "az_arena", "az_rules_replay", "az_rng_selfplay_tape", "az_rng_uniforms", "az_set_profiling", "az_set_subtree_reuse", "az_get_counters", "az_get_lanes", "az_get_persistent", "az_set_virtual_loss", "az_set_eval_cache",
     "az_set_trunk_mode", "az_get_trunk_mode", "az_set_leaf_symmetry", "az_emul_split",
@@ -108,6 +110,7 @@ def lib():
         L.az_last_error.restype = C.c_char_p
         L.az_last_error.argtypes = [C.c_void_p]
         L.az_create.argtypes = [C.POINTER(az_config), C.POINTER(C.c_void_p)]
+        L.az_create_deep.argtypes = [C.POINTER(az_config), C.POINTER(C.c_void_p)]
         L.az_destroy.argtypes = [C.c_void_p]
         L.az_destroy.restype = None
         L.az_record_bytes.restype = C.c_int64
@@ -163,11 +166,14 @@ def rng_uniforms(seed, count):
 
 class Engine:
     """One engine per GPU (az_create .. az_destroy).  engines = lanes inside the engine (az_config.engines): the slots
-    are split over that many HIP streams driven by the library's own host threads; 0 lets the library choose."""
+    are split over that many HIP streams driven by the library's own host threads; 0 lets the library choose.
+    deep=True: az_create_deep, num_simulations up to AZ_DEEP_MAX_SIMULATIONS (tree memory grows with it; see
+    include/az_engine.h); up to 1024 simulations the same engine as deep=False."""
 
     def __init__(self, board_size, win_length, num_simulations, slots, c_puct=2.0, dirichlet_alpha=0.3,
-                 dirichlet_weight=0.25, synthetic=False, device=0, log_table=None, model="plain", engines=0):
+                 dirichlet_weight=0.25, synthetic=False, device=0, log_table=None, model="plain", engines=0, deep=False):
         self.n, self.k, self.S, self.slots = board_size, win_length, num_simulations, slots
+        self.deep = bool(deep)
         self.device = int(device)
         if model not in ("plain", "resnet"):
             raise ValueError("model must be 'plain' or 'resnet'")
@@ -181,9 +187,10 @@ class Engine:
                         None if self._log_table is None else self._log_table.ctypes.data_as(C.POINTER(C.c_float)),
                         AZ_MODEL_RESNET if model == "resnet" else AZ_MODEL_PLAIN, int(engines))
         self.h = C.c_void_p()
-        rc = lib().az_create(C.byref(cfg), C.byref(self.h))
+        create = lib().az_create_deep if self.deep else lib().az_create
+        rc = create(C.byref(cfg), C.byref(self.h))
         if rc:
-            raise AzError(f"az_create failed ({rc}): {lib().az_last_error(None).decode()}")
+            raise AzError(f"{'az_create_deep' if self.deep else 'az_create'} failed ({rc}): {lib().az_last_error(None).decode()}")
         self.record_bytes = int(lib().az_record_bytes(self.h))
         self.last_records = 0
 

@@ -57,6 +57,7 @@ struct Lane {
     DevState dv{};                 // the net kernels' view (B = evaluation items = slots x leaves per batch)
     DevBuf board, s_game, s_ply, s_player, s_last, s_status, s_net, edges, rows_used, cnt, active_dev, carried;   // per slot
     DevBuf path, depth, leaf_kind, leaf, leaf_last, logits, vhid, pol_feat, dbg, scratch, it_status, it_net, leaf_sym;       // per evaluation item
+    DevBuf inflight;               // per slot, deep engines with virtual-loss batching only: in-flight count of every edge
     // one ply (k_begin, (S+1) x {trunk, fc, step}, k_move) captured once as a hipGraph and replayed every ply:
     // 3(S+1)+2 launches (6(S+1)+2 with the split trunk) become one submission.  Indexed [split trunk][arena].
     struct PlyGraph {
@@ -90,6 +91,7 @@ struct az_engine {
     int64_t tape_len = 0;          // doubles per game in the noise tape
     bool have_episode = false;
     int reuse = 0;
+    bool deep = false;             // created by az_create_deep: num_simulations up to AZ_DEEP_MAX_SIMULATIONS
     int vl = 1;                    // leaves per game and evaluation batch (az_set_virtual_loss); 1 = the reference's sequential loop
     bool vl_kernel = false;        // the batched tree kernel is in use (vl > 1, or AZ_VL_FORCE=1 to run it with batches of one)
     bool persist_allowed = true;   // AZ_PERSIST=0: never use the persistent search kernel
@@ -141,6 +143,7 @@ static LaunchCtx ctx_of_impl(const az_engine *e, const Lane &L)
     c.feat = (float *)L.pol_feat.p;
     c.dbg = (unsigned long long *)L.dbg.p;
     c.scratch = (float *)L.scratch.p;
+    c.inflight = (unsigned char *)L.inflight.p;
     return c;
 }
 
@@ -575,14 +578,29 @@ static int alloc_items(az_engine *e, Lane &L, int leaves)
     return AZ_OK;
 }
 
-extern "C" int az_create(const az_config *cfg, az_engine **out)
+// Deep engines: device memory that grows with num_simulations has to fit before anything is allocated, so that a search
+// too deep for the device is refused with its byte count instead of failing halfway with AZ_ERR_HIP
+static int deep_memory_guard(const char *what, size_t need, az_engine *e)
+{
+    size_t free_b = 0, total_b = 0;
+    hipError_t hr = hipMemGetInfo(&free_b, &total_b);
+    if (hr != hipSuccess) return fail(e, AZ_ERR_HIP, "hipMemGetInfo failed: %s", hipGetErrorString(hr));
+    if (need > free_b)
+        return fail(e, AZ_ERR_INVALID, "%s needs %zu bytes of device memory, %zu bytes are free", what, need, free_b);
+    return AZ_OK;
+}
+
+static int create_engine(const az_config *cfg, az_engine **out, bool deep)
 {
     if (!cfg || !out) return fail(nullptr, AZ_ERR_INVALID, "null argument");
     *out = nullptr;
     if (cfg->board_size < 3 || cfg->board_size > 15)
         return fail(nullptr, AZ_ERR_INVALID, "board_size must be 3..15 (got %d)", cfg->board_size);
     if (cfg->win_length < 2 || cfg->win_length > cfg->board_size) return fail(nullptr, AZ_ERR_INVALID, "bad win_length");
-    if (cfg->num_simulations < 1 || cfg->num_simulations > 1024) return fail(nullptr, AZ_ERR_INVALID, "num_simulations must be 1..1024");
+    if (!deep && (cfg->num_simulations < 1 || cfg->num_simulations > 1024))
+        return fail(nullptr, AZ_ERR_INVALID, "num_simulations must be 1..1024 (az_create_deep takes up to %d)", AZ_DEEP_MAX_SIMULATIONS);
+    if (deep && (cfg->num_simulations < 1 || cfg->num_simulations > AZ_DEEP_MAX_SIMULATIONS))
+        return fail(nullptr, AZ_ERR_INVALID, "num_simulations must be 1..%d", AZ_DEEP_MAX_SIMULATIONS);
     if (cfg->slots < 1 || cfg->slots > 65536) return fail(nullptr, AZ_ERR_INVALID, "slots must be 1..65536");
     if (cfg->model != AZ_MODEL_PLAIN && cfg->model != AZ_MODEL_RESNET) return fail(nullptr, AZ_ERR_INVALID, "unknown model kind %d", cfg->model);
     if (cfg->engines < 0 || cfg->engines > 16) return fail(nullptr, AZ_ERR_INVALID, "engines must be 0 (auto) .. 16");
@@ -592,6 +610,7 @@ extern "C" int az_create(const az_config *cfg, az_engine **out)
     if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, AZ_ERR_INVALID, "device %d out of range (%d devices)", cfg->device, ndev);
     az_engine *e = new az_engine();
     e->cfg = *cfg;
+    e->deep = deep;
     e->n = cfg->board_size;
     e->nn = e->n * e->n;
     e->RW = (e->nn + 63) / 64 * 64;
@@ -601,6 +620,18 @@ extern "C" int az_create(const az_config *cfg, az_engine **out)
     if (!e->ops) {
         delete e;
         return fail(nullptr, AZ_ERR_INVALID, "board size %d is not built into this library", cfg->board_size);
+    }
+    if (deep) {
+        // what grows with S: every slot's tree, (S + 1) rows of RW edges, and the log / sqrt tables
+        const size_t need = (size_t)cfg->slots * (size_t)e->R * (size_t)e->RW * sizeof(Edge) +
+                            (size_t)(cfg->num_simulations + 3) * (sizeof(float) + sizeof(double));
+        DeviceGuard g(cfg->device);
+        int rc = g.rc != hipSuccess ? fail(nullptr, AZ_ERR_HIP, "hipSetDevice(%d) failed", cfg->device)
+                                    : deep_memory_guard("the trees of this deep engine", need, nullptr);
+        if (rc) {
+            delete e;
+            return rc;
+        }
     }
     int K = cfg->engines > 0 ? cfg->engines : auto_lanes(e->n, cfg->slots);
     if (K > cfg->slots) K = cfg->slots;
@@ -706,6 +737,9 @@ extern "C" int az_create(const az_config *cfg, az_engine **out)
     return AZ_OK;
 }
 
+extern "C" int az_create(const az_config *cfg, az_engine **out) { return create_engine(cfg, out, false); }
+extern "C" int az_create_deep(const az_config *cfg, az_engine **out) { return create_engine(cfg, out, true); }
+
 static void dist_destroy(az_engine *e);
 
 extern "C" void az_destroy(az_engine *e)
@@ -719,7 +753,7 @@ extern "C" void az_destroy(az_engine *e)
     for (Lane &L : e->lanes) {
         DevBuf *all[] = {&L.board, &L.s_game, &L.s_ply, &L.s_player, &L.s_last, &L.s_status, &L.s_net, &L.edges, &L.rows_used,
                          &L.path, &L.depth, &L.leaf_kind, &L.leaf, &L.leaf_last, &L.logits, &L.vhid, &L.pol_feat, &L.cnt,
-                         &L.active_dev, &L.carried, &L.dbg, &L.scratch, &L.it_status, &L.it_net, &L.leaf_sym};
+                         &L.active_dev, &L.carried, &L.dbg, &L.scratch, &L.it_status, &L.it_net, &L.leaf_sym, &L.inflight};
         for (DevBuf *b : all) dev_free(*b);
         for (hipEvent_t ev : L.ev) (void)hipEventDestroy(ev);
         for (int i = 0; i < 4; i++)
@@ -1088,7 +1122,9 @@ static int lane_plies(az_engine *e, Lane &L, int max_steps)
             L.tape_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count();
             if (ev) HIPCHECK_L(L, hipStreamWaitEvent(L.stream, ev, 0));
         }
-        if (e->use_graph && !prof && full) {
+        // a deep search (S > DEFAULT_MAX_S) is launched kernel by kernel instead of as one graph of ~3 (S + 1) nodes per ply
+        // (measured, DESIGN 7b: 5x5 / 1024 slots / S = 1000 runs as fast eagerly as from the graph; a 15x15 search costs 2.5 %)
+        if (e->use_graph && !prof && full && S <= DEFAULT_MAX_S) {
             hipGraphExec_t exec = nullptr;
             int rcg = ply_graph(e, L, lc, use_split, nnets, net, &exec);
             if (rcg) return rcg;
@@ -1703,6 +1739,23 @@ extern "C" int az_set_virtual_loss(az_engine *e, int leaves)
     if (leaves < 1 || leaves > VL_MAX) return fail(e, AZ_ERR_INVALID, "virtual-loss batching supports 1..%d leaves per batch", VL_MAX);
     if (leaves > 1 && e->reuse) return fail(e, AZ_ERR_INVALID, "subtree reuse and virtual-loss batching cannot be combined");
     DEVICE_GUARD(e);
+    // deep search (S > DEFAULT_MAX_S) with batches: the in-flight counts live beside the tree, one byte per edge
+    const bool need_inflight = e->deep && e->cfg.num_simulations > DEFAULT_MAX_S && leaves > 1;
+    if (need_inflight) {
+        size_t need = 0;
+        for (Lane &L : e->lanes)
+            if (!L.inflight.p) need += (size_t)L.d.B * (size_t)e->R * (size_t)e->RW;
+        if (need) {
+            int rc = deep_memory_guard("the in-flight counts of virtual-loss batching", need, e);
+            if (rc) return rc;
+        }
+        for (Lane &L : e->lanes) {
+            int rc = dev_alloc(e, L.inflight, (size_t)L.d.B * (size_t)e->R * (size_t)e->RW);
+            if (rc) return rc;
+        }
+    } else {
+        for (Lane &L : e->lanes) dev_free(L.inflight);
+    }
     if (leaves != e->vl) {
         for (Lane &L : e->lanes) {
             int rc = alloc_items(e, L, leaves);

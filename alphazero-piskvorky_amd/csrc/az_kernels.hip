@@ -78,9 +78,15 @@ void fc(const LaunchCtx &c, int net_id)
     else fc_t<NetGeo<N>>(c, net_id, c.w[net_id], dbgfc);
 }
 
+// S > DEFAULT_MAX_S (deep engines only): the DEEP tree kernels, no LDS sqrt table (az_tree.h)
 void step(const LaunchCtx &c, int rootN, int do_select)
 {
     dim3 g((c.d.B + STEP_WAVES - 1) / STEP_WAVES), b(STEP_WAVES * 64);
+    if (c.d.S > DEFAULT_MAX_S) {
+        if (c.synthetic) hipLaunchKernelGGL((k_step<N, true, true>), g, b, 0, c.stream, c.d, rootN, do_select);
+        else hipLaunchKernelGGL((k_step<N, false, true>), g, b, 0, c.stream, c.d, rootN, do_select);
+        return;
+    }
     const size_t lds = (size_t)(c.d.S + 2) * sizeof(double);   // sqrt table
     if (c.synthetic)
         hipLaunchKernelGGL((k_step<N, true>), g, b, lds, c.stream, c.d, rootN, do_select);
@@ -91,6 +97,11 @@ void step(const LaunchCtx &c, int rootN, int do_select)
 void step_vl(const LaunchCtx &c, int sims_done, int nb_next)
 {
     dim3 g((c.d.B + 3) / 4), b(256);
+    if (c.d.S > DEFAULT_MAX_S) {
+        if (c.synthetic) hipLaunchKernelGGL((k_step_vl<N, true, true, unsigned char *>), g, b, 0, c.stream, c.d, sims_done, nb_next, c.inflight);
+        else hipLaunchKernelGGL((k_step_vl<N, false, true, unsigned char *>), g, b, 0, c.stream, c.d, sims_done, nb_next, c.inflight);
+        return;
+    }
     const size_t lds = (size_t)(c.d.S + 2) * sizeof(double);   // sqrt table
     if (c.synthetic)
         hipLaunchKernelGGL((k_step_vl<N, true>), g, b, lds, c.stream, c.d, sims_done, nb_next);
@@ -128,6 +139,7 @@ int search_prepare_t(int S)
 
 int search_prepare(int S, int games, int synthetic, int model)
 {
+    if (S > DEFAULT_MAX_S) return 0;                   // k_search's static sqrt table holds S + 2 <= 1026 entries
     const bool res = model == 1 && !synthetic;         // the synthetic evaluator has no net: the plain kernels serve it
     if (games == 2) {
         if constexpr (HAS_SEARCH2)

@@ -20,6 +20,7 @@ struct LaunchCtx {
     float *feat;
     unsigned long long *dbg;
     float *scratch;     // split-trunk images, SizeOps::split_floats_per_group floats per board group (or null)
+    unsigned char *inflight;   // deep search (S > DEFAULT_MAX_S) with virtual-loss batching: in-flight count per edge [B][R][RW], else null
 };
 
 struct SizeOps {

@@ -356,7 +356,7 @@ __global__ __launch_bounds__(NetGeo<N>::NW * 64) __attribute__((amdgpu_waves_per
     __shared__ __attribute__((aligned(16))) float w2_lds[GP * 64];           // value_fc2 weights of each game's net
     __shared__ unsigned path_l[GP][PG::PATH];
     __shared__ GameLds games[GP];
-    __shared__ double sq_lds[1026];                       // np.sqrt(N + 1e-8), N = 0..S+1 (S <= 1024)
+    __shared__ double sq_lds[1026];                       // np.sqrt(N + 1e-8), N = 0..S+1 (S <= DEFAULT_MAX_S: search_prepare)
     __shared__ int wg_net;
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];     // GP x R x ROWE edges
     Edge *rows_all = reinterpret_cast<Edge *>(dyn_lds);

@@ -17,6 +17,11 @@ __host__ __device__ constexpr bool leaf_needs_net(int kind) { return kind == LEA
 constexpr int VL_MAX = 32;             // leaves per batch in virtual-loss mode (5 spare bits of the edge's visit field)
 constexpr int EDGE_N_BITS = 11, EDGE_N_MASK = (1 << EDGE_N_BITS) - 1;   // visit count 0..1024 in the low bits, in-flight count above
 constexpr int REUSE_MAX_ROWS = 1024;   // rows per slot (S + 2) the in-place compaction of k_move can renumber
+// Deep searches (az_create_deep): above DEFAULT_MAX_S simulations the narrow budgets of the default kernels no longer hold --
+// the sqrt table outgrows k_step's LDS copy and the visit count outgrows EDGE_N_BITS -- so S > DEFAULT_MAX_S runs the DEEP
+// instantiations of k_step / k_step_vl (sqrt table read from HBM / L2, in-flight counts in a byte array beside the tree).  Up to
+// DEFAULT_MAX_S a deep engine runs the default instantiations, whose code and arguments the DEEP ones leave untouched.  The 16-bit child row, path row and visit fields bound S by 65534.
+constexpr int DEFAULT_MAX_S = 1024;
 constexpr int CNT_STRIDE = 8;  // per-slot counters: expansions, simulations, terminal hits, depth sum, reused roots, duplicate leaves,
                                // cache lookups, cache hits
 enum { SLOT_IDLE = 0, SLOT_ACTIVE = 1, SLOT_FINISHED = 2 };
@@ -311,10 +316,12 @@ __global__ void k_begin(DevState d)
 // k_step: consume the evaluation of the pending leaf (expand + backup), then select the next leaf.
 // Latency-bound (one wave per game, ~4 waves per CU): every load that does not depend on another load is
 // issued up front in one round trip; the sqrt table lives in LDS; the chosen edge is broadcast by shuffle.
-// Dynamic LDS: (S + 2) doubles.
+// Dynamic LDS: (S + 2) doubles.  DEEP (S > DEFAULT_MAX_S): no LDS table; each level's sqrt(N_parent + 1e-8) is read from
+// the global table (L2-resident) right after the chosen edge is known, so it is in flight with that level's win test
+// and the next level's edge loads (same values: results are bit-identical).
 // ------------------------------------------------------------------------------------------------
 constexpr int STEP_WAVES = 4;      // games (wavefronts) per k_step workgroup
-template <int N, bool SYNTH>
+template <int N, bool SYNTH, bool DEEP = false>
 __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN, int do_select)
 {
     typedef TreeGeo<N> G;
@@ -323,7 +330,8 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
     const int b = blockIdx.x * STEP_WAVES + (threadIdx.x >> 6);
     const bool inb = b < d.B;
     const int bb = inb ? b : 0;
-    for (int i = threadIdx.x; i < d.S + 2; i += STEP_WAVES * 64) sq_lds[i] = d.sqrt_table[i];
+    if constexpr (!DEEP)
+        for (int i = threadIdx.x; i < d.S + 2; i += STEP_WAVES * 64) sq_lds[i] = d.sqrt_table[i];
 
     // ---- independent loads, all in flight together ----
     const int status = d.s_status[bb];
@@ -514,11 +522,12 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
     Plane me = pl == 1 ? bX : bO;
     Plane opp = pl == 1 ? bO : bX;
     int row = 0, npar = rootN, depth = 0, last = slast, out_kind = LEAF_NONE;
+    double sq_next = DEEP ? d.sqrt_table[rootN] : 0.0;
     for (;;) {
         Plane occ;
 #pragma unroll
         for (int q = 0; q < 4; q++) occ.w[q] = me.w[q] | opp.w[q];
-        const double sq = sq_lds[npar];                       // np.sqrt(self.N + 1e-8), mcts.py:73
+        const double sq = DEEP ? sq_next : sq_lds[npar];      // np.sqrt(self.N + 1e-8), mcts.py:73
         double best = 0.0;
         int bi = -1, bN = 0, bC = 0;
 #pragma unroll
@@ -537,6 +546,7 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
         // the lane that owns cell a (a & 63) holds its edge: the global best is also that lane's best
         const int child = __builtin_amdgcn_readlane(bC, a & 63);
         const int an = __builtin_amdgcn_readlane(bN, a & 63);
+        if (DEEP) sq_next = d.sqrt_table[an];                 // the next level's parent visits: issued before the win test
         if (lane == 0) path[depth] = ((unsigned)row << 16) | (unsigned)a;
         depth++;
         pl_set(me, a);                                        // games.py:79-81 place, flip player, remember action
@@ -609,6 +619,10 @@ __global__ __launch_bounds__(256) void k_root_cache(DevState d)
 // The in-flight count lives in the 5 spare bits of the edge's 16-bit visit field; W is never touched by it, so taking
 // a virtual visit back is exact.  Same arithmetic and operator order as the oracle's restatement (orc_cfg.vl); with
 // L = 1 it reproduces k_step.  Dynamic LDS: (S + 2) doubles.
+// DEEP (S > DEFAULT_MAX_S, visit counts beyond EDGE_N_MASK): the edge's N is a plain 16-bit count and the in-flight count
+// lives in a byte array beside the tree (the DEEP kernel's extra argument, [B][R][RW], when L > 1), read with the edge, raised where the
+// narrow kernel adds 1 << EDGE_N_BITS, lowered at backup, zeroed with every new row; the sqrt table is read from HBM as in
+// k_step<.., DEEP>.  Mechanically the same rule: bit-identical to the oracle at any S.
 // ------------------------------------------------------------------------------------------------
 template <int N, bool SYNTH>
 __device__ __forceinline__ void vl_leaf_eval(const DevState &d, size_t it, const Plane &lme, const Plane &lopp, int leaf_last,
@@ -678,8 +692,11 @@ __device__ __forceinline__ void vl_leaf_eval(const DevState &d, size_t it, const
     v = az_tanhf(acc + b2);
 }
 
-template <int N, bool SYNTH>
-__global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int nb_next)
+__device__ __forceinline__ unsigned char *inflight_arg() { return nullptr; }
+__device__ __forceinline__ unsigned char *inflight_arg(unsigned char *p) { return p; }
+// InFlight is empty for the default kernel (its arguments stay those of the narrow kernel) and `unsigned char *` for DEEP
+template <int N, bool SYNTH, bool DEEP = false, class... InFlight>
+__global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int nb_next, InFlight... inflight)
 {
     typedef TreeGeo<N> G;
     extern __shared__ double sq_lds[];                 // np.sqrt(N + 1e-8), N = 0..S+1 (mcts.py:73)
@@ -687,12 +704,15 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
     __shared__ unsigned pend_lds[4][VL_MAX];           // leaf edge (row << 16 | cell) of every item waiting for an evaluation
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int b = blockIdx.x * 4 + wv;
-    for (int i = threadIdx.x; i < d.S + 2; i += 256) sq_lds[i] = d.sqrt_table[i];
+    if constexpr (!DEEP)
+        for (int i = threadIdx.x; i < d.S + 2; i += 256) sq_lds[i] = d.sqrt_table[i];
     __syncthreads();
     if (b >= d.B || d.s_status[b] != SLOT_ACTIVE) return;
     const int L = d.L;
     const size_t it0 = (size_t)b * L;
     Edge *rows = d.edges + (size_t)b * d.R * G::RW;
+    // DEEP: in-flight counts of this slot's edges (L == 1 never has any: no array, nothing read or written)
+    unsigned char *infl = DEEP && L > 1 ? inflight_arg(inflight...) + (size_t)b * d.R * G::RW : nullptr;
     const int pl = d.s_player[b], slast = d.s_last[b], netid = d.s_net[b], game = d.s_game[b], ply = d.s_ply[b];
     const Plane bX = pl_load(d.board + (size_t)b * 8), bO = pl_load(d.board + (size_t)b * 8 + 4);
     float *vals = vals_lds[wv];
@@ -737,6 +757,7 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
                 Edge e;
                 e.W = 0.0; e.P = P[i]; e.N = 0; e.child = 0;
                 rows[(size_t)row * G::RW + lane + 64 * i] = e;
+                if (DEEP && infl) infl[(size_t)row * G::RW + lane + 64 * i] = 0;
             }
             rows_used = row + 1;
             if (kind == LEAF_EXPAND) {
@@ -755,7 +776,12 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
                 const unsigned pe = path[dd];
                 Edge *e = rows + (size_t)(pe >> 16) * G::RW + (pe & 0xFFFFu);
                 const double val = ((depth0 - 1 - dd) & 1) ? value : -value;
-                e->N = (unsigned short)(e->N - (1 << EDGE_N_BITS) + 1);      // the in-flight visit becomes a real one
+                if (DEEP) {
+                    if (infl) { unsigned char *f = infl + (size_t)(pe >> 16) * G::RW + (pe & 0xFFFFu); *f = (unsigned char)(*f - 1); }
+                    e->N = (unsigned short)(e->N + 1);                        // the in-flight visit becomes a real one
+                } else {
+                    e->N = (unsigned short)(e->N - (1 << EDGE_N_BITS) + 1);  // the in-flight visit becomes a real one
+                }
                 e->W = e->W + val;
             }
             c_exp += kind == LEAF_EXPAND ? 1ull : 0ull;
@@ -779,11 +805,12 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
         int row = 0, npar = sims_done + j, depth = 0, last = slast, out_kind = LEAF_NONE;
         unsigned *path = d.path + it * G::PATH;
         unsigned leaf_edge = 0xFFFFFFFFu;
+        double sq_next = DEEP ? d.sqrt_table[npar] : 0.0;
         for (;;) {
             Plane occ;
 #pragma unroll
             for (int q = 0; q < 4; q++) occ.w[q] = me.w[q] | opp.w[q];
-            const double sq = sq_lds[npar];                       // np.sqrt(self.N + 1e-8), mcts.py:73
+            const double sq = DEEP ? sq_next : sq_lds[npar];      // np.sqrt(self.N + 1e-8), mcts.py:73
             double best = 0.0;
             int bi = -1, bN = 0, bC = 0;
 #pragma unroll
@@ -791,8 +818,9 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
                 int c = lane + 64 * i;
                 if (c < G::nn && !pl_get(occ, c)) {
                     Edge e = rows[(size_t)row * G::RW + c];
-                    const int fl = (int)e.N >> EDGE_N_BITS;               // simulations of this batch in flight through the edge
-                    const int nv = ((int)e.N & EDGE_N_MASK) + fl;
+                    // simulations of this batch in flight through the edge
+                    const int fl = DEEP ? (infl ? (int)infl[(size_t)row * G::RW + c] : 0) : (int)e.N >> EDGE_N_BITS;
+                    const int nv = (DEEP ? (int)e.N : ((int)e.N & EDGE_N_MASK)) + fl;
                     const double wvv = e.W - (double)fl;
                     double Q = nv ? wvv / (double)nv : 0.0;
                     double sc = Q + ((d.c_puct * (double)e.P) * sq) / (double)(1 + nv);
@@ -804,9 +832,14 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
             if (a < 0) { out_kind = LEAF_NONE; break; }
             const int child = __builtin_amdgcn_readlane(bC, a & 63);
             const int an = __builtin_amdgcn_readlane(bN, a & 63);
+            if (DEEP) sq_next = d.sqrt_table[an];                 // the next level's parent visits: issued before the win test
             if (lane == (a & 63)) {
-                Edge *e = rows + (size_t)row * G::RW + a;
-                e->N = (unsigned short)(e->N + (1 << EDGE_N_BITS));
+                if (DEEP) {
+                    if (infl) { unsigned char *f = infl + (size_t)row * G::RW + a; *f = (unsigned char)(*f + 1); }
+                } else {
+                    Edge *e = rows + (size_t)row * G::RW + a;
+                    e->N = (unsigned short)(e->N + (1 << EDGE_N_BITS));
+                }
             }
             if (lane == 0) path[depth] = ((unsigned)row << 16) | (unsigned)a;
             leaf_edge = ((unsigned)row << 16) | (unsigned)a;
@@ -911,11 +944,12 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
     int Nj[G::CPL], rank[G::CPL];
     bool legal[G::CPL];
     double e[G::CPL];
+    const int nmask = d.S > DEFAULT_MAX_S ? 0xFFFF : EDGE_N_MASK;     // deep searches: N is the whole 16-bit visit count
 #pragma unroll
     for (int i = 0; i < G::CPL; i++) {
         int j = lane + 64 * i;
         legal[i] = j < G::nn && !pl_get(occ, j);
-        Nj[i] = legal[i] ? (int)root[j].N & EDGE_N_MASK : 0;
+        Nj[i] = legal[i] ? (int)root[j].N & nmask : 0;
         rank[i] = legal[i] ? j - pl_rank(occ, j) : 0;
     }
     bool uniform = false;

@@ -7,7 +7,7 @@ import torch
 
 from . import constants as _c
 from . import parallel
-from ._capi import Engine
+from ._capi import AZ_MAX_SIMULATIONS, Engine
 from .controller import device_index, model_kind
 from .mcts import numpy_log_table
 
@@ -42,7 +42,8 @@ class ModelEvaluator:
             if self._engine is not None:
                 self._engine.close()
             self._engine = Engine(n, k, S, max(1, min(mine, _c.CONCURRENT_GAMES)), c_puct=_c.EVAL_EXPLORATION_CONSTANT,
-                                  device=device_index(self.device), log_table=numpy_log_table(S), model=key[4])
+                                  device=device_index(self.device), log_table=numpy_log_table(S), model=key[4],
+                                  deep=S > AZ_MAX_SIMULATIONS)
             self._engine.set_virtual_loss(self.virtual_loss)
             self._engine.set_eval_cache(self.eval_cache)
             self._key = key

@@ -7,7 +7,7 @@ them to the engine, so np.random.seed(s) reproduces the reference's choices."""
 import numpy as np
 
 from . import constants as _c
-from ._capi import Engine
+from ._capi import AZ_MAX_SIMULATIONS, Engine
 from .controller import PolicyValueFn, device_index, model_kind, weights_version
 
 
@@ -36,7 +36,8 @@ class MCTS:
     def _eng_external(self, n, k):
         if self._engine is None or (self._engine.n, self._engine.k) != (n, k):
             self._engine = Engine(n, k, self.num_simulations, 1, c_puct=self.c_puct, dirichlet_alpha=self.dirichlet_alpha,
-                                  dirichlet_weight=self.dirichlet_weight, log_table=numpy_log_table(self.num_simulations))
+                                  dirichlet_weight=self.dirichlet_weight, log_table=numpy_log_table(self.num_simulations),
+                                  deep=self.num_simulations > AZ_MAX_SIMULATIONS)
         return self._engine
 
     def _run_external(self, root_state, temperature, noise, u):
@@ -59,7 +60,7 @@ class MCTS:
             self._engine = Engine(n, k, self.num_simulations, 1, c_puct=self.c_puct,
                                   dirichlet_alpha=self.dirichlet_alpha, dirichlet_weight=self.dirichlet_weight,
                                   device=device_index(ctrl.device), log_table=numpy_log_table(self.num_simulations),
-                                  model=model_kind(ctrl.net))
+                                  model=model_kind(ctrl.net), deep=self.num_simulations > AZ_MAX_SIMULATIONS)
             self._engine.set_virtual_loss(self.virtual_loss)
             self._version = None
         ver = weights_version(ctrl.net)

@@ -7,7 +7,7 @@ import torch
 
 from . import constants as _c
 from . import parallel
-from ._capi import AZ_AUG_REFERENCE4, Engine
+from ._capi import AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine
 from .controller import device_index, model_kind
 from .mcts import numpy_log_table
 
@@ -51,7 +51,7 @@ class SelfPlayManager:
             # lanes per GPU: the library's own rule (1 on small boards, one per 128 slots up to 4) unless the caller fixed it
             self._engine = Engine(n, k, key[2], slots, engines=self.engines_per_gpu or 0, c_puct=key[4], dirichlet_alpha=key[5],
                                   dirichlet_weight=key[6], device=device_index(self.device),
-                                  log_table=numpy_log_table(key[2]), model=key[7])
+                                  log_table=numpy_log_table(key[2]), model=key[7], deep=key[2] > AZ_MAX_SIMULATIONS)
             self._engine.set_virtual_loss(self.virtual_loss)
             self._engine.set_eval_cache(self.eval_cache)
             self._engine.set_leaf_symmetry(self.leaf_symmetry)
@@ -86,6 +86,10 @@ class SelfPlayManager:
         if self.seed is None:
             seed0 = parallel.broadcast_seed(seed0, torch.device("cuda", device_index(self.device)))
         dev = torch.device("cuda", device_index(self.device))
+        sims = self.mcts_params.get("num_simulations", 100)
+        if self.subtree_reuse and sims > REUSE_MAX_SIMULATIONS:
+            raise ValueError(f"subtree_reuse supports at most {REUSE_MAX_SIMULATIONS} simulations per move (got {sims}): "
+                             "the retained tree is renumbered in a 1024-row table")
         eng = self._eng(n, k, max(1, min(self.concurrent_games, max(mine, 1))))
         eng.load_weights(self.controller.net.state_dict(), 0)
         eng.set_subtree_reuse(self.subtree_reuse)

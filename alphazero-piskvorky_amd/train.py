@@ -90,7 +90,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--episodes", type=int, default=C.NUM_EPISODES)
     ap.add_argument("--games", type=int, default=C.NUM_SELF_PLAY_GAMES)
-    ap.add_argument("--sims", type=int, default=C.NUM_SELF_PLAY_SIMULATIONS)
+    ap.add_argument("--sims", type=int, default=C.NUM_SELF_PLAY_SIMULATIONS,
+                    help="simulations per move; above 1024 the engines are created deep (az_create_deep, up to 65534), "
+                         "and so is the arena's when NUM_EVAL_SIMULATIONS is above 1024")
     ap.add_argument("--eval-games", type=int, default=C.EVALUATION_GAMES)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--model-dir", default=None)

@@ -51,7 +51,7 @@ enum { AZ_MODEL_PLAIN = 0, AZ_MODEL_RESNET = 1 };  /* net.py GomokuNet | Residua
 typedef struct {
     int32_t board_size;        /* constants.py:2  BOARD_SIZE   (3 .. 15)                         */
     int32_t win_length;        /* constants.py:3  WIN_LENGTH                                     */
-    int32_t num_simulations;   /* mcts.py:89      num_simulations (<= 1024)                      */
+    int32_t num_simulations;   /* mcts.py:89      num_simulations (<= 1024; az_create_deep: <= 65534) */
     int32_t slots;             /* concurrent games resident on this GPU                          */
     double c_puct;             /* mcts.py:90                                                      */
     double dirichlet_alpha;    /* mcts.py:91 (0.3)                                                */
@@ -74,6 +74,22 @@ typedef struct {
 
 /* ---- lifecycle ---- */
 int az_create(const az_config *cfg, az_engine **out);
+
+/* Deep searches: the reference takes any num_simulations (mcts.py:18 DEFAULT_NUM_SIMULATIONS = 10_000).  az_create_deep is
+ * az_create with num_simulations allowed in 1..AZ_DEEP_MAX_SIMULATIONS, a bound set by the 16-bit child row, path row and
+ * visit-count fields of the tree.  It is a separate entry point because the tree memory grows with S: (S + 1) x
+ * roundup(n*n, 64) x 16 B per slot (41 MB at 15x15 / S = 10 000), and a caller has to ask for that.  Before it allocates
+ * anything it adds up the trees of all slots and the tables that grow with S and returns AZ_ERR_INVALID, with the byte
+ * count in az_last_error, when that exceeds the device's free memory.
+ * Up to 1024 simulations a deep engine IS the default engine (same kernels, same results, same persistent-kernel choice).
+ * Above 1024 the tree step runs its deep instantiations (the sqrt table read from HBM instead of LDS; with virtual-loss
+ * batching the in-flight counts in a byte per edge beside the tree, allocated by az_set_virtual_loss under the same memory
+ * check), each ply is launched kernel by kernel instead of as one captured graph, and the persistent search kernel is never
+ * chosen.  Results are bit-identical to the oracle at any S.  Everything else combines as below 1024: evaluation cache,
+ * random-symmetry leaf evaluation, both nets, the emulated trunks, az_search, az_search_callback, az_arena and virtual-loss
+ * batching.  Subtree reuse stays limited to 1023 simulations (az_set_subtree_reuse). */
+#define AZ_DEEP_MAX_SIMULATIONS 65534
+int az_create_deep(const az_config *cfg, az_engine **out);
 void az_destroy(az_engine *e);
 const char *az_last_error(const az_engine *e);   /* valid until the next call on e; e may be NULL */
 
@@ -355,8 +371,8 @@ int az_get_lanes(const az_engine *e);
  * tree launch per evaluation batch; g > 0 = the persistent search kernel (csrc/az_search.h), one launch per ply with g
  * games per workgroup and their trees resident in LDS.  The library picks the persistent kernel by itself whenever it
  * applies -- boards up to 7x7 whose (num_simulations + 1) tree rows fit into LDS, either net or the synthetic evaluator,
- * float32 trunk, no virtual-loss batching (the evaluation cache, subtree reuse and the leaf symmetry it knows) -- because
- * its results are bit-identical; AZ_PERSIST=0 in the environment keeps the lock-step pipeline. */
+ * float32 trunk, no virtual-loss batching, at most 1024 simulations (the evaluation cache, subtree reuse and the leaf symmetry
+ * it knows) -- because its results are bit-identical; AZ_PERSIST=0 in the environment keeps the lock-step pipeline. */
 int az_get_persistent(const az_engine *e);
 
 #ifdef __cplusplus
