@@ -29,7 +29,7 @@ REUSE_MAX_SIMULATIONS = 1023                                   # az_set_subtree_
 
 EXPORTS = [
     "az_create", "az_create_deep", "az_destroy", "az_last_error", "az_load_weights", "az_load_weights_resnet", "az_net_eval", "az_search", "az_search_callback", "az_selfplay",
-    "az_selfplay_begin", "az_selfplay_step", "az_selfplay_end", "az_selfplay_games", "az_selfplay_records", "az_record_bytes", "az_selfplay_pack", "az_examples_from_packed",
+    "az_selfplay_begin", "az_selfplay_step", "az_selfplay_end", "az_selfplay_games", "az_selfplay_records", "az_selfplay_clear", "az_record_bytes", "az_selfplay_pack", "az_examples_from_packed",
     "az_examples_gather", "az_arena", "az_rules_replay", "az_rng_selfplay_tape", "az_rng_uniforms", "az_set_profiling", "az_set_subtree_reuse", "az_get_counters", "az_get_lanes", "az_get_persistent", "az_set_virtual_loss", "az_set_eval_cache",
     "az_set_trunk_mode", "az_get_trunk_mode", "az_set_leaf_symmetry", "az_emul_split",
     "az_dist_unique_id", "az_dist_init", "az_dist_rank", "az_dist_world", "az_dist_counts", "az_dist_gather_records",
@@ -337,6 +337,13 @@ class Engine:
                                               _p(out["actions"]), _p(out["pis"]), _p(out["visits"]), _p(out["z"])),
                     "az_selfplay_records")
         return out
+
+    def clear_episode(self):
+        """Forget the last episode (az_selfplay_clear): this engine then contributes no records to the episode-end exchange.
+        For a rank that got no games this time."""
+        self._check(lib().az_selfplay_clear(self.h), "az_selfplay_clear")
+        self.last_records = 0
+        self.last_games = 0
 
     def _torch_sync(self):
         """The engine works on its own non-blocking HIP stream and synchronises it before every call returns; device

@@ -1439,6 +1439,14 @@ extern "C" int az_selfplay_records(az_engine *e, uint8_t *boards, uint8_t *mover
     return AZ_OK;
 }
 
+extern "C" int az_selfplay_clear(az_engine *e)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_selfplay_clear: an episode is open (az_selfplay_end first)");
+    e->have_episode = false;
+    return AZ_OK;
+}
+
 extern "C" int64_t az_record_bytes(const az_engine *e) { return e ? record_bytes(e->nn) : 0; }
 
 extern "C" int az_selfplay_pack(az_engine *e, void *packed_dev)
@@ -1462,9 +1470,10 @@ extern "C" int az_selfplay_pack(az_engine *e, void *packed_dev)
 extern "C" int az_examples_from_packed(az_engine *e, const void *packed_dev, int64_t records, int aug, float *states_dev,
                                        float *pis_dev, float *z_dev)
 {
-    if (!e || !packed_dev || !states_dev || !pis_dev || !z_dev || records < 0) return fail(e, AZ_ERR_INVALID, "az_examples_from_packed: bad argument");
+    if (!e || records < 0) return fail(e, AZ_ERR_INVALID, "az_examples_from_packed: bad argument");
     if (aug != AZ_AUG_NONE && aug != AZ_AUG_REFERENCE4 && aug != AZ_AUG_DIHEDRAL8) return fail(e, AZ_ERR_INVALID, "aug must be 1, 4 or 8");
-    if (records == 0) return AZ_OK;
+    if (records == 0) return AZ_OK;         // nothing to read or write: the buffers of an empty batch may be null
+    if (!packed_dev || !states_dev || !pis_dev || !z_dev) return fail(e, AZ_ERR_INVALID, "az_examples_from_packed: bad argument");
     DEVICE_GUARD(e);
     hipLaunchKernelGGL(k_examples, dim3((unsigned)records), dim3(256), 0, e->stream, (const unsigned char *)packed_dev,
                        records, e->n, record_bytes(e->nn), aug, states_dev, pis_dev, z_dev);
@@ -1693,9 +1702,10 @@ extern "C" int az_debug_stamps(az_engine *e, unsigned long long *out, int max_gr
 extern "C" int az_examples_gather(az_engine *e, const void *packed_dev, const int64_t *idx_dev, const int32_t *sym_dev,
                                   int count, int reference_pi, float *states_dev, float *pis_dev, float *z_dev)
 {
-    if (!e || !packed_dev || !idx_dev || !sym_dev || !states_dev || !pis_dev || !z_dev || count < 0)
+    if (!e || count < 0) return fail(e, AZ_ERR_INVALID, "az_examples_gather: bad argument");
+    if (count == 0) return AZ_OK;           // nothing to read or write: the buffers of an empty batch may be null
+    if (!packed_dev || !idx_dev || !sym_dev || !states_dev || !pis_dev || !z_dev)
         return fail(e, AZ_ERR_INVALID, "az_examples_gather: bad argument");
-    if (count == 0) return AZ_OK;
     DEVICE_GUARD(e);
     hipLaunchKernelGGL(k_examples_gather, dim3((unsigned)count), dim3(256), 0, e->stream, (const unsigned char *)packed_dev,
                        (const long long *)idx_dev, (const int *)sym_dev, count, e->n, record_bytes(e->nn), reference_pi,

@@ -75,7 +75,9 @@ class SelfPlayManager:
     def generate_packed(self, num_games: int):
         """The same episode, but the result stays on the device as packed records (one per position, all ranks'
         records after the exchange): (uint8 tensor, record count, engine, device, n).  Feed it to
-        device_replay.DeviceReplayBuffer.extend_packed to train without materialising Python tuples."""
+        device_replay.DeviceReplayBuffer.extend_packed to train without materialising Python tuples.
+        Games are always played to the end here (max_plies is never passed), so no record carries the label of a cut
+        game, z = 99 (include/az_engine.h), which the example kernels would hand on as a value target."""
         n = self.controller.net.board_size
         k = min(_c.WIN_LENGTH, n)
         rank, world = parallel.rank_world()
@@ -99,7 +101,7 @@ class SelfPlayManager:
         if mine > 0:
             self.last_counters = eng.selfplay(mine, seed0=seed0 + lo, temperature_table=T)
         else:
-            eng.last_records = 0
+            eng.clear_episode()       # no games for this rank: it must not send the engine's previous episode again
         packed, counts = parallel.gather_packed_records(eng, dev, dst=self.gather_to)
         total = int(sum(counts)) if (self.gather_to is None or rank == self.gather_to) else 0
         return packed, total, eng, dev, n

@@ -201,8 +201,21 @@ int az_selfplay_games(az_engine *e, int32_t *nply, int32_t *result);
 int az_selfplay_records(az_engine *e, uint8_t *boards, uint8_t *movers, int16_t *lasts, int16_t *actions,
                         float *pis, int32_t *visits, int8_t *z);
 
-/* Packed records for the episode-end exchange (RCCL gather over xGMI):
- * az_record_bytes() per record: mover-relative bit-planes, last move, pi float32[n*n], z.
+/* Forgets the last episode: afterwards the engine is in the state of one that has not played (az_selfplay_games,
+ * az_selfplay_records and az_selfplay_pack fail with AZ_ERR_STATE, az_dist_counts / az_dist_gather_records contribute 0
+ * records).  For a rank that got no games in the current episode: without it the rank would send its previous episode again.
+ * AZ_ERR_STATE while an episode is open. */
+int az_selfplay_clear(az_engine *e);
+
+/* Packed records for the episode-end exchange (RCCL gather over xGMI), game-major then ply like
+ * az_selfplay_records.  One record = az_record_bytes() bytes, little-endian:
+ *   [0, 64)              8 x uint64 bit-planes, cell c = bit (c & 63) of word (c >> 6): words 0..3 the MOVER's stones,
+ *                        words 4..7 the opponent's (n <= 15: cells 0..224);
+ *   [64, 64 + 4 n*n)     pi float32[n*n];
+ *   then int16 last move (-1 at the first ply), uint8 mover (1 / 2), int8 z;
+ *   padded to a multiple of 8 bytes (4 padding bytes when n is even, none when n is odd; their content is unspecified).
+ * z is self_play.py:71's label: +1 the mover won, -1 the mover lost, 0 draw.  A game cut by max_plies has no outcome: its
+ * records carry z = 99, here exactly as in az_selfplay_records.
  * az_selfplay_pack writes records*az_record_bytes bytes to a DEVICE buffer. */
 int64_t az_record_bytes(const az_engine *e);
 int az_selfplay_pack(az_engine *e, void *packed_dev);
@@ -241,14 +254,20 @@ int az_dist_broadcast(az_engine *e, void *buf_dev, int64_t bytes, int root);
  * AZ_AUG_REFERENCE4 reproduces the reference (state rot k*90deg, pi rot 90deg once, Q16),
  * AZ_AUG_DIHEDRAL8 is the correct 8-fold group, AZ_AUG_NONE emits each position once.
  * Reads `records` packed records from packed_dev (this rank's or gathered ones) and writes
- * records*aug examples to DEVICE buffers, order (record, k). */
+ * records*aug examples to DEVICE buffers, order (record, k).  Every cell of every example is written (plane 3 with
+ * zeros), nothing behind the last example.  z is handed on as it is packed: cut games carry z = 99.0f as the value target;
+ * callers that train must not cut (the Python seams never pass max_plies).  records = 0 returns AZ_OK without touching
+ * any buffer (the pointers may then be NULL). */
 int az_examples_from_packed(az_engine *e, const void *packed_dev, int64_t records, int aug,
                             float *states_dev, float *pis_dev, float *z_dev);
 
 /* Training batch from a device-resident replay ring of packed records (replay_buffer.py:26-39 sample_batch +
  * controller.py:23-31 collate, with no host round trip): example i = symmetry sym_dev[i] (0..7, dihedral group;
  * 0..3 are the rotations) of record idx_dev[i].  reference_pi != 0 rotates pi once whatever the symmetry, like
- * self_play.py:105 does.  All pointers are DEVICE pointers. */
+ * self_play.py:105 does.  All pointers are DEVICE pointers.  idx_dev may repeat and need not be ordered; the caller keeps
+ * it inside the ring and sym_dev inside 0..7 (neither is checked).  z as in az_examples_from_packed: cut games carry
+ * z = 99.0f; callers that train must not cut.  count = 0 returns AZ_OK without touching any buffer (the pointers may
+ * then be NULL: the batch of an empty ring). */
 int az_examples_gather(az_engine *e, const void *packed_dev, const int64_t *idx_dev, const int32_t *sym_dev,
                        int count, int reference_pi, float *states_dev, float *pis_dev, float *z_dev);
 

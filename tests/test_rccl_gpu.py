@@ -65,6 +65,55 @@ net = GomokuNet(board_size=5).to(dev)
 before = [p.detach().clone() for p in net.parameters()]
 parallel.broadcast_module_(net, force=True)
 assert all(torch.equal(a, b) for a, b in zip(before, net.parameters()))
+# a rank without games sends no records, on either exchange path.  An engine that has played is put in the state of a rank
+# whose share of the next episode is empty: the library's own exchange must not send the previous episode again
+e3 = az.Engine(5, 4, 16, 8, synthetic=True)
+e3.selfplay(4, seed0=3)
+assert e3.last_records > 0
+packed, counts = parallel.gather_packed_records(e3, dev, force=True)
+assert parallel.last_exchange == "az_dist" and counts == [e3.last_records]
+e3.clear_episode()
+packed, counts = parallel.gather_packed_records(e3, dev, force=True)
+assert parallel.last_exchange == "az_dist"
+assert counts == [0] and packed.numel() == 0, f"a rank without games sent {counts} records through the library's exchange"
+assert e3.dist_counts() == [0]
+e3.selfplay(2, seed0=8)                                   # and it plays again afterwards
+want3 = torch.zeros(e3.last_records * e3.record_bytes, dtype=torch.uint8, device=dev)
+e3.pack_into(want3.data_ptr()); torch.cuda.synchronize()
+packed, counts = parallel.gather_packed_records(e3, dev, force=True)
+assert counts == [e3.last_records] and torch.equal(packed, want3)
+e3.close()
+# the same through the seam that creates that state: SelfPlayManager.generate_packed with no games for this rank keeps its
+# engine (same slots); first "an episode, then 0 games", then on a fresh manager "0 games first, then an episode"
+from alphazero_piskvorky_amd.controller import NeuralNetworkController
+from alphazero_piskvorky_amd.self_play import SelfPlayManager
+torch.manual_seed(0)
+ctrl = NeuralNetworkController(GomokuNet(board_size=5).eval(), device="cuda:0")
+def manager():
+    return SelfPlayManager(ctrl, "cuda:0", mcts_params={"num_simulations": 8}, concurrent_games=1, seed=21)
+mgr = manager()
+p1, total1, eng, _, _ = mgr.generate_packed(2)
+assert total1 > 0 and parallel.gather_packed_records(eng, dev, force=True)[1] == [total1]
+assert parallel.last_exchange == "az_dist"
+p0, total0, eng0, _, _ = mgr.generate_packed(0)
+assert eng0 is eng and total0 == 0 and p0.numel() == 0
+for path in ("az_dist", "torch.distributed"):
+    if path == "torch.distributed":                      # the fall-back engine_comm takes when RCCL cannot be set up
+        eng._dist_group_ok, eng._dist_failed = False, True
+    packed, counts = parallel.gather_packed_records(eng, dev, force=True)
+    assert parallel.last_exchange == path
+    assert counts == [0] and packed.numel() == 0, f"{path}: a rank without games sent {counts} records"
+mgr2 = manager()
+p0, total0, eng2, _, _ = mgr2.generate_packed(0)
+assert total0 == 0 and p0.numel() == 0
+packed, counts = parallel.gather_packed_records(eng2, dev, force=True)
+assert parallel.last_exchange == "az_dist" and counts == [0] and packed.numel() == 0
+p2, total2, eng2b, _, _ = mgr2.generate_packed(2)
+assert eng2b is eng2 and total2 == total1 and torch.equal(p2, p1)       # same seed, same net: the same episode
+packed, counts = parallel.gather_packed_records(eng2, dev, force=True)
+assert parallel.last_exchange == "az_dist" and counts == [total2] and torch.equal(packed, p2)
+out["records_after_empty_share"] = total2
+eng.close(); eng2.close()
 td.barrier()
 td.destroy_process_group()
 json.dump(out, open(sys.argv[2], "w"))
@@ -78,7 +127,8 @@ def test_one_rank_nccl_group_runs_every_collective_of_the_path(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29741", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     p = subprocess.run([sys.executable, str(script), ROOT, str(res)], env=env, timeout=600, capture_output=True, text=True)
     assert p.returncode == 0, p.stderr[-2000:]
-    assert json.load(open(res))["records"] > 0
+    got = json.load(open(res))
+    assert got["records"] > 0 and got["records_after_empty_share"] > 0
 
 
 def _bench(cmd, env):
