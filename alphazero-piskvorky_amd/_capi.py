@@ -28,7 +28,7 @@ AZ_MAX_SIMULATIONS, AZ_DEEP_MAX_SIMULATIONS = 1024, 65534      # az_create | az_
 REUSE_MAX_SIMULATIONS = 1023                                   # az_set_subtree_reuse
 
 EXPORTS = [
-    "az_create", "az_create_deep", "az_destroy", "az_last_error", "az_load_weights", "az_load_weights_resnet", "az_net_eval", "az_search", "az_search_callback", "az_selfplay",
+    "az_create", "az_create_deep", "az_destroy", "az_last_error", "az_load_weights", "az_load_weights_resnet", "az_net_eval", "az_search", "az_search_batch", "az_search_callback", "az_selfplay",
     "az_selfplay_begin", "az_selfplay_step", "az_selfplay_end", "az_selfplay_games", "az_selfplay_records", "az_selfplay_clear", "az_record_bytes", "az_selfplay_pack", "az_examples_from_packed",
     "az_examples_gather", "az_arena", "az_rules_replay", "az_rng_selfplay_tape", "az_rng_uniforms", "az_set_profiling", "az_set_subtree_reuse", "az_get_counters", "az_get_lanes", "az_get_persistent", "az_set_virtual_loss", "az_set_eval_cache",
     "az_set_trunk_mode", "az_get_trunk_mode", "az_set_leaf_symmetry", "az_emul_split",
@@ -123,6 +123,8 @@ def lib():
         L.az_dist_allreduce_sum.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.az_dist_broadcast.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
         L.az_dist_unique_id.argtypes = [C.c_void_p]
+        if hasattr(L, "az_search_batch"):        # an experiment build from older sources (AZ_ENGINE_LIB) may lack it
+            L.az_search_batch.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 11
         _LIB = L
     return _LIB
 
@@ -252,6 +254,50 @@ class Engine:
         self._check(lib().az_search(self.h, int(slot), _p(board), int(player), int(last), C.c_double(temperature),
                                     _dp(nz), C.c_double(u), _p(pi), C.byref(a), _p(N), _p(W), _p(P)), "az_search")
         return dict(action=int(a.value), pi=pi, N=N, W=W, P=P)
+
+    # ---- many searches at once ----
+    def search_batch(self, boards, players, lasts, temperature, noise=None, u=None, slot=0):
+        """MCTS.run for every position of a list (az_search_batch): boards [count, n*n] or [count, n, n], players / lasts
+        [count], temperature a scalar or [count], noise None or `count` float64 arrays (array i: one entry per legal cell of
+        position i), u None (0.5 for every position, like search) or [count].  Position i gets exactly what
+        search(boards[i], players[i], lasts[i], temperature[i], noise[i], u[i], slot) returns.
+        -> dict(action [count], pi [count, n*n], N, W, P)."""
+        nn = self.nn
+        boards = np.ascontiguousarray(boards, np.uint8)
+        if not ((boards.ndim == 2 and boards.shape[1] == nn) or (boards.ndim == 3 and boards.shape[1:] == (self.n, self.n))):
+            raise ValueError(f"boards must be [count, {nn}] or [count, {self.n}, {self.n}], got {boards.shape}")
+        cnt = boards.shape[0]
+        boards = boards.reshape(cnt, nn)
+        players = np.ascontiguousarray(players, np.uint8)
+        lasts = np.ascontiguousarray(lasts, np.int16)
+        if players.shape != (cnt,) or lasts.shape != (cnt,):
+            raise ValueError(f"players and lasts must have one entry per position ({cnt})")
+        T = np.asarray(temperature, np.float64)
+        if T.ndim == 0:
+            T = np.full(cnt, float(T), np.float64)
+        if T.shape != (cnt,):
+            raise ValueError(f"temperature must be a scalar or have one entry per position ({cnt})")
+        T = np.ascontiguousarray(T)
+        uu = np.full(cnt, 0.5, np.float64) if u is None else np.ascontiguousarray(u, np.float64)
+        if uu.shape != (cnt,):
+            raise ValueError(f"u must have one entry per position ({cnt})")
+        nz = None
+        if noise is not None:
+            if len(noise) != cnt:
+                raise ValueError(f"noise must have one array per position ({cnt})")
+            nz = np.zeros((cnt, nn), np.float64)
+            legal = (boards == 0).sum(axis=1)
+            for i, row in enumerate(noise):
+                row = np.asarray(row, np.float64)
+                if row.ndim != 1 or len(row) != int(legal[i]):
+                    raise ValueError(f"noise[{i}] must have one entry per legal cell ({int(legal[i])})")
+                nz[i, :len(row)] = row
+        pi = np.zeros((cnt, nn), np.float32); N = np.zeros((cnt, nn), np.int32)
+        W = np.zeros((cnt, nn), np.float64); P = np.zeros((cnt, nn), np.float32)
+        a = np.full(cnt, -1, np.int32)
+        self._check(lib().az_search_batch(self.h, int(slot), cnt, _p(boards), _p(players), _p(lasts), _p(T), _p(nz), _p(uu),
+                                          _p(pi), _p(a), _p(N), _p(W), _p(P)), "az_search_batch")
+        return dict(action=a, pi=pi, N=N, W=W, P=P)
 
     _EVAL_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float))
 

@@ -73,6 +73,7 @@ struct Lane {
     double trunk_ms = 0.0, nn_ms = 0.0, step_ms = 0.0;
     double tape_wait_s = 0.0;      // host time this lane's thread was blocked on a tape wave (production or its upload)
     int rc = AZ_OK;                // result of the last threaded call on this lane
+    int preset_m = 0;              // preset episodes (az_search, az_search_batch): the first preset_m slots hold given positions
     std::string err;
 };
 
@@ -99,6 +100,9 @@ struct az_engine {
     int trunk_mode = AZ_TRUNK_F32; // az_set_trunk_mode: AZ_TRUNK_BF16X3 / AZ_TRUNK_F16X2 = the convs on the 16-bit MFMAs with split operands
     int persist_gp = 0;            // games per workgroup of the persistent search kernel for the open episode, 0 = lock-step pipeline
     DevBuf cache;                  // evaluation cache shared by the lanes (az_set_eval_cache)
+    // az_search_batch, all sized by the slots: the wave's positions, temperatures and compact root statistics, and the all-zero
+    // noise_off table that makes row g of the [wave][n*n] noise upload the tape of game g
+    DevBuf bt_cells, bt_players, bt_lasts, bt_T, bt_zero_off, bt_visits, bt_W, bt_prior, bt_pi, bt_action;
     unsigned cache_mask = 0, cache_gen = 1;
     std::vector<int> h_nply, h_result;
     PackedNet net[2];
@@ -684,6 +688,7 @@ static int create_engine(const az_config *cfg, az_engine **out, bool deep)
         d.carried = (int *)L.carried.p; d.reuse = 0;
         d.v2w[0] = d.v2w[1] = d.v2b[0] = d.v2b[1] = nullptr;
         d.cache = nullptr; d.cache_mask = 0; d.cache_gen = e->cache_gen; d.ext_eval = 0; d.leaf_sym = nullptr; d.game_key0 = 0;
+        d.key_stride = 1; d.T_game = nullptr;
         if (!rc) rc = alloc_items(e, L, 1);
     }
     if (!rc) rc = dev_alloc(e, e->next_game, 16);
@@ -761,7 +766,8 @@ extern "C" void az_destroy(az_engine *e)
     }
     DevBuf *shared[] = {&e->T_table, &e->log_table, &e->sqrt_table, &e->noise_off, &e->next_game, &e->noise, &e->u,
                         &e->rec_planes, &e->rec_last, &e->rec_action, &e->rec_mover, &e->rec_pi, &e->rec_visits, &e->g_nply,
-                        &e->g_result, &e->src_index, &e->cache};
+                        &e->g_result, &e->src_index, &e->cache, &e->bt_cells, &e->bt_players, &e->bt_lasts, &e->bt_T,
+                        &e->bt_zero_off, &e->bt_visits, &e->bt_W, &e->bt_prior, &e->bt_pi, &e->bt_action};
     for (DevBuf *b : shared) dev_free(*b);
     for (int s = 0; s < 2; s++) {
         PackedNet &p = e->net[s];
@@ -932,7 +938,8 @@ static int ensure_episode_buffers(az_engine *e, int games, bool need_noise)
 struct EpisodeSpec {
     int num_games = 0, max_plies = 0;
     bool add_noise = true, arena = false;
-    bool preset = false;      // slot 0 of lane 0 already holds a position (az_search); skip the initial refill
+    bool preset = false;      // the first Lane::preset_m slots of every lane already hold positions (az_search: slot 0 of lane 0); skip the initial refill
+    bool batch = false;       // preset by az_search_batch: the ply runs over the preset slots only, throughput kernel choices as in self-play
     bool profile = true;      // this episode may be timed with HIP events (only when az_set_profiling is on)
     unsigned game_key0 = 0;   // low 32 bits of seed0: the leaf-symmetry hash names game g by its seed, seed0 + g
 };
@@ -980,7 +987,7 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
     if (e->persist_allowed && !e->vl_kernel && e->trunk_mode == AZ_TRUNK_F32) {
         const int synth = e->cfg.eval_kind == AZ_EVAL_SYNTHETIC ? 1 : 0;
         const int S = e->cfg.num_simulations;
-        if (!sp.arena && !sp.preset && e->ops->search_prepare(S, 2, synth, e->cfg.model)) e->persist_gp = 2;
+        if (!sp.arena && (!sp.preset || sp.batch) && e->ops->search_prepare(S, 2, synth, e->cfg.model)) e->persist_gp = 2;
         else if (e->ops->search_prepare(S, 1, synth, e->cfg.model)) e->persist_gp = 1;     // arena: a workgroup's games must share one net
     }
     az_engine::Run &r = e->run;
@@ -1002,13 +1009,14 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
             HIPCHECK(e, hipMemsetAsync(L.s_status.p, 0, L.s_status.bytes, L.stream));
             hipLaunchKernelGGL(k_refill, dim3(1), dim3(1024), 0, L.stream, L.d, share, e->compact ? 1 : 0);
             HIPCHECK(e, hipMemcpyAsync(&L.active, L.active_dev.p, 4, hipMemcpyDeviceToHost, L.stream));
-        } else if (L.index != 0) {
-            HIPCHECK(e, hipMemsetAsync(L.s_status.p, 0, L.s_status.bytes, L.stream));
+        } else {
+            if (L.preset_m == 0) HIPCHECK(e, hipMemsetAsync(L.s_status.p, 0, L.s_status.bytes, L.stream));
+            L.active = L.preset_m;
+            if (sp.batch && L.preset_m > 0) L.cur = L.preset_m;
         }
         HIPCHECK(e, hipStreamSynchronize(L.stream));
         if (!sp.preset && e->compact && !e->reuse) L.cur = L.active;       // the active slots are the first L.active ones
     }
-    if (sp.preset) e->lanes[0].active = 1;
     r.open = true;
     e->have_episode = false;
     return AZ_OK;
@@ -1261,7 +1269,7 @@ static int episode_end(az_engine *e, az_counters *out)
     HIPCHECK(e, az_memcpy(e->stream, e->h_nply.data(), e->g_nply.p, (size_t)r.num_games * 4, hipMemcpyDeviceToHost));
     HIPCHECK(e, az_memcpy(e->stream, e->h_result.data(), e->g_result.p, (size_t)r.num_games * 4, hipMemcpyDeviceToHost));
     if (r.preset) {
-        e->h_nply[0] = 1;   // az_search plays exactly one ply; the game itself is not finished by it
+        e->h_nply.assign(r.num_games, 1);   // a preset search plays exactly one ply; the game itself is not finished by it
     } else {
         // games still in flight when the caller stops early: report the plies played so far
         for (Lane &L : e->lanes) {
@@ -1587,6 +1595,7 @@ extern "C" int az_search(az_engine *e, int slot, const uint8_t *board, int playe
     const float *sv2w = L0.d.v2w[0], *sv2b = L0.d.v2b[0];
     // (the evaluation cache keys its entries by net id: the swapped search runs under its own cache generation)
     if (slot == 1) { e->net[0] = e->net[1]; L0.d.v2w[0] = L0.d.v2w[1]; L0.d.v2b[0] = L0.d.v2b[1]; e->cache_gen ^= 0x80000000u; }
+    for (Lane &L : e->lanes) L.preset_m = L.index == 0 ? 1 : 0;
     rc = run_episode(e, sp, nullptr);
     if (slot == 1) { e->net[0] = saved0; L0.d.v2w[0] = sv2w; L0.d.v2b[0] = sv2b; e->cache_gen ^= 0x80000000u; }
     if (rc) return rc;
@@ -1609,6 +1618,151 @@ extern "C" int az_search(az_engine *e, int slot, const uint8_t *board, int playe
         }
     }
     e->have_episode = false;
+    return AZ_OK;
+}
+
+// ---- many positions at once: MCTS.run for every position of a list ----
+// Waves of at most `slots` positions; a wave is ONE ply of every lane (a one-ply episode whose game i is position i of the
+// wave), so the searches of a wave share every evaluation batch.  Position i of the wave sits in slot i - first(l) of lane l.
+static void add_counters(az_counters &t, const az_counters &c)
+{
+    t.games += c.games; t.plies += c.plies; t.records += c.records; t.simulations += c.simulations;
+    t.expansions += c.expansions; t.root_evals += c.root_evals; t.terminal_hits += c.terminal_hits; t.depth_sum += c.depth_sum;
+    t.steps += c.steps; t.seconds += c.seconds; t.nn_seconds += c.nn_seconds; t.trunk_seconds += c.trunk_seconds;
+    t.trunk_launches += c.trunk_launches; t.trunk_boards += c.trunk_boards; t.step_seconds += c.step_seconds;
+    t.duplicate_leaves += c.duplicate_leaves; t.cache_lookups += c.cache_lookups; t.cache_hits += c.cache_hits;
+    t.tape_wait_seconds = std::max(t.tape_wait_seconds, c.tape_wait_seconds);
+    t.tape_threads = c.tape_threads; t.host_cpus = c.host_cpus;
+}
+
+extern "C" int az_search_batch(az_engine *e, int slot, int count, const uint8_t *boards, const uint8_t *players,
+                               const int16_t *lasts, const double *temperatures, const double *noise, const double *u,
+                               float *pi, int32_t *actions, int32_t *visits, double *W, float *prior)
+{
+    if (!e || slot < 0 || slot > 1 || count < 0) return fail(e, AZ_ERR_INVALID, "az_search_batch: bad argument");
+    if (count == 0) return AZ_OK;
+    if (!boards || !players || !lasts || !temperatures || !u) return fail(e, AZ_ERR_INVALID, "az_search_batch: null argument");
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_search_batch: a self-play episode is open on this engine");
+    const int nn = e->nn, K = (int)e->lanes.size();
+    // every position is checked on the host before any GPU work: an error leaves every output untouched
+    for (int i = 0; i < count; i++) {
+        const uint8_t *bd = boards + (size_t)i * nn;
+        if (players[i] != 1 && players[i] != 2) return fail(e, AZ_ERR_INVALID, "az_search_batch: position %d: player %d", i, players[i]);
+        int st = 0;
+        for (int j = 0; j < nn; j++) {
+            if (bd[j] > 2) return fail(e, AZ_ERR_INVALID, "az_search_batch: position %d: cell value %d", i, bd[j]);
+            st += bd[j] != 0;
+        }
+        if (st >= nn) return fail(e, AZ_ERR_INVALID, "az_search_batch: position %d: no legal action", i);
+        if (lasts[i] >= nn || (lasts[i] >= 0 && bd[lasts[i]] == 0)) return fail(e, AZ_ERR_INVALID, "az_search_batch: position %d: bad last action", i);
+    }
+    if (e->cfg.eval_kind == AZ_EVAL_NET && !e->net[slot].loaded) return fail(e, AZ_ERR_NO_WEIGHTS, "weights slot %d not loaded", slot);
+    if (K > BATCH_MAX_LANES) return fail(e, AZ_ERR_INVALID, "az_search_batch: more than %d lanes", BATCH_MAX_LANES);
+    DEVICE_GUARD(e);
+    const int Wv = std::min(count, e->cfg.slots);           // positions per wave: everything below is sized by it, not by count
+    int rc = ensure_episode_buffers(e, Wv, false);
+    const size_t wn = (size_t)Wv * nn;
+    if (!rc && noise) rc = dev_alloc(e, e->noise, wn * 8, false);
+    if (!rc && !e->bt_zero_off.p) rc = dev_alloc(e, e->bt_zero_off, (size_t)(nn + 2) * sizeof(int), true);
+    if (!rc) rc = dev_alloc(e, e->bt_cells, wn, false);
+    if (!rc) rc = dev_alloc(e, e->bt_players, (size_t)Wv, false);
+    if (!rc) rc = dev_alloc(e, e->bt_lasts, (size_t)Wv * 2, false);
+    if (!rc) rc = dev_alloc(e, e->bt_T, (size_t)Wv * 8, false);
+    if (!rc && visits) rc = dev_alloc(e, e->bt_visits, wn * 4, false);
+    if (!rc && W) rc = dev_alloc(e, e->bt_W, wn * 8, false);
+    if (!rc && prior) rc = dev_alloc(e, e->bt_prior, wn * 4, false);
+    if (!rc && pi) rc = dev_alloc(e, e->bt_pi, wn * 4, false);
+    if (!rc && actions) rc = dev_alloc(e, e->bt_action, (size_t)Wv * 4, false);
+    if (rc) return rc;
+    // The lanes' states for this call: per-position temperatures, key 0 for every position, and the compact noise rows.  The
+    // baseline net (slot 1) searches as net 0 under its own cache generation, like az_search.  Everything is put back on
+    // every way out, so that no other entry point ever sees these values.
+    const PackedNet saved0 = e->net[0];
+    const float *sv2w = e->lanes[0].d.v2w[0], *sv2b = e->lanes[0].d.v2b[0];
+    struct Restore {
+        az_engine *e; int slot; const PackedNet &saved0; const float *sv2w, *sv2b;
+        ~Restore()
+        {
+            if (slot == 1) { e->net[0] = saved0; e->cache_gen ^= 0x80000000u; }
+            each_state(e, [&](DevState &d) {
+                d.T_game = nullptr; d.key_stride = 1; d.noise_off = (const int *)e->noise_off.p; d.noise_stride = e->tape_len;
+                if (slot == 1) { d.v2w[0] = sv2w; d.v2b[0] = sv2b; d.cache_gen = e->cache_gen; }
+            });
+            for (Lane &L : e->lanes) L.preset_m = 0;
+            e->have_episode = false;
+        }
+    } restore{e, slot, saved0, sv2w, sv2b};
+    if (slot == 1) { e->net[0] = e->net[1]; e->cache_gen ^= 0x80000000u; }
+    each_state(e, [&](DevState &d) {
+        d.T_game = (const double *)e->bt_T.p; d.key_stride = 0; d.noise_off = (const int *)e->bt_zero_off.p;
+        d.noise = (const double *)e->noise.p; d.noise_stride = nn;
+        if (slot == 1) { d.v2w[0] = d.v2w[1]; d.v2b[0] = d.v2b[1]; }
+    });
+    EpisodeSpec sp;
+    sp.max_plies = 0; sp.add_noise = noise != nullptr; sp.arena = false; sp.preset = true; sp.batch = true; sp.profile = false;
+    az_counters total{};
+    std::vector<double> hu(wn);
+    for (int w0 = 0; w0 < count; w0 += Wv) {
+        const int m = std::min(Wv, count - w0);
+        // the wave's positions over the lanes: an even share each, what a lane cannot hold goes to the lanes with room
+        BatchLanes bl{};
+        bl.K = K; bl.L = e->lanes[0].d.L;
+        int left = m;
+        for (int l = 0; l < K; l++) {
+            Lane &L = e->lanes[l];
+            L.preset_m = std::min(L.d.B, (left + (K - l) - 1) / (K - l));
+            left -= L.preset_m;
+        }
+        for (int l = 0; l < K && left > 0; l++) {
+            Lane &L = e->lanes[l];
+            const int add = std::min(L.d.B - L.preset_m, left);
+            L.preset_m += add; left -= add;
+        }
+        int first = 0;
+        for (int l = 0; l < K; l++) {
+            const Lane &L = e->lanes[l];
+            BatchLane &b = bl.lane[l];
+            b.board = L.d.board; b.s_game = L.d.s_game; b.s_ply = L.d.s_ply; b.s_player = L.d.s_player; b.s_last = L.d.s_last;
+            b.s_status = L.d.s_status; b.leaf_kind = L.d.leaf_kind; b.carried = L.d.carried; b.edges = L.d.edges;
+            b.B = L.d.B; b.first = first; b.m = L.preset_m;
+            first += L.preset_m;
+        }
+        // u is read at d.u[game * nn + ply]: scattered here, the other entries of the row are never read
+        std::fill(hu.begin(), hu.begin() + (size_t)m * nn, 0.0);
+        for (int i = 0; i < m; i++) {
+            const uint8_t *bd = boards + (size_t)(w0 + i) * nn;
+            int st = 0;
+            for (int j = 0; j < nn; j++) st += bd[j] != 0;
+            hu[(size_t)i * nn + st] = u[w0 + i];
+        }
+        HIPCHECK(e, hipMemcpyAsync(e->bt_cells.p, boards + (size_t)w0 * nn, (size_t)m * nn, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(e->bt_players.p, players + w0, (size_t)m, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(e->bt_lasts.p, lasts + w0, (size_t)m * 2, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(e->bt_T.p, temperatures + w0, (size_t)m * 8, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(e->u.p, hu.data(), (size_t)m * nn * 8, hipMemcpyHostToDevice, e->stream));
+        if (noise) HIPCHECK(e, hipMemcpyAsync(e->noise.p, noise + (size_t)w0 * nn, (size_t)m * nn * 8, hipMemcpyHostToDevice, e->stream));
+        e->ops->set_positions(e->stream, bl, (const unsigned char *)e->bt_cells.p, (const unsigned char *)e->bt_players.p,
+                              (const short *)e->bt_lasts.p);
+        HIPCHECK(e, hipStreamSynchronize(e->stream));
+        HIPCHECK(e, hipGetLastError());
+        sp.num_games = m;
+        az_counters c{};
+        if ((rc = run_episode(e, sp, &c))) return rc;
+        add_counters(total, c);
+        // the lanes' streams are drained: every slot's root row and record into the compact staging, one copy per output
+        e->ops->gather_roots(e->stream, bl, e->lanes[0].d, (const unsigned char *)e->bt_cells.p, visits ? (int *)e->bt_visits.p : nullptr, W ? (double *)e->bt_W.p : nullptr,
+                             prior ? (float *)e->bt_prior.p : nullptr, pi ? (float *)e->bt_pi.p : nullptr,
+                             actions ? (int *)e->bt_action.p : nullptr);
+        const size_t o = (size_t)w0 * nn, mn = (size_t)m * nn;
+        if (visits) HIPCHECK(e, hipMemcpyAsync(visits + o, e->bt_visits.p, mn * 4, hipMemcpyDeviceToHost, e->stream));
+        if (W) HIPCHECK(e, hipMemcpyAsync(W + o, e->bt_W.p, mn * 8, hipMemcpyDeviceToHost, e->stream));
+        if (prior) HIPCHECK(e, hipMemcpyAsync(prior + o, e->bt_prior.p, mn * 4, hipMemcpyDeviceToHost, e->stream));
+        if (pi) HIPCHECK(e, hipMemcpyAsync(pi + o, e->bt_pi.p, mn * 4, hipMemcpyDeviceToHost, e->stream));
+        if (actions) HIPCHECK(e, hipMemcpyAsync(actions + w0, e->bt_action.p, (size_t)m * 4, hipMemcpyDeviceToHost, e->stream));
+        HIPCHECK(e, hipStreamSynchronize(e->stream));
+        HIPCHECK(e, hipGetLastError());
+    }
+    e->last = total;
     return AZ_OK;
 }
 

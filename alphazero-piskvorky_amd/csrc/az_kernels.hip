@@ -188,10 +188,31 @@ void eval_tail_l(const LaunchCtx &c, int count, float *pol, float *val)
     dim3 g((count + 3) / 4), b(256);
     hipLaunchKernelGGL(k_eval_tail<N>, g, b, 0, c.stream, c.dv, count, pol, val);
 }
+
+int batch_slots(const BatchLanes &bl)
+{
+    int slots = 0;
+    for (int l = 0; l < bl.K; l++) slots += bl.lane[l].B;
+    return slots;
+}
+
+void set_positions(hipStream_t stream, const BatchLanes &bl, const unsigned char *cells, const unsigned char *players, const short *lasts)
+{
+    dim3 g((batch_slots(bl) + 3) / 4), b(256);
+    hipLaunchKernelGGL(k_set_positions<N>, g, b, 0, stream, bl, cells, players, lasts);
+}
+
+void gather_roots(hipStream_t stream, const BatchLanes &bl, const DevState &d, const unsigned char *cells, int *visits, double *W, float *prior, float *pi, int *action)
+{
+    dim3 g((batch_slots(bl) + 3) / 4), b(256);
+    hipLaunchKernelGGL(k_gather_roots<N>, g, b, 0, stream, bl, d.R, d.S, cells, (const float *)d.rec_pi,
+                       (const short *)d.rec_action, visits, W, prior, pi, action);
+}
 }   // namespace
 
 const SizeOps *AZ_CAT(az_size_ops_, AZ_N)()
 {
-    static const SizeOps ops = {trunk, trunk_split, split_scratch_floats, fc, step, step_vl, root_cache, search_prepare, search, move, eval_tail_l};
+    static const SizeOps ops = {trunk, trunk_split, split_scratch_floats, fc, step, step_vl, root_cache, search_prepare, search, move, eval_tail_l,
+                                set_positions, gather_roots};
     return &ops;
 }

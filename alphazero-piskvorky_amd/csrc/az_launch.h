@@ -4,6 +4,7 @@
 #include "az_net.h"
 #include "az_net_emul.h"
 #include "az_search.h"
+#include "az_batch.h"
 
 struct LaunchCtx {
     hipStream_t stream;
@@ -37,6 +38,10 @@ struct SizeOps {
     void (*search)(const LaunchCtx &, int games);
     void (*move)(const LaunchCtx &);
     void (*eval_tail)(const LaunchCtx &, int count, float *policy, float *value);
+    // az_search_batch (az_batch.h), one launch over the slots of every lane: the given positions into the slots, and after
+    // the ply every slot's root row and record into compact [wave][n*n] staging (null outputs are skipped)
+    void (*set_positions)(hipStream_t, const BatchLanes &, const unsigned char *cells, const unsigned char *players, const short *lasts);
+    void (*gather_roots)(hipStream_t, const BatchLanes &, const DevState &, const unsigned char *cells, int *visits, double *W, float *prior, float *pi, int *action);
 };
 
 const SizeOps *az_size_ops(int n);     // nullptr for unsupported sizes

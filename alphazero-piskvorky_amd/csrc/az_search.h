@@ -229,7 +229,7 @@ __device__ __forceinline__ void step_lds(const DevState &d, int b, int lane, Edg
         gs.leaf_last = last;
         gs.leaf_kind = out_kind;
         gs.depth = depth;
-        if (d.leaf_sym) gs.sym = leaf_sym_of((int)(d.game_key0 + (unsigned)game), ply, rootN + 1);     // this leaf is evaluation rootN + 1 of the search (as k_step)
+        if (d.leaf_sym) gs.sym = leaf_sym_of(game_key(d, game), ply, rootN + 1);     // this leaf is evaluation rootN + 1 of the search (as k_step)
     }
     ST_STAMP(14);                    // selection: `depth` levels
 #ifdef AZ_STAMPS

@@ -87,7 +87,12 @@ struct DevState {
     int ext_eval;          // the pending rows were filled by an evaluator outside the engine (az_search_callback): priors and value as given
     unsigned game_key0;    // leaf-symmetry hash key of game id 0 = low 32 bits of the episode's seed0: key(g) = game_key0 + g is the game's
                            // seed, a GLOBAL name of the game that does not depend on which rank / slot / lane plays it
+    unsigned key_stride;   // key(g) = game_key0 + key_stride * g.  1 everywhere; 0 in az_search_batch, whose positions all carry
+                           // key 0 like az_search's, so that a result never depends on the position's index in the batch
+    const double *T_game;  // [G] temperature per game, preferred over T_table by k_move when set (az_search_batch: positions with
+                           // the same stone count may ask for different temperatures); nullptr everywhere else
 };
+__device__ __forceinline__ int game_key(const DevState &d, int game) { return (int)(d.game_key0 + d.key_stride * (unsigned)game); }
 
 template <int N>
 struct TreeGeo {
@@ -300,7 +305,7 @@ __global__ void k_begin(DevState d)
         lf[4 + i] = pl == 1 ? bd[4 + i] : bd[i];
     }
     d.leaf_last[it] = d.s_last[b];
-    if (d.leaf_sym) d.leaf_sym[it] = leaf_sym_of((int)(d.game_key0 + (unsigned)d.s_game[b]), d.s_ply[b], 0);
+    if (d.leaf_sym) d.leaf_sym[it] = leaf_sym_of(game_key(d, d.s_game[b]), d.s_ply[b], 0);
     d.leaf_kind[it] = (d.reuse && d.carried[b] >= 0) ? LEAF_REUSE : LEAF_ROOT;
     d.depth[it] = 0;
     const int netid = d.arena ? (pl == 1 ? 0 : 1) : 0;   // evaluator.py:73-79: each side searches with its own net
@@ -561,7 +566,7 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
     if (!SYNTH && d.cache && out_kind == LEAF_EXPAND) {
         // the leaf's evaluation may be known already (an earlier ply's search, another game, a transposition)
         float cx[G::CPL], ch;
-        const int sym = d.leaf_sym ? leaf_sym_of((int)(d.game_key0 + (unsigned)game), ply, rootN + 1) : 0;     // as stored below
+        const int sym = d.leaf_sym ? leaf_sym_of(game_key(d, game), ply, rootN + 1) : 0;     // as stored below
         const bool hit = cache_lookup<N>(d, me, opp, last, cache_net_key(netid, sym), lane, cx, ch);
         if (hit) {
             cache_hit_store<N>(d.logits + (size_t)b * G::RW, cx, lane, d.leaf_sym != nullptr, sym);
@@ -579,7 +584,7 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
         d.leaf_last[b] = last;
         d.leaf_kind[b] = out_kind;
         d.depth[b] = depth;
-        if (d.leaf_sym) d.leaf_sym[b] = leaf_sym_of((int)(d.game_key0 + (unsigned)game), ply, rootN + 1);     // this leaf is evaluation rootN + 1 of the search
+        if (d.leaf_sym) d.leaf_sym[b] = leaf_sym_of(game_key(d, game), ply, rootN + 1);     // this leaf is evaluation rootN + 1 of the search
     }
 }
 
@@ -864,7 +869,7 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
                 mark = leaf_edge;
                 if (!SYNTH && d.cache) {
                     float cx[G::CPL], ch;
-                    const int sym = d.leaf_sym ? leaf_sym_of((int)(d.game_key0 + (unsigned)game), ply, sims_done + j + 1) : 0;
+                    const int sym = d.leaf_sym ? leaf_sym_of(game_key(d, game), ply, sims_done + j + 1) : 0;
                     const bool hit = cache_lookup<N>(d, me, opp, last, cache_net_key(netid, sym), lane, cx, ch);
                     if (hit) {
                         cache_hit_store<N>(d.logits + it * G::RW, cx, lane, d.leaf_sym != nullptr, sym);
@@ -884,7 +889,7 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
             d.leaf_kind[it] = out_kind;
             d.depth[it] = depth;
             // simulation sims_done + j of the search: its leaf is evaluation sims_done + j + 1 (0 = the root), as in k_step
-            if (d.leaf_sym) d.leaf_sym[it] = leaf_sym_of((int)(d.game_key0 + (unsigned)game), ply, sims_done + j + 1);
+            if (d.leaf_sym) d.leaf_sym[it] = leaf_sym_of(game_key(d, game), ply, sims_done + j + 1);
         }
         wave_mem_sync();
     }
@@ -938,7 +943,7 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
     for (int q = 0; q < 4; q++) occ.w[q] = X.w[q] | O.w[q];
     const int A = G::nn - pl_count(occ);
     const Edge *root = d.edges + (size_t)b * d.R * G::RW;
-    const double T = d.T_table[d.arena ? ((ply + 1) >> 1) : ply];   // evaluator.py:71-90 step quirk
+    const double T = d.T_game ? d.T_game[g] : d.T_table[d.arena ? ((ply + 1) >> 1) : ply];   // evaluator.py:71-90 step quirk
     const double u = d.u[(size_t)g * G::nn + ply];
 
     int Nj[G::CPL], rank[G::CPL];

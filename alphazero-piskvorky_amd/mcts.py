@@ -32,6 +32,8 @@ class MCTS:
         self.virtual_loss = virtual_loss      # opt-in: leaves per evaluation batch (az_set_virtual_loss); 1 = the reference's loop
         self._engine = None
         self._version = None
+        self._batch_engine = None             # run_many's own engine; run() and its one-slot engine are untouched by it
+        self._batch_version = None
 
     def _eng_external(self, n, k):
         if self._engine is None or (self._engine.n, self._engine.k) != (n, k):
@@ -84,3 +86,78 @@ class MCTS:
         a = r["action"]
         self.last_visits = r["N"].reshape(n, n)
         return r["pi"].reshape(n, n), (a // n, a % n)
+
+    # ---- many positions at once (az_search_batch) ----
+    BATCH_MIN_SLOTS, BATCH_MAX_SLOTS = 64, 1024
+
+    def _eng_batch(self, n, k, count):
+        """run_many's engine: slots = the next power of two >= count inside [64, 1024]; grows with a larger batch, never shrinks"""
+        ctrl = self.policy_value_fn.controller
+        slots = self.BATCH_MIN_SLOTS
+        while slots < min(count, self.BATCH_MAX_SLOTS):
+            slots *= 2
+        eng = self._batch_engine
+        if eng is None or (eng.n, eng.k) != (n, k) or eng.slots < slots:
+            if eng is not None:
+                eng.close()
+            self._batch_engine = Engine(n, k, self.num_simulations, slots, c_puct=self.c_puct,
+                                        dirichlet_alpha=self.dirichlet_alpha, dirichlet_weight=self.dirichlet_weight,
+                                        device=device_index(ctrl.device), log_table=numpy_log_table(self.num_simulations),
+                                        model=model_kind(ctrl.net), deep=self.num_simulations > AZ_MAX_SIMULATIONS)
+            self._batch_engine.set_virtual_loss(self.virtual_loss)
+            self._batch_version = None
+        ver = weights_version(ctrl.net)
+        if ver != self._batch_version:
+            self._batch_engine.load_weights(ctrl.net.state_dict(), 0)
+            self._batch_version = ver
+        return self._batch_engine
+
+    def run_many(self, states, temperature, add_root_noise=False):
+        """run() for every state of a list, searched together on the GPU: [(pi [n, n], move or None), ...].  Draws from
+        numpy's global RNG in the order a loop of run() would -- per state the Dirichlet sample when add_root_noise, then
+        one random_sample(); a state without a legal cell draws nothing -- so after np.random.seed(s) the result equals
+        [run(s_i, T_i) for s_i in states].  temperature: a scalar or one value per state.  With a plain callable as the
+        evaluator this IS that loop (az_search_callback: compatible, not fast)."""
+        states = list(states)
+        count = len(states)
+        T = np.asarray(temperature, np.float64)
+        if T.ndim == 0:
+            T = np.full(count, float(T), np.float64)
+        if T.shape != (count,):
+            raise ValueError(f"temperature must be a scalar or have one entry per state ({count})")
+        if count == 0:
+            self.last_visits = np.zeros((0, 0, 0), np.int32)
+            return []
+        n, k = states[0].board_size, states[0].win_length
+        if any((s.board_size, s.win_length) != (n, k) for s in states):
+            raise ValueError("run_many: the states differ in board size or win length")
+        if self._external:
+            out, visits = [], np.zeros((count, n, n), np.int32)
+            for i, s in enumerate(states):
+                out.append(self.run(s, T[i], add_root_noise))
+                if out[-1][1] is not None:
+                    visits[i] = self.last_visits
+            self.last_visits = visits
+            return out
+        live, noise, us = [], [], []
+        for i, s in enumerate(states):
+            legal = int((s.cells == 0).sum())
+            if legal == 0:
+                continue                                                # mcts.py:152-153: nothing is drawn
+            if add_root_noise:
+                noise.append(np.random.dirichlet([self.dirichlet_alpha] * legal))
+            us.append(np.random.random_sample())
+            live.append(i)
+        out = [(np.zeros((n, n), dtype=np.float32), None) for _ in range(count)]     # mcts.py:152-153 for the full boards
+        visits = np.zeros((count, n, n), np.int32)
+        if live:
+            eng = self._eng_batch(n, k, len(live))
+            r = eng.search_batch(np.stack([np.asarray(states[i].cells, np.uint8).reshape(n * n) for i in live]),
+                                 [states[i].player_code() for i in live], [states[i].last_index() for i in live],
+                                 T[live], noise if add_root_noise else None, us)
+            for j, i in enumerate(live):
+                a = int(r["action"][j])
+                out[i] = (r["pi"][j].reshape(n, n), (a // n, a % n))
+                visits[i] = r["N"][j].reshape(n, n)
+        self.last_visits = visits
+        return out

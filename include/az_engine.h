@@ -124,6 +124,33 @@ int az_search(az_engine *e, int slot, const uint8_t *board, int player, int last
               const double *noise, double u, float *pi, int32_t *action, int32_t *visits, double *W,
               float *prior);
 
+/* ---- many positions at once: MCTS.run (mcts.py:101-183) for every position of a list ----
+ * The throughput form of az_search: the positions are searched in waves of at most `slots`, every wave as one ply of every
+ * lane, so the searches share their evaluation batches instead of each being a latency-bound chain over one board.  The
+ * outputs of position i are exactly what az_search(e, slot, boards[i], players[i], lasts[i], temperatures[i],
+ * noise ? row i : NULL, u[i], ...) returns on the same engine, whatever count, slots and lanes are, and with every search
+ * option (virtual-loss batching, evaluation cache, random-symmetry leaf evaluation with key 0 for every position as in
+ * az_search, both nets, the synthetic evaluator, the emulated trunks, deep engines; boards up to 7x7 run on the persistent
+ * search kernel).  Every search starts from a fresh root.  Noise is all or nothing per call.
+ * Every position is checked on the host first, by az_search's rules (cell values, at least one legal action, last in range
+ * and on an occupied cell, player 1 or 2): AZ_ERR_INVALID, with the index of the first offending position in az_last_error
+ * and no output written.  count = 0 returns AZ_OK and touches nothing.  AZ_ERR_STATE while an episode is open;
+ * AZ_ERR_NO_WEIGHTS as az_search.  Like az_search the call forgets the last self-play episode (az_selfplay_games /
+ * az_selfplay_records then fail with AZ_ERR_STATE).  Afterwards az_get_counters reports the sums over the whole batch
+ * (simulations = count * num_simulations, root_evals = plies = count).  Device and host memory of the call are bounded by
+ * the engine's slots, not by count. */
+int az_search_batch(az_engine *e, int slot, int count,
+                    const uint8_t *boards,        /* [count][n*n] absolute cells 0 / 1 X / 2 O          */
+                    const uint8_t *players,       /* [count] side to move, 1 / 2                        */
+                    const int16_t *lasts,         /* [count] last action r*n+c, -1 none                 */
+                    const double *temperatures,   /* [count], one per position (np.float64 schedules)  */
+                    const double *noise,          /* NULL = add_root_noise False for all; else [count][n*n]: row i holds the Dirichlet
+                                                     sample of position i over its legal cells in row-major order in its first
+                                                     (n*n - stones_i) entries, the rest is ignored */
+                    const double *u,              /* [count] the np.random.choice draw of each search  */
+                    float *pi, int32_t *actions, int32_t *visits, double *W, float *prior);
+                    /* outputs [count][n*n] (actions: [count]); any may be NULL */
+
 /* ---- the same search with the evaluator outside the engine: the policy_value_fn plugin seam (mcts.py:87-93) ----
  * The reference's MCTS takes ANY callable state -> (policy float32[n,n], value float) (controller.py:39-53 is just the
  * one the training loop uses).  az_search_callback keeps that seam: select / expand / backup / pi extraction run on the
