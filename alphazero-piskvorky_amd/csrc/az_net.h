@@ -71,6 +71,7 @@ struct NetGeo {
     // image, so the 16 lanes of a fragment hit 16 consecutive LDS banks); other sizes: 16 consecutive cells.
     static constexpr bool ROWT = (N == 15);
     static constexpr int MT = ROWT ? G * N : (M + 15) / 16, MR = MT * 16;
+    static constexpr bool BORDER_SKIP = ROWT && G == 1;            // cell tile t is board row t: conv_layer leaves out the taps on the zero rows
     static constexpr int CS = up16(G * PP);                        // channel stride of padded planes (floats), == 16 mod 32
     static constexpr int CS3 = up16(MR);                           // channel stride of the conv3 output image
     static constexpr int LDSF = (96 * CS > 128 * CS3) ? 96 * CS : 128 * CS3;
@@ -167,6 +168,46 @@ __device__ __forceinline__ ConvPre<CIN> conv_prefetch(const float *__restrict__ 
     return r;
 }
 
+// Border rows of a row-tiled single-board geometry (n = 15: cell tile t is board row t).  The three taps with ky = 0 of row 0 and
+// the three with ky = 2 of row n - 1 read nothing but the top / bottom padding row of the LDS image, which is zero by
+// construction: conv_layer leaves their MFMAs (and fragment reads) out.  Only a geometry that says so (BORDER_SKIP) is
+// touched: the tile-split geometries (TileGeoT::A / B) and the persistent search kernel's have no such member and compile to
+// the code they had.
+// Exactness: for a finite weight fma(w, +0, acc) == acc bit for bit unless acc is -0 (then +0).  A -0 accumulator can only
+// come from a real product that underflowed, and the layer's output erases its sign in both variants: acc + bias, then
+// v > 0 ? v : +0 (the residual paths likewise), so every layer output keeps its bits.  With a non-finite weight the full chain
+// made NaN on the border rows where the oracle (conv3x3_core: out-of-board taps skipped) does not: the skip is the definition.
+template <class G, class = void>
+struct BorderSkip { static constexpr bool value = false; static constexpr int n = 0; };
+template <class G>
+struct BorderSkip<G, std::void_t<decltype(G::BORDER_SKIP)>> { static constexpr bool value = G::BORDER_SKIP; static constexpr int n = G::n; };
+
+// tile i of cell-tile group mgc (board row mgc + i * MG) has nothing to add at this tap
+template <bool SKIP, int N, int MG>
+__host__ __device__ constexpr bool border_dead(int mgc, int i, int tap)
+{
+    if (!SKIP) return false;
+    const int row = mgc + i * MG;
+    return (row == 0 && tap / 3 == 0) || (row == N - 1 && tap / 3 == 2);
+}
+template <bool SKIP, int N, int MG>
+__host__ __device__ constexpr int border_live(int mgc, int mtw, int tap)
+{
+    int c = 0;
+    for (int i = 0; i < mtw; i++) c += border_dead<SKIP, N, MG>(mgc, i, tap) ? 0 : 1;
+    return c;
+}
+
+// Runs body(cell tiles of the wave's cell-tile group, the group) with BOTH as compile-time values: one body per group.
+template <int K, int MG, int MT_FULL, int MT_REM, class B>
+__device__ __forceinline__ void conv_by_group(int mg, B &body)
+{
+    constexpr int MTW = MT_FULL + (K < MT_REM ? 1 : 0);
+    if constexpr (K + 1 == MG) body(std::integral_constant<int, MTW>{}, std::integral_constant<int, K>{});
+    else if (mg == K) body(std::integral_constant<int, MTW>{}, std::integral_constant<int, K>{});
+    else conv_by_group<K + 1, MG, MT_FULL, MT_REM>(mg, body);
+}
+
 template <class G, int CIN, int COUT, int MODE, int MTL = G::MT, class GO = G, int O3S = G::CS3>
 __device__ __forceinline__ void conv_layer(const float *in, float *out, const float *__restrict__ wp,
                                            const float *__restrict__ bias, const unsigned short *wpos,
@@ -193,9 +234,14 @@ __device__ __forceinline__ void conv_layer(const float *in, float *out, const fl
     constexpr int KS4 = (KS + 3) / 4;
     const int ng = wave % NG, mg = wave / NG;       // wave is wave-uniform (readfirstlane) -> scalar control flow
     const int q = lane >> 4, r16 = lane & 15;
+    // border rows (BorderSkip above): the packed-input layers of a fused row-tiled kernel; the cell-tile group is then a
+    // compile-time value of the body (MGC), so that "tile i is row 0 / row n - 1" folds away in the unrolled tap loop
+    constexpr bool SKIP = BorderSkip<G>::value && !SUBSET && CIN >= 32;
+    constexpr int BN = BorderSkip<G>::n;
 
-    auto body = [&](auto mtw_c) __attribute__((always_inline)) {
+    auto body = [&](auto mtw_c, auto mg_c) __attribute__((always_inline)) {
     constexpr int MTW = decltype(mtw_c)::value;
+    constexpr int MGC = decltype(mg_c)::value;      // the wave's cell-tile group where SKIP, else unused
     if constexpr (MTW == 0) {
         if constexpr (OUT3) __syncthreads();       // a wave without a tile still meets the layer's barrier
     } else {
@@ -251,7 +297,8 @@ __device__ __forceinline__ void conv_layer(const float *in, float *out, const fl
 #pragma unroll
         for (int j = 0; j < NQ; j++) bw[j] = pre ? pre->bw[j] : wp4[(size_t)j * 64];
 #pragma unroll
-        for (int i = 0; i < MTW; i++) a0[i] = in4[ra[i]];
+        for (int i = 0; i < MTW; i++)
+            if (!border_dead<SKIP, BN, MG>(MGC, i, 0)) a0[i] = in4[ra[i]];
         // The nine taps unrolled, so that every fragment address is the tile's base register + a constant (the ds_read's
         // 16-bit immediate: at most ((NQ - 1) 4 CS + 2 PW + 2) x 16 B = 58.9 KB at n = 15) and the weight registers of
         // consecutive taps are renamed instead of copied.  The rolled loop kept a running index per tile and recomputed
@@ -280,21 +327,28 @@ __device__ __forceinline__ void conv_layer(const float *in, float *out, const fl
                 // first group of the next tap (the last group of all reads its own again: never used)
                 const int gtap = sq + 1 < NQ ? tap : tn, gsq = sq + 1 < NQ ? sq + 1 : (tap + 1 < 9 ? 0 : sq);
                 const int noff = gsq * 4 * G::CS + (gtap / 3) * G::PW + (gtap % 3);
+                // a tile on a border row neither reads nor multiplies the fragments of its zero row
 #pragma unroll
-                for (int i = 0; i < MTW; i++) nxt[i] = in4[ra[i] + noff];
+                for (int i = 0; i < MTW; i++)
+                    if (!border_dead<SKIP, BN, MG>(MGC, i, gtap)) nxt[i] = in4[ra[i] + noff];
 #pragma unroll
                 for (int e = 0; e < 4; e++)
 #pragma unroll
                     for (int i = 0; i < MTW; i++) {
+                        if (border_dead<SKIP, BN, MG>(MGC, i, tap)) continue;
                         const float4 wv = bw[sq];
                         const float we = e == 0 ? wv.x : e == 1 ? wv.y : e == 2 ? wv.z : wv.w;
                         const float ae = e == 0 ? cur[i].x : e == 1 ? cur[i].y : e == 2 ? cur[i].z : cur[i].w;
                         acc[i] = mfma4(we, ae, acc[i]);
                     }
+                // one read after the four MFMAs of a tile; where this group and the next differ in live tiles (the taps next to a
+                // change of ky), the surplus reads follow the last MFMAs, surplus MFMAs go without a read
+                const int nm = border_live<SKIP, BN, MG>(MGC, MTW, tap);
+                const int nr = border_live<SKIP, BN, MG>(MGC, MTW, gtap);
 #pragma unroll
                 for (int i = 0; i < MTW; i++) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);         // 4 MFMAs
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);         // 1 LDS read (b128)
+                    if (i < nm) __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);         // 4 MFMAs
+                    if (i < nr) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);         // 1 LDS read (b128)
                 }
             }
 #pragma unroll
@@ -341,9 +395,11 @@ __device__ __forceinline__ void conv_layer(const float *in, float *out, const fl
     AZ_LSTAMP(3);
     }
     };
-    if constexpr (MT_REM == 0) body(std::integral_constant<int, MT_FULL>{});
-    else if (mg < MT_REM) body(std::integral_constant<int, MT_FULL + 1>{});
-    else body(std::integral_constant<int, MT_FULL>{});
+    typedef std::integral_constant<int, -1> any_group;
+    if constexpr (SKIP) conv_by_group<0, MG, MT_FULL, MT_REM>(mg, body);
+    else if constexpr (MT_REM == 0) body(std::integral_constant<int, MT_FULL>{}, any_group{});
+    else if (mg < MT_REM) body(std::integral_constant<int, MT_FULL + 1>{}, any_group{});
+    else body(std::integral_constant<int, MT_FULL>{}, any_group{});
 }
 
 // policy_conv (128->4) and value_conv (128->2), 1x1 (net.py:64,69): D[head channel][cell] over the float32 conv3 image
