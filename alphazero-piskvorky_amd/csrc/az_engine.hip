@@ -1597,7 +1597,12 @@ extern "C" int az_search(az_engine *e, int slot, const uint8_t *board, int playe
     if (slot == 1) { e->net[0] = e->net[1]; L0.d.v2w[0] = L0.d.v2w[1]; L0.d.v2b[0] = L0.d.v2b[1]; e->cache_gen ^= 0x80000000u; }
     for (Lane &L : e->lanes) L.preset_m = L.index == 0 ? 1 : 0;
     rc = run_episode(e, sp, nullptr);
-    if (slot == 1) { e->net[0] = saved0; L0.d.v2w[0] = sv2w; L0.d.v2b[0] = sv2b; e->cache_gen ^= 0x80000000u; }
+    if (slot == 1) {
+        e->net[0] = saved0; e->cache_gen ^= 0x80000000u;
+        // put back in the states AND their item views (Lane::dv, refreshed by each_state): episode_begin copied the swapped
+        // pointers there, and az_net_eval's tail reads them through the item view without an episode_begin of its own
+        each_state(e, [&](DevState &d) { d.v2w[0] = sv2w; d.v2b[0] = sv2b; d.cache_gen = e->cache_gen; });
+    }
     if (rc) return rc;
     // outputs: record 0*nn + stones
     const size_t ri = (size_t)stones;

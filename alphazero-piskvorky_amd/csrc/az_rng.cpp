@@ -6,8 +6,8 @@
 // The draw sequence per game does not depend on the trajectory, so the host can
 // produce each game's "tape" ahead of the device search.  This file restates the published
 // algorithms of numpy's legacy generator (numpy/random/src/mt19937, src/legacy/legacy-distributions.c)
-// so that RandomState(seed) streams are reproduced bit for bit (tests/test_host_rng.py checks
-// against numpy itself).
+// so that RandomState(seed) streams are reproduced bit for bit (tests/test_host_cpu.py::test_host_rng_*
+// and tests/test_host_properties_cpu.py check against numpy itself).
 #include <cmath>
 #include <cstdint>
 #include <cstring>
