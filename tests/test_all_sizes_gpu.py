@@ -33,7 +33,7 @@ def test_forward_both_models_bit_exact(n, k):
     for model in ("plain", "resnet"):
         sd = synthetic_state_dict(n) if model == "plain" else synthetic_resnet_state_dict(n)
         onet = orc.Net(n, sd) if model == "plain" else orc.Net(n, resnet_tensors=fold_resnet_state_dict(sd))
-        for split in (("0", "1000000") if model == "plain" else ("0",)):      # fused trunk | split trunk (plain net only)
+        for split in ("0", "1000000"):      # fused trunk | tile-split trunk (k_tile, k_tile_res), both nets
             os.environ["AZ_SPLIT_MAX"] = split
             try:
                 e = az.Engine(n, k, 4, 9, model=model)
