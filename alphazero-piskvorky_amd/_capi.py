@@ -32,6 +32,7 @@ EXPORTS = [
     "az_selfplay_begin", "az_selfplay_step", "az_selfplay_end", "az_selfplay_games", "az_selfplay_records", "az_selfplay_clear", "az_record_bytes", "az_selfplay_pack", "az_examples_from_packed",
     "az_examples_gather", "az_arena", "az_rules_replay", "az_rng_selfplay_tape", "az_rng_uniforms", "az_set_profiling", "az_set_subtree_reuse", "az_get_counters", "az_get_lanes", "az_get_persistent", "az_set_virtual_loss", "az_set_eval_cache",
     "az_set_trunk_mode", "az_get_trunk_mode", "az_set_leaf_symmetry", "az_emul_split",
+    "az_set_start_positions", "az_get_start_positions",
     "az_dist_unique_id", "az_dist_init", "az_dist_rank", "az_dist_world", "az_dist_counts", "az_dist_gather_records",
     "az_dist_allreduce_sum", "az_dist_broadcast",
 ]
@@ -125,6 +126,9 @@ def lib():
         L.az_dist_unique_id.argtypes = [C.c_void_p]
         if hasattr(L, "az_search_batch"):        # an experiment build from older sources (AZ_ENGINE_LIB) may lack it
             L.az_search_batch.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 11
+        if hasattr(L, "az_set_start_positions"):
+            L.az_set_start_positions.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+            L.az_get_start_positions.argtypes = [C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -456,6 +460,33 @@ class Engine:
         """Opt-in: every net evaluation of a search sees a pseudo-random dihedral symmetry of the position (SURVEY 8f-2's
         optional half); see include/az_engine.h."""
         self._check(lib().az_set_leaf_symmetry(self.h, 1 if on else 0), "az_set_leaf_symmetry")
+
+    def set_start_positions(self, boards, players, lasts, first=0):
+        """Opt-in: later selfplay* / arena games start from these positions instead of the empty board
+        (az_set_start_positions): boards [count, n*n] or [count, n, n] cells 0 / 1 X / 2 O, players / lasts [count].  Self-play
+        game g starts from position (first + g) % count; arena game g from ((first + g) >> 1) % count, colours exchanged
+        for odd g.  Plies stay absolute (stones on the board); records carry the searched plies only."""
+        nn = self.nn
+        boards = np.ascontiguousarray(boards, np.uint8)
+        if not ((boards.ndim == 2 and boards.shape[1] == nn) or (boards.ndim == 3 and boards.shape[1:] == (self.n, self.n))):
+            raise ValueError(f"boards must be [count, {nn}] or [count, {self.n}, {self.n}], got {boards.shape}")
+        cnt = boards.shape[0]
+        if cnt == 0:
+            raise ValueError("no positions given (clear_start_positions() goes back to the empty board)")
+        boards = boards.reshape(cnt, nn)
+        players = np.ascontiguousarray(players, np.uint8)
+        lasts = np.ascontiguousarray(lasts, np.int16)
+        if players.shape != (cnt,) or lasts.shape != (cnt,):
+            raise ValueError(f"players and lasts must have one entry per position ({cnt})")
+        self._check(lib().az_set_start_positions(self.h, cnt, _p(boards), _p(players), _p(lasts), int(first)),
+                    "az_set_start_positions")
+
+    def clear_start_positions(self):
+        self._check(lib().az_set_start_positions(self.h, 0, None, None, None, 0), "az_set_start_positions")
+
+    def start_positions(self):
+        """Number of start positions in force, 0 = games start from the empty board."""
+        return int(lib().az_get_start_positions(self.h))
 
     def set_trunk_mode(self, mode):
         """Opt-in: "bf16x3" / "f16x2" = fp32-emulating conv trunks on the 16-bit matrix cores (tolerance instead of

@@ -33,9 +33,30 @@ __device__ __forceinline__ bool batch_slot_of(const BatchLanes &bl, int w, int &
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_set_positions: cells[wave][n*n] (0 empty, 1 X, 2 O) -> the slots' bit-planes and game state, as k_set_position and
-// k_refill do for one slot.  Lane j of the wavefront reads cell j + 64 q; the ballots of (cell == 1) and (cell == 2)
-// ARE word q of the X and O planes, and the ply is the popcount of the occupancy.  Slots beyond the lane's share go idle.
+// cells_to_planes: one position's cells[n*n] (0 empty, 1 X, 2 O) -> bit-planes, by the whole wavefront.  Lane j reads cell
+// j + 64 q; the ballots of (cell == 1) and (cell == 2) ARE word q of the X and O planes, and the ply is the popcount of the
+// occupancy.  Returns in lanes 0..3 X word `lane`, in lanes 4..7 O word `lane - 4` (words beyond CPL zero).
+// ------------------------------------------------------------------------------------------------
+template <int N>
+__device__ __forceinline__ u64 cells_to_planes(const unsigned char *__restrict__ cp, int lane, int &ply)
+{
+    typedef TreeGeo<N> G;
+    u64 mine = 0ull;
+    ply = 0;
+#pragma unroll
+    for (int q = 0; q < G::CPL; q++) {
+        const int j = lane + 64 * q;
+        const int c = j < G::nn ? (int)cp[j] : 0;
+        const u64 x = __ballot(c == 1), o = __ballot(c == 2);
+        ply += __popcll(x | o);
+        mine = lane == q ? x : (lane == 4 + q ? o : mine);
+    }
+    return mine;
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_set_positions: cells[wave][n*n] -> the slots' bit-planes and game state, as k_set_position and k_refill do for one
+// slot.  Slots beyond the lane's share go idle.
 // ------------------------------------------------------------------------------------------------
 template <int N>
 __global__ __launch_bounds__(256) void k_set_positions(BatchLanes bl, const unsigned char *__restrict__ cells,
@@ -52,17 +73,8 @@ __global__ __launch_bounds__(256) void k_set_positions(BatchLanes bl, const unsi
         return;
     }
     const int i = ln.first + b;
-    const unsigned char *cp = cells + (size_t)i * G::nn;
-    u64 mine = 0ull;                   // lanes 0..3 end up with X word `lane`, lanes 4..7 with O word `lane - 4`
-    int ply = 0;
-#pragma unroll
-    for (int q = 0; q < G::CPL; q++) {
-        const int j = lane + 64 * q;
-        const int c = j < G::nn ? (int)cp[j] : 0;
-        const u64 x = __ballot(c == 1), o = __ballot(c == 2);
-        ply += __popcll(x | o);
-        mine = lane == q ? x : (lane == 4 + q ? o : mine);
-    }
+    int ply;
+    const u64 mine = cells_to_planes<N>(cells + (size_t)i * G::nn, lane, ply);
     if (lane < 8) ln.board[(size_t)b * 8 + lane] = mine;       // one 64-byte store; words beyond CPL are zero
     if (lane == 0) {
         ln.s_game[b] = i;
@@ -73,6 +85,25 @@ __global__ __launch_bounds__(256) void k_set_positions(BatchLanes bl, const unsi
         ln.leaf_kind[(size_t)b * bl.L] = LEAF_NONE;
         ln.carried[b] = -1;            // a fresh root, whatever az_set_subtree_reuse says
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_build_positions: cells[count][n*n] -> the table of start positions k_refill loads claimed games from
+// (az_set_start_positions).  One wavefront per position, the same planes and ply as k_set_positions.
+// ------------------------------------------------------------------------------------------------
+template <int N>
+__global__ __launch_bounds__(256) void k_build_positions(int count, const unsigned char *__restrict__ cells,
+                                                         const unsigned char *__restrict__ players, const short *__restrict__ lasts,
+                                                         StartPos *__restrict__ table)
+{
+    typedef TreeGeo<N> G;
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= count) return;
+    int ply;
+    const u64 mine = cells_to_planes<N>(cells + (size_t)i * G::nn, lane, ply);
+    if (lane < 8) table[i].w[lane] = mine;
+    if (lane == 0) { table[i].ply = ply; table[i].player = players[i]; table[i].last = lasts[i]; table[i].pad = 0; }
 }
 
 // ------------------------------------------------------------------------------------------------

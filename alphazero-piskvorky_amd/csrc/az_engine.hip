@@ -104,7 +104,13 @@ struct az_engine {
     // noise_off table that makes row g of the [wave][n*n] noise upload the tape of game g
     DevBuf bt_cells, bt_players, bt_lasts, bt_T, bt_zero_off, bt_visits, bt_W, bt_prior, bt_pi, bt_action;
     unsigned cache_mask = 0, cache_gen = 1;
-    std::vector<int> h_nply, h_result;
+    // az_set_start_positions: the device table k_refill loads claimed games from, and each position's stone count on the host
+    DevBuf start_tab;
+    int start_count = 0, start_first = 0, start_max_ply = 0;     // start_first = first mod 2 * start_count
+    std::vector<int> start_ply;
+    // last episode per game: plies searched, result, and the ply the game started at (the device keeps absolute plies:
+    // the records of game g sit at g * nn + h_start[g] + 0 .. h_nply[g])
+    std::vector<int> h_nply, h_result, h_start;
     PackedNet net[2];
     az_counters last{};
     // running episode (az_selfplay_begin .. az_selfplay_end)
@@ -114,6 +120,7 @@ struct az_engine {
         bool add_noise = true, arena = false, preset = false, profile = true;
         az_counters c{};
         int64_t reused_roots = 0;
+        std::vector<int> start;    // ply every game starts at (az_set_start_positions); empty = 0 for all
     } run;
     bool profile = false;          // HIP events around every trunk / FC launch (az_set_profiling); lanes then play one after another
     bool use_graph = true;         // AZ_GRAPH=0: launch kernel by kernel
@@ -689,6 +696,7 @@ static int create_engine(const az_config *cfg, az_engine **out, bool deep)
         d.v2w[0] = d.v2w[1] = d.v2b[0] = d.v2b[1] = nullptr;
         d.cache = nullptr; d.cache_mask = 0; d.cache_gen = e->cache_gen; d.ext_eval = 0; d.leaf_sym = nullptr; d.game_key0 = 0;
         d.key_stride = 1; d.T_game = nullptr;
+        d.start_pos = nullptr; d.start_count = 0; d.start_first = 0;
         if (!rc) rc = alloc_items(e, L, 1);
     }
     if (!rc) rc = dev_alloc(e, e->next_game, 16);
@@ -766,7 +774,7 @@ extern "C" void az_destroy(az_engine *e)
     }
     DevBuf *shared[] = {&e->T_table, &e->log_table, &e->sqrt_table, &e->noise_off, &e->next_game, &e->noise, &e->u,
                         &e->rec_planes, &e->rec_last, &e->rec_action, &e->rec_mover, &e->rec_pi, &e->rec_visits, &e->g_nply,
-                        &e->g_result, &e->src_index, &e->cache, &e->bt_cells, &e->bt_players, &e->bt_lasts, &e->bt_T,
+                        &e->g_result, &e->src_index, &e->cache, &e->start_tab, &e->bt_cells, &e->bt_players, &e->bt_lasts, &e->bt_T,
                         &e->bt_zero_off, &e->bt_visits, &e->bt_W, &e->bt_prior, &e->bt_pi, &e->bt_action};
     for (DevBuf *b : shared) dev_free(*b);
     for (int s = 0; s < 2; s++) {
@@ -981,6 +989,11 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
         d.total_games = sp.num_games; d.reuse = e->reuse; d.game_key0 = sp.game_key0;
         d.cache = (float *)e->cache.p; d.cache_mask = e->cache_mask; d.cache_gen = e->cache_gen;
         d.ext_eval = 0;
+        // start positions are for the games k_refill claims: a preset episode (az_search, az_search_batch) brings its own
+        const bool sps = !sp.preset && e->start_count > 0;
+        d.start_pos = sps ? (const StartPos *)e->start_tab.p : nullptr;
+        d.start_count = sps ? e->start_count : 0;
+        d.start_first = sps ? e->start_first : 0;
     });
     // persistent search kernel: plain net or synthetic evaluator, the reference's sequential search, trees that fit into LDS
     e->persist_gp = 0;
@@ -994,6 +1007,13 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
     r = az_engine::Run();
     r.num_games = sp.num_games; r.max_plies = sp.max_plies; r.add_noise = sp.add_noise; r.arena = sp.arena;
     r.preset = sp.preset; r.profile = sp.profile;
+    if (!sp.preset && e->start_count > 0) {
+        r.start.resize(sp.num_games);
+        for (int g = 0; g < sp.num_games; g++) {
+            const unsigned f = (unsigned)e->start_first + (unsigned)g;
+            r.start[g] = e->start_ply[(sp.arena ? f >> 1 : f) % (unsigned)e->start_count];
+        }
+    }
     HIPCHECK(e, hipMemsetAsync(e->next_game.p, 0, 16, e->stream));
     HIPCHECK(e, hipStreamSynchronize(e->stream));
     // the first refill hands every lane an equal share of the games (as many as its slots hold); afterwards a freed
@@ -1122,7 +1142,7 @@ static int lane_plies(az_engine *e, Lane &L, int max_steps)
         if (e->tapes) {       // the tapes of this ply must be on the device (streamed a wave ahead of the games)
             hipEvent_t ev = nullptr;
             const auto tw0 = std::chrono::steady_clock::now();
-            hipError_t trc = e->tapes->need(L.plies_played, &ev);
+            hipError_t trc = e->tapes->need(L.plies_played + e->tapes->ahead, &ev);
             if (trc != hipSuccess) return lane_fail(L, AZ_ERR_HIP, "tape producer: %s", hipGetErrorString(trc));
             // a wave whose upload is still in flight would stall the play stream by the same amount: wait for it here so
             // that the stall is counted (az_counters.tape_wait_seconds); normally the wave landed a ply or two ago
@@ -1282,6 +1302,12 @@ static int episode_end(az_engine *e, az_counters *out)
                 if (ss[b] == SLOT_ACTIVE && sg[b] >= 0 && sg[b] < r.num_games) e->h_nply[sg[b]] = sp[b];
         }
     }
+    // the device counts plies from the empty board; from here on h_nply is the plies searched (a game not begun stays 0)
+    e->h_start.assign(r.num_games, 0);
+    for (int g = 0; g < (int)r.start.size(); g++) {
+        e->h_start[g] = r.start[g];
+        e->h_nply[g] = std::max(0, e->h_nply[g] - r.start[g]);
+    }
     int64_t plies = 0;
     for (int g = 0; g < r.num_games; g++) plies += e->h_nply[g];
     r.c.plies = r.c.records = plies;
@@ -1324,6 +1350,8 @@ extern "C" int az_selfplay_begin(az_engine *e, const az_selfplay_args *a)
     if (e->run.open) return fail(e, AZ_ERR_STATE, "az_selfplay_begin: an episode is already open (az_selfplay_end first)");
     DEVICE_GUARD(e);
     const int nn = e->nn, G = a->num_games;
+    if (e->start_count > 0 && a->max_plies > 0 && e->start_max_ply >= a->max_plies)
+        return fail(e, AZ_ERR_INVALID, "az_selfplay: a start position already holds %d stones, max_plies is %d", e->start_max_ply, a->max_plies);
     int rc = ensure_episode_buffers(e, G, true);
     if (rc) return rc;
     if ((rc = upload_T(e, a->temperature_table, false))) return rc;
@@ -1340,6 +1368,7 @@ extern "C" int az_selfplay_begin(az_engine *e, const az_selfplay_args *a)
         HIPCHECK(e, hipStreamSynchronize(e->stream));
     } else if (e->stream_tapes) {
         e->tapes = new TapeProducer();
+        e->tapes->ahead = e->start_count > 0 ? e->start_max_ply : 0;      // a game's ply runs this far ahead of the episode's
         hipError_t trc = e->tapes->start(e->cfg.device, a->seed0, G, nn, plies, e->cfg.dirichlet_alpha, e->tape_len,
                                          (double *)e->noise.p, (double *)e->u.p, e->tape_threads);
         if (trc != hipSuccess) { stop_tapes(e); return fail(e, AZ_ERR_HIP, "tape producer: %s", hipGetErrorString(trc)); }
@@ -1428,7 +1457,7 @@ extern "C" int az_selfplay_records(az_engine *e, uint8_t *boards, uint8_t *mover
     size_t r = 0;
     for (int g = 0; g < G; g++) {
         for (int m = 0; m < e->h_nply[g]; m++, r++) {
-            size_t si = (size_t)g * nn + m;
+            size_t si = (size_t)g * nn + e->h_start[g] + m;
             int mover = mv[si];
             if (boards)
                 for (int j = 0; j < nn; j++) {
@@ -1464,7 +1493,7 @@ extern "C" int az_selfplay_pack(az_engine *e, void *packed_dev)
     const int nn = e->nn;
     std::vector<int> src;
     for (int g = 0; g < e->episode_games; g++)
-        for (int m = 0; m < e->h_nply[g]; m++) src.push_back(g * nn + m);
+        for (int m = 0; m < e->h_nply[g]; m++) src.push_back(g * nn + e->h_start[g] + m);
     if (src.empty()) return AZ_OK;
     int rc = upload(e, e->src_index, src.data(), src.size() * 4);
     if (rc) return rc;
@@ -1771,6 +1800,85 @@ extern "C" int az_search_batch(az_engine *e, int slot, int count, const uint8_t 
     return AZ_OK;
 }
 
+// ---- start positions: later self-play and arena games continue these instead of beginning on the empty board ----
+// a line of k or more stones of either colour anywhere on the board: the kernels test only lines through the last stone
+// (wins_through) and the reference's winner is sticky (games.py:140-141), so such a position would be played on
+static bool has_line(const uint8_t *bd, int n, int k)
+{
+    static const int dr[4] = {0, 1, 1, 1}, dc[4] = {1, 0, 1, -1};
+    for (int r = 0; r < n; r++)
+        for (int c = 0; c < n; c++) {
+            const int v = bd[r * n + c];
+            if (!v) continue;
+            for (int t = 0; t < 4; t++) {
+                int len = 1;
+                for (int rr = r + dr[t], cc = c + dc[t]; rr >= 0 && rr < n && cc >= 0 && cc < n && bd[rr * n + cc] == v; rr += dr[t], cc += dc[t]) len++;
+                if (len >= k) return true;
+            }
+        }
+    return false;
+}
+
+extern "C" int az_set_start_positions(az_engine *e, int count, const uint8_t *boards, const uint8_t *players,
+                                      const int16_t *lasts, int64_t first)
+{
+    if (!e || count < 0 || count > (1 << 24) || first < 0) return fail(e, AZ_ERR_INVALID, "az_set_start_positions: bad argument");
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_start_positions: an episode is open");
+    if (count == 0) {
+        e->start_count = e->start_first = e->start_max_ply = 0;
+        e->start_ply.clear();
+        return AZ_OK;
+    }
+    if (!boards || !players || !lasts) return fail(e, AZ_ERR_INVALID, "az_set_start_positions: null argument");
+    const int nn = e->nn;
+    // every position is checked on the host before anything is uploaded, by az_search_batch's rules and the line test
+    std::vector<int> ply(count);
+    int max_ply = 0;
+    for (int i = 0; i < count; i++) {
+        const uint8_t *bd = boards + (size_t)i * nn;
+        if (players[i] != 1 && players[i] != 2) return fail(e, AZ_ERR_INVALID, "az_set_start_positions: position %d: player %d", i, players[i]);
+        int st = 0;
+        for (int j = 0; j < nn; j++) {
+            if (bd[j] > 2) return fail(e, AZ_ERR_INVALID, "az_set_start_positions: position %d: cell value %d", i, bd[j]);
+            st += bd[j] != 0;
+        }
+        if (st >= nn) return fail(e, AZ_ERR_INVALID, "az_set_start_positions: position %d: no legal action", i);
+        if (lasts[i] >= nn || lasts[i] < -1 || (lasts[i] >= 0 && bd[lasts[i]] == 0)) return fail(e, AZ_ERR_INVALID, "az_set_start_positions: position %d: bad last action", i);
+        if (has_line(bd, e->n, e->cfg.win_length)) return fail(e, AZ_ERR_INVALID, "az_set_start_positions: position %d: already won (a line of %d)", i, e->cfg.win_length);
+        ply[i] = st;
+        max_ply = std::max(max_ply, st);
+    }
+    DEVICE_GUARD(e);
+    // a new table beside the one in force: any failure below keeps the previous setting
+    DevBuf tab, cells, pl, la;
+    int rc = dev_alloc(e, tab, (size_t)count * sizeof(StartPos), false);
+    if (!rc) rc = dev_alloc(e, cells, (size_t)count * nn, false);
+    if (!rc) rc = dev_alloc(e, pl, (size_t)count, false);
+    if (!rc) rc = dev_alloc(e, la, (size_t)count * 2, false);
+    if (!rc) {
+        hipError_t hr = hipMemcpyAsync(cells.p, boards, (size_t)count * nn, hipMemcpyHostToDevice, e->stream);
+        if (hr == hipSuccess) hr = hipMemcpyAsync(pl.p, players, (size_t)count, hipMemcpyHostToDevice, e->stream);
+        if (hr == hipSuccess) hr = hipMemcpyAsync(la.p, lasts, (size_t)count * 2, hipMemcpyHostToDevice, e->stream);
+        if (hr == hipSuccess) {
+            e->ops->build_positions(e->stream, count, (const unsigned char *)cells.p, (const unsigned char *)pl.p, (const short *)la.p, (StartPos *)tab.p);
+            hr = hipStreamSynchronize(e->stream);
+        }
+        if (hr == hipSuccess) hr = hipGetLastError();
+        if (hr != hipSuccess) rc = fail(e, AZ_ERR_HIP, "az_set_start_positions: %s", hipGetErrorString(hr));
+    }
+    dev_free(cells); dev_free(pl); dev_free(la);
+    if (rc) { dev_free(tab); return rc; }
+    dev_free(e->start_tab);
+    e->start_tab = tab;
+    e->start_count = count;
+    e->start_first = (int)(first % (2 * (int64_t)count));
+    e->start_max_ply = max_ply;
+    e->start_ply.swap(ply);
+    return AZ_OK;
+}
+
+extern "C" int az_get_start_positions(const az_engine *e) { return e ? e->start_count : AZ_ERR_INVALID; }
+
 extern "C" int az_arena(az_engine *e, const az_arena_args *a, az_arena_result *out, int32_t *results, int16_t *actions,
                         int32_t *nply)
 {
@@ -1801,7 +1909,7 @@ extern "C" int az_arena(az_engine *e, const az_arena_args *a, az_arena_result *o
         std::vector<short> ac((size_t)G * nn);
         HIPCHECK(e, az_memcpy(e->stream, ac.data(), e->rec_action.p, ac.size() * 2, hipMemcpyDeviceToHost));
         for (int g = 0; g < G; g++)
-            for (int m = 0; m < nn; m++) actions[(size_t)g * nn + m] = m < e->h_nply[g] ? ac[(size_t)g * nn + m] : (int16_t)-1;
+            for (int m = 0; m < nn; m++) actions[(size_t)g * nn + m] = m < e->h_nply[g] ? ac[(size_t)g * nn + e->h_start[g] + m] : (int16_t)-1;
     }
     if (out) {
         out->wins = w; out->losses = l; out->draws = dr; out->total = w + l + dr;

@@ -77,10 +77,13 @@ static StreamPool g_streams;
 // plies the games never reach).  The draws are trajectory-independent, so "wave" w = plies [wP, wP+P) of
 // every unfinished game is produced by a few host threads into pinned staging, copied with two strided 2-D copies on a
 // copy stream, and the play stream waits on the wave's event before the first ply that needs it.  A game's ply never
-// exceeds the number of plies the episode has played, so waiting for wave floor(step / P) covers every slot, refilled
-// ones included.  Same numbers in the same device layout as the bulk path (AZ_TAPE_STREAM=0).
+// exceeds the number of plies the episode has played plus `ahead`, the largest ply a game starts at (0 unless
+// az_set_start_positions is in force), so waiting for wave floor((step + ahead) / P) covers every slot, refilled
+// ones included; the waves below a game's start ply are produced too, because a game's stream is sequential.
+// Same numbers in the same device layout as the bulk path (AZ_TAPE_STREAM=0).
 struct TapeProducer {
     static constexpr int P = 2;          // plies per wave
+    int ahead = 0;                       // largest start ply of a game; set before start()
     int device = 0, G = 0, nn = 0, plies = 0, waves = 0, threads = 1;
     double alpha = 0.3;
     int64_t tape_len = 0;
@@ -119,7 +122,7 @@ struct TapeProducer {
         for (int w = 0; w < waves; w++)
             if ((rc = hipEventCreateWithFlags(&wave_event[w], hipEventDisableTiming))) return rc;
         streams = azrng::streams_new(seed0, G);
-        want = 2;                        // waves 0 and 1 are produced straight away
+        want = ahead / P + 2;            // the waves of the first ply and the one behind it are produced straight away
         th = std::thread([this]() { run(); });
         return hipSuccess;
     }
@@ -170,12 +173,13 @@ struct TapeProducer {
         }
     }
 
-    // consumer side: the episode is about to play its ply number `step`; returns the event to wait on (or null)
+    // consumer side: the games are about to play plies up to `step` (the episode's ply number plus `ahead`); returns the
+    // event to wait on (or null)
     hipError_t need(int step, hipEvent_t *ev)
     {
         *ev = nullptr;
         const int w = step / P;
-        if (w >= waves) return hipSuccess;
+        if (w >= waves) return hipSuccess;       // ahead < plies, so an earlier call has waited for the last wave
         std::unique_lock<std::mutex> lk(mu);
         if (want < w + 2) { want = w + 2; cv.notify_all(); }
         cv.wait(lk, [&] { return waves_done > w || error != hipSuccess; });

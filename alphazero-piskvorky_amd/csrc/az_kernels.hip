@@ -208,11 +208,17 @@ void gather_roots(hipStream_t stream, const BatchLanes &bl, const DevState &d, c
     hipLaunchKernelGGL(k_gather_roots<N>, g, b, 0, stream, bl, d.R, d.S, cells, (const float *)d.rec_pi,
                        (const short *)d.rec_action, visits, W, prior, pi, action);
 }
+
+void build_positions(hipStream_t stream, int count, const unsigned char *cells, const unsigned char *players, const short *lasts, StartPos *table)
+{
+    dim3 g((count + 3) / 4), b(256);
+    hipLaunchKernelGGL(k_build_positions<N>, g, b, 0, stream, count, cells, players, lasts, table);
+}
 }   // namespace
 
 const SizeOps *AZ_CAT(az_size_ops_, AZ_N)()
 {
     static const SizeOps ops = {trunk, trunk_split, split_scratch_floats, fc, step, step_vl, root_cache, search_prepare, search, move, eval_tail_l,
-                                set_positions, gather_roots};
+                                set_positions, gather_roots, build_positions};
     return &ops;
 }

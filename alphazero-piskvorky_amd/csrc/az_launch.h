@@ -42,6 +42,8 @@ struct SizeOps {
     // the ply every slot's root row and record into compact [wave][n*n] staging (null outputs are skipped)
     void (*set_positions)(hipStream_t, const BatchLanes &, const unsigned char *cells, const unsigned char *players, const short *lasts);
     void (*gather_roots)(hipStream_t, const BatchLanes &, const DevState &, const unsigned char *cells, int *visits, double *W, float *prior, float *pi, int *action);
+    // az_set_start_positions: `count` positions given as cells -> the table k_refill starts games from
+    void (*build_positions)(hipStream_t, int count, const unsigned char *cells, const unsigned char *players, const short *lasts, StartPos *table);
 };
 
 const SizeOps *az_size_ops(int n);     // nullptr for unsupported sizes

@@ -33,6 +33,12 @@ struct __attribute__((aligned(16))) Edge {
     unsigned short child;  // row of the expanded child node, 0 = not expanded (row 0 is the root)
 };
 
+// One start position of az_set_start_positions: the board a claimed game begins from instead of the empty one.
+struct __attribute__((aligned(16))) StartPos {
+    u64 w[8];              // absolute bit-planes like DevState.board: words 0-3 X, 4-7 O
+    int ply, player, last, pad;   // stones on the board, side to move (1 / 2), last action (-1 none)
+};
+
 struct DevState {
     int B, R, S, k, max_plies, add_noise, arena, total_games;
     double c_puct, w_noise;
@@ -91,6 +97,11 @@ struct DevState {
                            // key 0 like az_search's, so that a result never depends on the position's index in the batch
     const double *T_game;  // [G] temperature per game, preferred over T_table by k_move when set (az_search_batch: positions with
                            // the same stone count may ask for different temperatures); nullptr everywhere else
+    // --- opt-in start positions (az_set_start_positions), read by k_refill only; nullptr / 0 on every path but self-play and arena ---
+    const StartPos *start_pos;   // [start_count]; nullptr = every game starts from the empty board
+    int start_count;
+    int start_first;       // `first` mod 2 * start_count: game g starts from position (start_first + g) % start_count, in the
+                           // arena from ((start_first + g) >> 1) % start_count with the colours exchanged for odd g
 };
 __device__ __forceinline__ int game_key(const DevState &d, int game) { return (int)(d.game_key0 + d.key_stride * (unsigned)game); }
 
@@ -1169,12 +1180,24 @@ __global__ __launch_bounds__(1024) void k_refill(DevState d, int claim_cap, int 
             const int idx = off + pre;
             if (idx < take_s) {
                 u64 *bd = d.board + (size_t)b * 8;
-                for (int q = 0; q < 8; q++) bd[q] = 0ull;
                 const int gid = base_s + idx;
+                const int odd = (d.arena && (gid & 1)) ? 1 : 0;   // evaluator.py:64-69: the other side moves first
                 d.s_game[b] = gid;
-                d.s_ply[b] = 0;
-                d.s_player[b] = (d.arena && (gid & 1)) ? 2 : 1;   // evaluator.py:64-69
-                d.s_last[b] = -1;
+                if (d.start_pos) {
+                    // the game continues a given position; odd arena games see it with the colours exchanged (the plane
+                    // halves swapped, the other side to move), which for the empty board is the rule above
+                    const unsigned f = (unsigned)d.start_first + (unsigned)gid;
+                    const StartPos &sp = d.start_pos[(d.arena ? f >> 1 : f) % (unsigned)d.start_count];
+                    for (int q = 0; q < 8; q++) bd[q] = sp.w[odd ? q ^ 4 : q];
+                    d.s_ply[b] = sp.ply;
+                    d.s_player[b] = odd ? 3 - sp.player : sp.player;
+                    d.s_last[b] = sp.last;
+                } else {
+                    for (int q = 0; q < 8; q++) bd[q] = 0ull;
+                    d.s_ply[b] = 0;
+                    d.s_player[b] = odd ? 2 : 1;
+                    d.s_last[b] = -1;
+                }
                 d.s_status[b] = SLOT_ACTIVE;
                 d.leaf_kind[(size_t)b * d.L] = LEAF_NONE;
                 d.carried[b] = -1;

@@ -17,13 +17,17 @@ def temperature_schedule(move: int) -> float:
 
 
 class ModelEvaluator:
-    def __init__(self, game_class=None, print_games=False, device=None, seed=None, virtual_loss=1, eval_cache=0):
+    def __init__(self, game_class=None, print_games=False, device=None, seed=None, virtual_loss=1, eval_cache=0,
+                 start_positions=None):
         self.game_class = game_class
         self.print_games = print_games
         self.device = device if device is not None else torch.device("cuda")
         self.seed = seed
         self.virtual_loss = virtual_loss      # opt-in search upgrades (mcts.py:17-22 TODO), see include/az_engine.h
         self.eval_cache = eval_cache
+        # opt-in: (boards, players, lasts); games 2i and 2i+1 both start from position i mod count, the second with the
+        # colours exchanged, so every position is played once from either side
+        self.start_positions = start_positions
         self._engine = None
 
     def evaluate(self, candidate_controller, baseline_controller, num_games=20, debug=False):
@@ -54,6 +58,10 @@ class ModelEvaluator:
         seed0 = self.seed if self.seed is not None else int(np.random.randint(0, 2 ** 31 - 1))
         if self.seed is None:
             seed0 = parallel.broadcast_seed(seed0, dev)
+        if self.start_positions is not None:
+            eng.set_start_positions(*self.start_positions, first=lo)      # lo is even (parallel.arena_block): no pair is torn apart
+        elif eng.start_positions():
+            eng.clear_start_positions()
         r = eng.arena(mine, seed0=seed0 + lo, temperature_table=T) if mine > 0 else {"wins": 0, "losses": 0, "draws": 0, "total": 0, "win_rate": 0.0}
         if world > 1:
             w, l, d = parallel.all_reduce_tally(r["wins"], r["losses"], r["draws"], dev, engine=eng)

@@ -9,6 +9,34 @@ from . import constants as _c
 _DIRS = ((0, 1), (1, 0), (1, 1), (1, -1))
 
 
+def position_from_actions(actions, board_size, first_player=1):
+    """The position an action list leads to, for callers that hold games rather than boards (Engine.set_start_positions,
+    Engine.search_batch): actions are cell indices r * n + c or (r, c) pairs, played alternately from the empty board with
+    `first_player` (1 X / 2 O) to move.  -> (cells uint8[n*n] 0 / 1 X / 2 O, side to move 1 / 2, last action or -1).
+    Only occupancy is checked here; whether the position is already won is the engine's check."""
+    n = int(board_size)
+    if first_player not in (1, 2):
+        raise ValueError("first_player must be 1 (X) or 2 (O)")
+    cells = np.zeros(n * n, dtype=np.uint8)
+    player, last = int(first_player), -1
+    for a in actions:
+        idx = int(a[0]) * n + int(a[1]) if isinstance(a, (tuple, list)) else int(a)
+        if not 0 <= idx < n * n or cells[idx] != 0:
+            raise ValueError("Invalid move")                     # games.py:76-77
+        cells[idx] = player
+        player, last = 3 - player, idx
+    return cells, player, last
+
+
+def positions_from_actions(action_lists, board_size, first_player=1):
+    """position_from_actions for many lists -> (boards uint8[count, n*n], players uint8[count], lasts int16[count]), the
+    arrays Engine.set_start_positions takes."""
+    ps = [position_from_actions(a, board_size, first_player) for a in action_lists]
+    n2 = int(board_size) ** 2
+    return (np.array([p[0] for p in ps], np.uint8).reshape(len(ps), n2), np.array([p[1] for p in ps], np.uint8),
+            np.array([p[2] for p in ps], np.int16))
+
+
 class Gomoku:
     def __init__(self, board_size=None, win_length=None):
         board_size = _c.BOARD_SIZE if board_size is None else board_size

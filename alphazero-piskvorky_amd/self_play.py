@@ -22,7 +22,8 @@ class SelfPlayManager:
                  temperature_schedule: Callable[[int], float] = default_temperature_schedule,
                  concurrent_games: int = None, augmentation: int = AZ_AUG_REFERENCE4, seed: int = None,
                  engines_per_gpu: int = None, subtree_reuse: bool = False, gather_to: int = None,
-                 eval_cache: int = 0, virtual_loss: int = 1, trunk: str = "f32", leaf_symmetry: bool = False):
+                 eval_cache: int = 0, virtual_loss: int = 1, trunk: str = "f32", leaf_symmetry: bool = False,
+                 start_positions=None):
         self.controller = controller
         self.device = device
         self.mcts_params = mcts_params or {"num_simulations": 100}
@@ -36,6 +37,7 @@ class SelfPlayManager:
         self.virtual_loss = virtual_loss      # opt-in: leaves per search and evaluation batch (mcts.py:17-22 TODO); 1 = sequential like the reference
         self.trunk = trunk                    # opt-in: "bf16x3" / "f16x2" = fp32-emulating conv trunks on the 16-bit matrix cores (tolerance, not bit-exact)
         self.leaf_symmetry = leaf_symmetry    # opt-in: every net evaluation sees a pseudo-random dihedral symmetry of the position (README.md:61,82)
+        self.start_positions = start_positions    # opt-in: (boards, players, lasts); game g continues position g mod count instead of starting on the empty board
         self.gather_to = gather_to            # multi-rank: None = every rank receives all records (all-gather); r = only rank r does
         self.last_counters = None
         self._engine = None
@@ -98,6 +100,10 @@ class SelfPlayManager:
         if eng.trunk_mode() != self.trunk:
             eng.set_trunk_mode(self.trunk)
         T = np.array([float(self.temperature_schedule(m)) for m in range(n * n + 1)], dtype=np.float64)
+        if self.start_positions is not None:
+            eng.set_start_positions(*self.start_positions, first=lo)      # by global game id, like the seed
+        elif eng.start_positions():
+            eng.clear_start_positions()
         if mine > 0:
             self.last_counters = eng.selfplay(mine, seed0=seed0 + lo, temperature_table=T)
         else:

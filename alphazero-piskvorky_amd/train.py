@@ -10,6 +10,7 @@ import os
 import tempfile
 import time
 
+import numpy as np
 import torch
 
 from . import constants as C
@@ -26,11 +27,13 @@ PROMOTION_THRESHOLD = 0.55          # promoter.py:19, strict ">" with draws coun
 
 
 def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=None, log=print, device_replay=False,
-        subtree_reuse=False, trunk="f32", eval_sims=None):
+        subtree_reuse=False, trunk="f32", eval_sims=None, start_positions=None):
     """eval_sims: simulations per move in the arena (evaluator.py:53-62 takes NUM_EVAL_SIMULATIONS = 200 whatever the
     self-play count is; main() passes that constant); None = as many as self-play, which keeps small test runs short.
     device_replay=True keeps the examples on the GPU from the episode-end gather to the optimizer step (packed records
-    in a device ring, batches unpacked + augmented by az_examples_gather) instead of materialising Python tuples."""
+    in a device ring, batches unpacked + augmented by az_examples_gather) instead of materialising Python tuples.
+    start_positions: (boards, players, lasts) the self-play games continue instead of starting on the empty board
+    (Engine.set_start_positions); the arena keeps the empty board."""
     torch.manual_seed(seed)
     n = C.BOARD_SIZE
     rank, world = parallel.rank_world()
@@ -40,7 +43,8 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
     # multi-rank: every rank plays its shard of the games; the records go to rank 0 only (the reference has one trainer,
     # train.py:95-104), rank 0 takes the optimizer steps and its weights are broadcast; only rank 0 writes model_dir
     manager = SelfPlayManager(candidate, device, mcts_params={"num_simulations": sims, "c_puct": C.SELF_PLAY_EXPLORATION_CONSTANT},
-                              seed=seed, subtree_reuse=subtree_reuse, gather_to=0 if world > 1 else None, trunk=trunk)
+                              seed=seed, subtree_reuse=subtree_reuse, gather_to=0 if world > 1 else None, trunk=trunk,
+                              start_positions=start_positions)
     evaluator = ModelEvaluator(game_class=Gomoku, print_games=False, device=device, seed=seed)
     promoter = ModelPromoter(model_dir, evaluator, lambda: GomokuNet(board_size=n), device, threshold=PROMOTION_THRESHOLD)
     buffer = ReplayBuffer(capacity=C.BUFFER_CAPACITY)
@@ -99,7 +103,14 @@ def main():
     ap.add_argument("--trunk", default="f32", choices=["f32", "bf16x3", "f16x2"], help="self-play conv trunk: f32 (bit-exact default) or an fp32-emulating trunk on the 16-bit matrix cores (opt-in: bf16x3, or the faster f16x2 with float16's range)")
     ap.add_argument("--subtree-reuse", action="store_true", help="self-play keeps the chosen child's subtree between plies (opt-in search upgrade)")
     ap.add_argument("--device-replay", action="store_true", help="keep examples on the GPU (packed ring + on-device batch unpacking)")
+    ap.add_argument("--start-positions", default=None, metavar="FILE.npz",
+                    help="self-play games continue these positions instead of starting on the empty board: arrays boards "
+                         "[count, n*n] (0 / 1 X / 2 O), players [count] (1 / 2), lasts [count] (-1 none); game g takes position g mod count")
     a = ap.parse_args()
+    start_positions = None
+    if a.start_positions:
+        with np.load(a.start_positions) as z:
+            start_positions = (z["boards"], z["players"], z["lasts"])
     # one process per GPU under torch.distributed.run: games and arena games are sharded over the ranks (self_play.py,
     # evaluator.py), the examples are gathered to rank 0, which trains, writes the checkpoints and broadcasts the weights
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -110,7 +121,7 @@ def main():
         td.init_process_group("nccl", device_id=torch.device("cuda", local))
         a.device = f"cuda:{local}"
     run(a.episodes, a.games, a.sims, a.eval_games, a.device, model_dir=a.model_dir, device_replay=a.device_replay,
-        subtree_reuse=a.subtree_reuse, trunk=a.trunk, eval_sims=C.NUM_EVAL_SIMULATIONS)
+        subtree_reuse=a.subtree_reuse, trunk=a.trunk, eval_sims=C.NUM_EVAL_SIMULATIONS, start_positions=start_positions)
     if world > 1:
         td.barrier()
         td.destroy_process_group()

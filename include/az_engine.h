@@ -377,6 +377,34 @@ int az_set_eval_cache(az_engine *e, int64_t entries);
  * evaluation s + 1); az_search_callback evaluates positions as they are.  Not allowed while an episode is open. */
 int az_set_leaf_symmetry(az_engine *e, int on);
 
+/* Opt-in: start positions.  The reference always starts `Gomoku()` (self_play.py:50, evaluator.py:64); with count > 0 later
+ * az_selfplay*, az_arena start their games from these positions instead of the empty board; count = 0 (pointers may be
+ * NULL): back to the empty board.  Same position format as az_search_batch.  The definition: a game started from the
+ * position that game g reached at ply m, with game g's seed, continues game g bit for bit.
+ *   Self-play: game g starts from position (first + g) mod count.  Its ply is the number of stones on the board, side to
+ *     move and last move are as given.  Everything indexed by ply keeps the ABSOLUTE ply -- the temperature table, the
+ *     noise tape offset, u[g][ply], the explicit noise_tape / u_tape arguments, the leaf-symmetry hash, and max_plies (a
+ *     game is cut once max_plies stones are on the board): a game whose first moves were forced.
+ *   Arena: game g starts from position ((first + g) >> 1) mod count, for odd g with the colours exchanged (stones 1 <-> 2,
+ *     side to move 3 - player): games 2i and 2i+1 are the same position with the nets on opposite sides (first even).
+ *     The empty board with X to move gives the default arena.  Temperature temperature_table[(ply + 1) >> 1] and u by
+ *     absolute ply.
+ *   Records carry only searched plies: az_selfplay_games' nply[g] counts the plies searched = the records of game g;
+ *     az_selfplay_records, az_selfplay_pack, az_dist_counts and az_dist_gather_records likewise, the first record of a
+ *     game showing the start position with its `last`; az_arena's actions[g][0 .. nply[g]) are the moves played after the
+ *     start position.  Counters: plies = records = root_evals (less retained roots) count searched plies.
+ *   Checked on the host before anything is uploaded, by az_search_batch's rules (cell values, a legal action exists, last
+ *     in range and on an occupied cell or -1, player 1 or 2) and one more: no line of win_length or more stones of either
+ *     colour anywhere on the board (an already won position would be played on).  AZ_ERR_INVALID with the index of the first
+ *     offending position in az_last_error; the previous setting is kept.  first >= 0.  AZ_ERR_STATE while an episode is
+ *     open.  az_selfplay_begin / az_selfplay return AZ_ERR_INVALID when max_plies > 0 and some position already holds
+ *     max_plies or more stones.
+ * az_search, az_search_batch, az_search_callback, az_net_eval and az_rules_replay ignore the setting.  Combines with every
+ * search option; with subtree reuse the first ply of a game has a fresh root. */
+int az_set_start_positions(az_engine *e, int count, const uint8_t *boards /* [count][n*n] 0 / 1 X / 2 O */,
+                           const uint8_t *players, const int16_t *lasts, int64_t first);
+int az_get_start_positions(const az_engine *e);   /* count in force, 0 = none */
+
 /* Opt-in: fp32-emulating conv trunks.  AZ_TRUNK_F32 (default) computes the net's forward (net.py:55-72) on the float32
  * matrix instruction in the build's canonical fp order: bit-identical to the oracle.  The other two run every conv but the
  * first (99 % of the net's arithmetic) and the 1x1 head convs on the 16 x faster 16-bit matrix instructions with split
