@@ -33,6 +33,8 @@ EXPORTS = [
     "az_examples_gather", "az_arena", "az_rules_replay", "az_rng_selfplay_tape", "az_rng_uniforms", "az_set_profiling", "az_set_subtree_reuse", "az_get_counters", "az_get_lanes", "az_get_persistent", "az_set_virtual_loss", "az_set_eval_cache",
     "az_set_trunk_mode", "az_get_trunk_mode", "az_set_leaf_symmetry", "az_emul_split",
     "az_set_start_positions", "az_get_start_positions",
+    "az_set_resign", "az_get_resign", "az_selfplay_values", "az_selfplay_pack_values", "az_selfplay_resign_info",
+    "az_resign_mix", "az_resign_exempt",
     "az_dist_unique_id", "az_dist_init", "az_dist_rank", "az_dist_world", "az_dist_counts", "az_dist_gather_records",
     "az_dist_allreduce_sum", "az_dist_broadcast",
 ]
@@ -129,6 +131,15 @@ def lib():
         if hasattr(L, "az_set_start_positions"):
             L.az_set_start_positions.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
             L.az_get_start_positions.argtypes = [C.c_void_p]
+        if hasattr(L, "az_set_resign"):
+            L.az_set_resign.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int]
+            L.az_get_resign.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+            L.az_selfplay_values.argtypes = [C.c_void_p, C.c_void_p]
+            L.az_selfplay_pack_values.argtypes = [C.c_void_p, C.c_void_p]
+            L.az_selfplay_resign_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+            L.az_resign_mix.argtypes = [C.c_uint32]
+            L.az_resign_mix.restype = C.c_uint32
+            L.az_resign_exempt.argtypes = [C.c_uint32, C.c_int]
         _LIB = L
     return _LIB
 
@@ -168,6 +179,24 @@ def rng_uniforms(seed, count):
     if rc:
         raise AzError(f"az_rng_uniforms failed ({rc})")
     return u
+
+
+def resign_mix(key):
+    """The 32-bit mix that names the exempt games (az_resign_mix; needs no GPU)."""
+    return int(lib().az_resign_mix(int(key) & 0xFFFFFFFF))
+
+
+def resign_exempt(key, playout_permille):
+    """True when the game named key = low 32 bits of seed0 + g plays on whatever its search values (az_resign_exempt)."""
+    return bool(lib().az_resign_exempt(int(key) & 0xFFFFFFFF, int(playout_permille)))
+
+
+def resign_permille(playout):
+    """The share of games that play out, as az_set_resign takes it: round(1000 * playout), 0 <= playout <= 1."""
+    playout = float(playout)
+    if not 0.0 <= playout <= 1.0:
+        raise ValueError(f"playout must be a share in [0, 1], got {playout}")
+    return int(round(1000 * playout))
 
 
 class Engine:
@@ -440,6 +469,8 @@ class Engine:
         results = np.zeros(num_games, np.int32); actions = np.zeros((num_games, self.nn), np.int16)
         nply = np.zeros(num_games, np.int32)
         self._check(lib().az_arena(self.h, C.byref(args), C.byref(res), _p(results), _p(actions), _p(nply)), "az_arena")
+        self.last_games = int(num_games)      # the arena is the engine's last episode now: games(), records(), values(), resign_info()
+        self.last_records = int(nply.sum())
         return dict(wins=res.wins, losses=res.losses, draws=res.draws, total=res.total, win_rate=res.win_rate,
                     results=results, actions=actions, nply=nply)
 
@@ -487,6 +518,43 @@ class Engine:
     def start_positions(self):
         """Number of start positions in force, 0 = games start from the empty board."""
         return int(lib().az_get_start_positions(self.h))
+
+    # ---- search value per record, resignation ----
+    def set_resign(self, threshold, min_ply=0, playout=0.0):
+        """Opt-in: a selfplay* / arena game ends as a loss of the mover once a ply at or after min_ply has a search value
+        v < -threshold (v = W / N of the root's most visited cell); a pseudo-random share `playout` of the self-play games,
+        named by their seeds, is exempt and plays on.  threshold = 0 switches it off.  See include/az_engine.h."""
+        threshold, min_ply = float(threshold), int(min_ply)
+        if not 0.0 <= threshold <= 1.0:
+            raise ValueError(f"threshold must be 0 (off) or in (0, 1], got {threshold}")
+        if min_ply < 0:
+            raise ValueError(f"min_ply must be >= 0, got {min_ply}")
+        self._check(lib().az_set_resign(self.h, threshold, min_ply, resign_permille(playout)), "az_set_resign")
+
+    def resign(self):
+        """The setting in force: dict(threshold, min_ply, playout); threshold 0.0 = off."""
+        t, m, p = C.c_double(0.0), C.c_int(0), C.c_int(0)
+        self._check(lib().az_get_resign(self.h, C.byref(t), C.byref(m), C.byref(p)), "az_get_resign")
+        return dict(threshold=float(t.value), min_ply=int(m.value), playout=int(p.value) / 1000.0)
+
+    def values(self):
+        """float32 search value of every record of the last episode, in the order of records() (az_selfplay_values)."""
+        v = np.zeros(self.last_records, np.float32)
+        self._check(lib().az_selfplay_values(self.h, _p(v)), "az_selfplay_values")
+        return v
+
+    def pack_values_into(self, dev_ptr):
+        """The same values into a device buffer of last_records floats, in pack_into's order (az_selfplay_pack_values)."""
+        self._torch_sync()
+        self._check(lib().az_selfplay_pack_values(self.h, C.c_void_p(dev_ptr)), "az_selfplay_pack_values")
+
+    def resign_info(self):
+        """(cross_ply int32[games], exempt bool[games]) of the last episode: the first ply whose value crossed the threshold
+        (absolute ply, -1 = none), exempt games included (az_selfplay_resign_info)."""
+        G = getattr(self, "last_games", 0)
+        cross = np.full(G, -1, np.int32); ex = np.zeros(G, np.uint8)
+        self._check(lib().az_selfplay_resign_info(self.h, _p(cross), _p(ex)), "az_selfplay_resign_info")
+        return cross, ex.astype(bool)
 
     def set_trunk_mode(self, mode):
         """Opt-in: "bf16x3" / "f16x2" = fp32-emulating conv trunks on the 16-bit matrix cores (tolerance instead of

@@ -144,6 +144,15 @@ __device__ __forceinline__ unsigned wave_xor_u(unsigned v)
     for (int m = 32; m >= 1; m >>= 1) v = v ^ (unsigned)__shfl_xor((int)v, m, 64);
     return v;
 }
+__device__ __forceinline__ unsigned wave_max_u(unsigned v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const unsigned o = (unsigned)__shfl_xor((int)v, m, 64);
+        v = o > v ? o : v;
+    }
+    return v;
+}
 __device__ __forceinline__ double max_d(double a, double b) { return b > a ? b : a; }
 __device__ __forceinline__ int min_i(int a, int b) { return b < a ? b : a; }
 // argmax with first-index tie-break: max score, then min index (mcts.py:71 "first maximal child"); idx < 0 = no candidate in

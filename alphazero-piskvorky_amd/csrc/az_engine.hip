@@ -87,6 +87,7 @@ struct az_engine {
     // shared by the lanes: tables, the game-id queue, the episode's tapes and records
     DevBuf T_table, log_table, sqrt_table, noise_off, next_game;
     DevBuf noise, u, rec_planes, rec_last, rec_action, rec_mover, rec_pi, rec_visits, g_nply, g_result, src_index;
+    DevBuf rec_value, g_cross;     // the search value of every record and the first crossing ply of every game (az_set_resign)
     int split_max = 64;            // use the tile-split (low-latency) trunk when at most this many slots of a lane are active (measured: 32 / 64 / 128 -> 102.0 / 102.3 / 101.0 games per second on the 1024-game episode; the 51-game arena 3.08 / 1.64 / 1.64 s)
     int episode_games = 0;
     int64_t tape_len = 0;          // doubles per game in the noise tape
@@ -111,6 +112,12 @@ struct az_engine {
     // last episode per game: plies searched, result, and the ply the game started at (the device keeps absolute plies:
     // the records of game g sit at g * nn + h_start[g] + 0 .. h_nply[g])
     std::vector<int> h_nply, h_result, h_start;
+    std::vector<int> h_cross;      // first crossing ply per game of the last episode (absolute ply), -1 = none
+    unsigned h_key0 = 0;           // ... and the episode's game_key0 and playout share, what az_selfplay_resign_info names the exempt games by
+    int h_permille = 0;
+    // az_set_resign: 0 = off
+    double resign_thr = 0.0;
+    int resign_min_ply = 0, resign_permille = 0;
     PackedNet net[2];
     az_counters last{};
     // running episode (az_selfplay_begin .. az_selfplay_end)
@@ -120,6 +127,7 @@ struct az_engine {
         bool add_noise = true, arena = false, preset = false, profile = true;
         az_counters c{};
         int64_t reused_roots = 0;
+        unsigned game_key0 = 0;
         std::vector<int> start;    // ply every game starts at (az_set_start_positions); empty = 0 for all
     } run;
     bool profile = false;          // HIP events around every trunk / FC launch (az_set_profiling); lanes then play one after another
@@ -428,6 +436,13 @@ __global__ void k_pack(DevState d, const int *src_index, int64_t records, int nn
     }
 }
 
+// the search value of every packed record, in k_pack's order
+__global__ void k_pack_values(const float *__restrict__ rec_value, const int *__restrict__ src_index, int64_t records, float *__restrict__ out)
+{
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < records) out[r] = rec_value[src_index[r]];
+}
+
 __global__ void k_examples(const unsigned char *packed, int64_t records, int n, int64_t rb, int aug, float *states,
                            float *pis, float *zs)
 {
@@ -697,6 +712,7 @@ static int create_engine(const az_config *cfg, az_engine **out, bool deep)
         d.cache = nullptr; d.cache_mask = 0; d.cache_gen = e->cache_gen; d.ext_eval = 0; d.leaf_sym = nullptr; d.game_key0 = 0;
         d.key_stride = 1; d.T_game = nullptr;
         d.start_pos = nullptr; d.start_count = 0; d.start_first = 0;
+        d.resign_thr = 0.0; d.resign_min_ply = 0; d.resign_permille = 0; d.rec_value = nullptr; d.g_cross = nullptr;
         if (!rc) rc = alloc_items(e, L, 1);
     }
     if (!rc) rc = dev_alloc(e, e->next_game, 16);
@@ -774,7 +790,7 @@ extern "C" void az_destroy(az_engine *e)
     }
     DevBuf *shared[] = {&e->T_table, &e->log_table, &e->sqrt_table, &e->noise_off, &e->next_game, &e->noise, &e->u,
                         &e->rec_planes, &e->rec_last, &e->rec_action, &e->rec_mover, &e->rec_pi, &e->rec_visits, &e->g_nply,
-                        &e->g_result, &e->src_index, &e->cache, &e->start_tab, &e->bt_cells, &e->bt_players, &e->bt_lasts, &e->bt_T,
+                        &e->g_result, &e->src_index, &e->rec_value, &e->g_cross, &e->cache, &e->start_tab, &e->bt_cells, &e->bt_players, &e->bt_lasts, &e->bt_T,
                         &e->bt_zero_off, &e->bt_visits, &e->bt_W, &e->bt_prior, &e->bt_pi, &e->bt_action};
     for (DevBuf *b : shared) dev_free(*b);
     for (int s = 0; s < 2; s++) {
@@ -930,6 +946,8 @@ static int ensure_episode_buffers(az_engine *e, int games, bool need_noise)
     ALLOC(rec_last, G * nn * 2, false); ALLOC(rec_action, G * nn * 2, false); ALLOC(rec_mover, G * nn, false);
     ALLOC(rec_pi, G * nn * nn * 4, false); ALLOC(rec_visits, G * nn * nn * 2, false);
     ALLOC(g_nply, G * 4, true); ALLOC(g_result, G * 4, true);
+    ALLOC(rec_value, G * nn * 4, false); ALLOC(g_cross, G * 4, false);
+    if (!rc) HIPCHECK(e, hipMemsetAsync(e->g_cross.p, 0xFF, G * 4, e->stream));      // -1: no game has crossed
     ALLOC(u, G * nn * sizeof(double), false);
     if (need_noise) ALLOC(noise, G * (size_t)e->tape_len * sizeof(double), false);
 #undef ALLOC
@@ -938,6 +956,7 @@ static int ensure_episode_buffers(az_engine *e, int games, bool need_noise)
         d.rec_planes = (u64 *)e->rec_planes.p; d.rec_last = (short *)e->rec_last.p; d.rec_action = (short *)e->rec_action.p;
         d.rec_mover = (unsigned char *)e->rec_mover.p; d.rec_pi = (float *)e->rec_pi.p;
         d.rec_visits = (unsigned short *)e->rec_visits.p; d.g_nply = (int *)e->g_nply.p; d.g_result = (int *)e->g_result.p;
+        d.rec_value = (float *)e->rec_value.p; d.g_cross = (int *)e->g_cross.p;
         d.u = (const double *)e->u.p; d.noise = (const double *)e->noise.p; d.noise_stride = e->tape_len;
     });
     return AZ_OK;
@@ -994,6 +1013,10 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
         d.start_pos = sps ? (const StartPos *)e->start_tab.p : nullptr;
         d.start_count = sps ? e->start_count : 0;
         d.start_first = sps ? e->start_first : 0;
+        // resignation is for self-play and the arena: a preset episode searches given positions, it plays no game
+        d.resign_thr = sp.preset ? 0.0 : e->resign_thr;
+        d.resign_min_ply = sp.preset ? 0 : e->resign_min_ply;
+        d.resign_permille = sp.preset || sp.arena ? 0 : e->resign_permille;
     });
     // persistent search kernel: plain net or synthetic evaluator, the reference's sequential search, trees that fit into LDS
     e->persist_gp = 0;
@@ -1007,6 +1030,7 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
     r = az_engine::Run();
     r.num_games = sp.num_games; r.max_plies = sp.max_plies; r.add_noise = sp.add_noise; r.arena = sp.arena;
     r.preset = sp.preset; r.profile = sp.profile;
+    r.game_key0 = sp.game_key0;
     if (!sp.preset && e->start_count > 0) {
         r.start.resize(sp.num_games);
         for (int g = 0; g < sp.num_games; g++) {
@@ -1288,6 +1312,10 @@ static int episode_end(az_engine *e, az_counters *out)
     e->h_result.assign(r.num_games, 0);
     HIPCHECK(e, az_memcpy(e->stream, e->h_nply.data(), e->g_nply.p, (size_t)r.num_games * 4, hipMemcpyDeviceToHost));
     HIPCHECK(e, az_memcpy(e->stream, e->h_result.data(), e->g_result.p, (size_t)r.num_games * 4, hipMemcpyDeviceToHost));
+    e->h_cross.assign(r.num_games, -1);
+    HIPCHECK(e, az_memcpy(e->stream, e->h_cross.data(), e->g_cross.p, (size_t)r.num_games * 4, hipMemcpyDeviceToHost));
+    e->h_key0 = r.game_key0;
+    e->h_permille = r.arena || r.preset ? 0 : e->resign_permille;
     if (r.preset) {
         e->h_nply.assign(r.num_games, 1);   // a preset search plays exactly one ply; the game itself is not finished by it
     } else {
@@ -1484,6 +1512,16 @@ extern "C" int az_selfplay_clear(az_engine *e)
     return AZ_OK;
 }
 
+// source index (game * nn + absolute ply) of every record of the last episode, game-major then ply, on the device
+static int upload_src_index(az_engine *e, int64_t *records)
+{
+    std::vector<int> src;
+    for (int g = 0; g < e->episode_games; g++)
+        for (int m = 0; m < e->h_nply[g]; m++) src.push_back(g * e->nn + e->h_start[g] + m);
+    *records = (int64_t)src.size();
+    return src.empty() ? AZ_OK : upload(e, e->src_index, src.data(), src.size() * 4);
+}
+
 extern "C" int64_t az_record_bytes(const az_engine *e) { return e ? record_bytes(e->nn) : 0; }
 
 extern "C" int az_selfplay_pack(az_engine *e, void *packed_dev)
@@ -1491,16 +1529,83 @@ extern "C" int az_selfplay_pack(az_engine *e, void *packed_dev)
     if (!e || !e->have_episode || !packed_dev) return fail(e, AZ_ERR_STATE, "az_selfplay_pack: no episode / null buffer");
     DEVICE_GUARD(e);
     const int nn = e->nn;
-    std::vector<int> src;
-    for (int g = 0; g < e->episode_games; g++)
-        for (int m = 0; m < e->h_nply[g]; m++) src.push_back(g * nn + e->h_start[g] + m);
-    if (src.empty()) return AZ_OK;
-    int rc = upload(e, e->src_index, src.data(), src.size() * 4);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_pack, dim3((unsigned)src.size()), dim3(64), 0, e->stream, e->lanes[0].d, (const int *)e->src_index.p,
-                       (int64_t)src.size(), nn, record_bytes(nn), (unsigned char *)packed_dev);
+    int64_t records = 0;
+    int rc = upload_src_index(e, &records);
+    if (rc || records == 0) return rc;
+    hipLaunchKernelGGL(k_pack, dim3((unsigned)records), dim3(64), 0, e->stream, e->lanes[0].d, (const int *)e->src_index.p,
+                       records, nn, record_bytes(nn), (unsigned char *)packed_dev);
     HIPCHECK(e, hipStreamSynchronize(e->stream));
     HIPCHECK(e, hipGetLastError());
+    return AZ_OK;
+}
+
+// ---- the search value per record, and resignation ----
+extern "C" int az_selfplay_values(az_engine *e, float *values)
+{
+    if (!e || !e->have_episode) return fail(e, AZ_ERR_STATE, "no episode has been run");
+    if (!values) return fail(e, AZ_ERR_INVALID, "az_selfplay_values: null buffer");
+    DEVICE_GUARD(e);
+    const int nn = e->nn, G = e->episode_games;
+    std::vector<float> val((size_t)G * nn);
+    HIPCHECK(e, az_memcpy(e->stream, val.data(), e->rec_value.p, val.size() * 4, hipMemcpyDeviceToHost));
+    size_t r = 0;
+    for (int g = 0; g < G; g++)
+        for (int m = 0; m < e->h_nply[g]; m++) values[r++] = val[(size_t)g * nn + e->h_start[g] + m];
+    return AZ_OK;
+}
+
+extern "C" int az_selfplay_pack_values(az_engine *e, float *values_dev)
+{
+    if (!e || !e->have_episode || !values_dev) return fail(e, AZ_ERR_STATE, "az_selfplay_pack_values: no episode / null buffer");
+    DEVICE_GUARD(e);
+    int64_t records = 0;
+    int rc = upload_src_index(e, &records);
+    if (rc || records == 0) return rc;
+    hipLaunchKernelGGL(k_pack_values, dim3((unsigned)((records + 255) / 256)), dim3(256), 0, e->stream, (const float *)e->rec_value.p,
+                       (const int *)e->src_index.p, records, values_dev);
+    HIPCHECK(e, hipStreamSynchronize(e->stream));
+    HIPCHECK(e, hipGetLastError());
+    return AZ_OK;
+}
+
+extern "C" uint32_t az_resign_mix(uint32_t x)     // the host's az_fmix32 (az_device.h), which k_move names the exempt games by
+{
+    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
+    return x;
+}
+
+extern "C" int az_resign_exempt(uint32_t key, int playout_permille)
+{
+    return (int)(az_resign_mix(key) % 1000u) < playout_permille ? 1 : 0;
+}
+
+extern "C" int az_set_resign(az_engine *e, double threshold, int min_ply, int playout_permille)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_resign: an episode is open (az_selfplay_end first)");
+    if (!(threshold >= 0.0 && threshold <= 1.0) || min_ply < 0 || playout_permille < 0 || playout_permille > 1000)
+        return fail(e, AZ_ERR_INVALID, "az_set_resign: threshold %g (0 = off, else in (0, 1]), min_ply %d (>= 0), playout_permille %d (0..1000)",
+                    threshold, min_ply, playout_permille);
+    e->resign_thr = threshold; e->resign_min_ply = min_ply; e->resign_permille = playout_permille;
+    return AZ_OK;
+}
+
+extern "C" int az_get_resign(const az_engine *e, double *threshold, int *min_ply, int *playout_permille)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (threshold) *threshold = e->resign_thr;
+    if (min_ply) *min_ply = e->resign_min_ply;
+    if (playout_permille) *playout_permille = e->resign_permille;
+    return AZ_OK;
+}
+
+extern "C" int az_selfplay_resign_info(az_engine *e, int32_t *cross_ply, uint8_t *exempt)
+{
+    if (!e || !e->have_episode) return fail(e, AZ_ERR_STATE, "no episode has been run");
+    for (int g = 0; g < e->episode_games; g++) {
+        if (cross_ply) cross_ply[g] = e->h_cross[g];
+        if (exempt) exempt[g] = (uint8_t)az_resign_exempt(e->h_key0 + (uint32_t)g, e->h_permille);
+    }
     return AZ_OK;
 }
 

@@ -102,6 +102,12 @@ struct DevState {
     int start_count;
     int start_first;       // `first` mod 2 * start_count: game g starts from position (start_first + g) % start_count, in the
                            // arena from ((start_first + g) >> 1) % start_count with the colours exchanged for odd g
+    // --- search value per record and opt-in resignation (az_set_resign), written / applied by k_move only ---
+    double resign_thr;     // a ply crosses when ply >= resign_min_ply and v < -resign_thr; 0 = off (and on every preset episode)
+    float *rec_value;      // [G*nn] (float)v of every record, v = W[a*] / N[a*] of the root's most visited legal cell
+    int *g_cross;          // [G] first crossing ply of the game, exempt games included; -1 = none
+    int resign_min_ply;
+    int resign_permille;   // game g is exempt (plays on) when fmix32(key(g)) % 1000 < resign_permille; no arena game is
 };
 __device__ __forceinline__ int game_key(const DevState &d, int game) { return (int)(d.game_key0 + d.key_stride * (unsigned)game); }
 
@@ -1048,6 +1054,21 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
             d.rec_visits[ri * G::nn + j] = (unsigned short)Nj[i];
         }
     }
+    // ---- search value of the ply: v = W[a*] / N[a*], a* = the most visited legal cell, the lowest cell on ties ----
+    // one order-independent reduction of (N << 16 | 0xFFFF - cell): N fits 16 bits, a cell 8.  Every ply ends with at least
+    // one visit under the root, so N[a*] >= 1.
+    unsigned best = 0u;
+#pragma unroll
+    for (int i = 0; i < G::CPL; i++) {
+        const unsigned key = ((unsigned)Nj[i] << 16) | (unsigned)(0xFFFF - (lane + 64 * i));
+        if (legal[i] && key > best) best = key;
+    }
+    best = wave_max_u(best);
+    const int astar = best ? 0xFFFF - (int)(best & 0xFFFFu) : 0;      // an active slot always has a legal cell
+    const double v = root[astar].W / (double)(int)(best >> 16);
+    // resignation (az_set_resign): the ply crosses below -threshold; an exempt game only notes it and plays on
+    const bool crossed = d.resign_thr > 0.0 && ply >= d.resign_min_ply && v < -d.resign_thr;
+    const bool exempt = !d.arena && az_fmix32((unsigned)game_key(d, g)) % 1000u < (unsigned)d.resign_permille;
     // ---- apply + terminal ----
     Plane mine = pl == 1 ? X : O;
     pl_set(mine, a);
@@ -1055,6 +1076,7 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
     pl_set(occ2, a);
     bool win = wins_through(mine, a, N, d.k);
     bool full = pl_count(occ2) == G::nn;
+    const bool resign = crossed && !exempt && !(win || full);     // a natural end by this very move takes precedence
     if (lane == 0) {
         u64 *rp = d.rec_planes + ri * 8;
         for (int q = 0; q < 4; q++) {
@@ -1068,7 +1090,10 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
         d.s_player[b] = 3 - pl;
         d.s_last[b] = a;
         d.s_ply[b] = ply + 1;
+        d.rec_value[ri] = (float)v;
+        if (crossed && d.g_cross[g] < 0) d.g_cross[g] = ply;
         int res = win ? pl : (full ? 3 : 0);
+        if (resign) res = 3 - pl;           // the mover resigns: on a crossing ply this is the result, max_plies or not
         bool cut = d.max_plies > 0 && ply + 1 >= d.max_plies;
         if (res != 0 || cut) {
             d.g_result[g] = res;
@@ -1083,7 +1108,7 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
     // pass marks the rows reachable from the child, a second one moves them down in place (destination <= source)
     // and renumbers the child links (R <= REUSE_MAX_ROWS, checked by az_set_subtree_reuse).
     {
-        const bool cont = !(win || full) && !(d.max_plies > 0 && ply + 1 >= d.max_plies) && !d.arena;
+        const bool cont = !(win || full) && !resign && !(d.max_plies > 0 && ply + 1 >= d.max_plies) && !d.arena;
         Edge *rows = d.edges + (size_t)b * d.R * G::RW;
         const int c = cont ? (int)rows[a].child : 0;
         if (c == 0) {

@@ -10,6 +10,7 @@ from . import parallel
 from ._capi import AZ_MAX_SIMULATIONS, Engine
 from .controller import device_index, model_kind
 from .mcts import numpy_log_table
+from .self_play import check_resign
 
 
 def temperature_schedule(move: int) -> float:
@@ -18,7 +19,7 @@ def temperature_schedule(move: int) -> float:
 
 class ModelEvaluator:
     def __init__(self, game_class=None, print_games=False, device=None, seed=None, virtual_loss=1, eval_cache=0,
-                 start_positions=None):
+                 start_positions=None, resign: dict = None):
         self.game_class = game_class
         self.print_games = print_games
         self.device = device if device is not None else torch.device("cuda")
@@ -28,6 +29,9 @@ class ModelEvaluator:
         # opt-in: (boards, players, lasts); games 2i and 2i+1 both start from position i mod count, the second with the
         # colours exchanged, so every position is played once from either side
         self.start_positions = start_positions
+        # opt-in: dict(threshold, min_ply=0); an arena game ends as a loss of the mover once the search value of a ply falls
+        # below -threshold.  No arena game is exempt: a `playout` share is accepted and has no effect here.
+        self.resign = check_resign(resign)
         self._engine = None
 
     def evaluate(self, candidate_controller, baseline_controller, num_games=20, debug=False):
@@ -62,6 +66,11 @@ class ModelEvaluator:
             eng.set_start_positions(*self.start_positions, first=lo)      # lo is even (parallel.arena_block): no pair is torn apart
         elif eng.start_positions():
             eng.clear_start_positions()
+        self.resign = check_resign(self.resign)
+        if self.resign is not None:
+            eng.set_resign(**self.resign)
+        elif eng.resign()["threshold"]:
+            eng.set_resign(0.0)
         r = eng.arena(mine, seed0=seed0 + lo, temperature_table=T) if mine > 0 else {"wins": 0, "losses": 0, "draws": 0, "total": 0, "win_rate": 0.0}
         if world > 1:
             w, l, d = parallel.all_reduce_tally(r["wins"], r["losses"], r["draws"], dev, engine=eng)

@@ -7,7 +7,7 @@ import torch
 
 from . import constants as _c
 from . import parallel
-from ._capi import AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine
+from ._capi import AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine, resign_permille
 from .controller import device_index, model_kind
 from .mcts import numpy_log_table
 
@@ -17,13 +17,55 @@ def default_temperature_schedule(move: int) -> float:
     return (np.exp(-move / _c.TEMPERATURE_SCHEDULE_HALFTIME) + _c.TEMPERATURE_BASELINE) / norm
 
 
+def resign_stats(result, cross_ply, exempt, movers) -> dict:
+    """What an episode says about its resignation threshold, per game: result (AZ_RES_*, 0 = cut), cross_ply (first ply
+    whose search value crossed, -1 = none), exempt (the game was played out whatever its values) and movers (the side to
+    move at cross_ply, 1 / 2; ignored where cross_ply < 0).
+      resigned                games that ended by resignation: crossed, not exempt, lost by the side that crossed (a move
+                              that ends the game itself takes precedence, and then the mover has won or drawn)
+      exempt                  games that were played out
+      exempt_crossed          ... of which some ply crossed: they would have resigned
+      false_positives         ... of which the side that crossed did NOT lose in the end
+      false_positive_rate     false_positives / exempt_crossed, None without an exempt game that crossed"""
+    result, cross_ply = np.asarray(result, np.int64), np.asarray(cross_ply, np.int64)
+    exempt, movers = np.asarray(exempt, bool), np.asarray(movers, np.int64)
+    if not (result.shape == cross_ply.shape == exempt.shape == movers.shape and result.ndim == 1):
+        raise ValueError("result, cross_ply, exempt and movers must be one-dimensional and of one length")
+    crossed = cross_ply >= 0
+    if not np.isin(movers[crossed], (1, 2)).all():
+        raise ValueError("movers must be 1 or 2 wherever a ply crossed")
+    lost = crossed & (result == 3 - movers)
+    ec = crossed & exempt
+    fp = int((ec & ~lost).sum())
+    return {"games": int(len(result)), "resigned": int((lost & ~exempt).sum()), "exempt": int(exempt.sum()),
+            "exempt_crossed": int(ec.sum()), "false_positives": fp,
+            "false_positive_rate": fp / int(ec.sum()) if ec.any() else None}
+
+
+def check_resign(resign):
+    """None, or the dict a seam takes: threshold in (0, 1], optional min_ply >= 0 and playout share in [0, 1]."""
+    if resign is None:
+        return None
+    extra = set(resign) - {"threshold", "min_ply", "playout"}
+    if extra or "threshold" not in resign:
+        raise ValueError(f"resign takes threshold, min_ply and playout (threshold is required), got {sorted(resign)}")
+    out = {"threshold": float(resign["threshold"]), "min_ply": int(resign.get("min_ply", 0)),
+           "playout": float(resign.get("playout", 0.0))}
+    if not 0.0 < out["threshold"] <= 1.0:
+        raise ValueError(f"resign threshold must be in (0, 1], got {out['threshold']}")
+    if out["min_ply"] < 0:
+        raise ValueError(f"resign min_ply must be >= 0, got {out['min_ply']}")
+    resign_permille(out["playout"])
+    return out
+
+
 class SelfPlayManager:
     def __init__(self, controller, device, mcts_params: dict = None,
                  temperature_schedule: Callable[[int], float] = default_temperature_schedule,
                  concurrent_games: int = None, augmentation: int = AZ_AUG_REFERENCE4, seed: int = None,
                  engines_per_gpu: int = None, subtree_reuse: bool = False, gather_to: int = None,
                  eval_cache: int = 0, virtual_loss: int = 1, trunk: str = "f32", leaf_symmetry: bool = False,
-                 start_positions=None):
+                 start_positions=None, resign: dict = None):
         self.controller = controller
         self.device = device
         self.mcts_params = mcts_params or {"num_simulations": 100}
@@ -38,6 +80,10 @@ class SelfPlayManager:
         self.trunk = trunk                    # opt-in: "bf16x3" / "f16x2" = fp32-emulating conv trunks on the 16-bit matrix cores (tolerance, not bit-exact)
         self.leaf_symmetry = leaf_symmetry    # opt-in: every net evaluation sees a pseudo-random dihedral symmetry of the position (README.md:61,82)
         self.start_positions = start_positions    # opt-in: (boards, players, lasts); game g continues position g mod count instead of starting on the empty board
+        # opt-in: dict(threshold, min_ply=0, playout=0.0); a game ends as a loss of the mover once the search value of a ply
+        # falls below -threshold, except in the share `playout` of the games, which measure the false positives
+        self.resign = check_resign(resign)
+        self.last_resign_stats = None         # resign_stats() of this rank's games of the last episode (None while resignation is off)
         self.gather_to = gather_to            # multi-rank: None = every rank receives all records (all-gather); r = only rank r does
         self.last_counters = None
         self._engine = None
@@ -74,6 +120,20 @@ class SelfPlayManager:
         print(f"[SelfPlayManager] Collected {len(zs)} examples from {num_games} games.")
         return list(zip(states.unbind(0), list(pis), zs.tolist()))     # (tensor view, ndarray view, int) per example
 
+    def _resign_stats(self, eng, lo, mine):
+        """resign_stats of the games this rank has just played (ids lo .. lo + mine); X moves first from the empty board,
+        a start position names its own side to move"""
+        _, result = eng.games()
+        cross, exempt = eng.resign_info()
+        first, ply0 = np.ones(mine, np.int64), np.zeros(mine, np.int64)
+        if self.start_positions is not None:
+            boards, players, _ = self.start_positions
+            boards = np.asarray(boards).reshape(len(players), -1)
+            idx = (lo + np.arange(mine)) % len(players)
+            first, ply0 = np.asarray(players, np.int64)[idx], (boards != 0).sum(axis=1)[idx]
+        movers = np.where((cross - ply0) % 2 == 0, first, 3 - first)
+        return resign_stats(result, cross, exempt, movers)
+
     def generate_packed(self, num_games: int):
         """The same episode, but the result stays on the device as packed records (one per position, all ranks'
         records after the exchange): (uint8 tensor, record count, engine, device, n).  Feed it to
@@ -104,8 +164,16 @@ class SelfPlayManager:
             eng.set_start_positions(*self.start_positions, first=lo)      # by global game id, like the seed
         elif eng.start_positions():
             eng.clear_start_positions()
+        self.resign = check_resign(self.resign)
+        if self.resign is not None:
+            eng.set_resign(**self.resign)
+        elif eng.resign()["threshold"]:
+            eng.set_resign(0.0)
+        self.last_resign_stats = None
         if mine > 0:
             self.last_counters = eng.selfplay(mine, seed0=seed0 + lo, temperature_table=T)
+            if self.resign is not None:
+                self.last_resign_stats = self._resign_stats(eng, lo, mine)
         else:
             eng.clear_episode()       # no games for this rank: it must not send the engine's previous episode again
         packed, counts = parallel.gather_packed_records(eng, dev, dst=self.gather_to)

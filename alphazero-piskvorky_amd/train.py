@@ -27,13 +27,16 @@ PROMOTION_THRESHOLD = 0.55          # promoter.py:19, strict ">" with draws coun
 
 
 def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=None, log=print, device_replay=False,
-        subtree_reuse=False, trunk="f32", eval_sims=None, start_positions=None):
+        subtree_reuse=False, trunk="f32", eval_sims=None, start_positions=None, resign=None):
     """eval_sims: simulations per move in the arena (evaluator.py:53-62 takes NUM_EVAL_SIMULATIONS = 200 whatever the
     self-play count is; main() passes that constant); None = as many as self-play, which keeps small test runs short.
     device_replay=True keeps the examples on the GPU from the episode-end gather to the optimizer step (packed records
     in a device ring, batches unpacked + augmented by az_examples_gather) instead of materialising Python tuples.
     start_positions: (boards, players, lasts) the self-play games continue instead of starting on the empty board
-    (Engine.set_start_positions); the arena keeps the empty board."""
+    (Engine.set_start_positions); the arena keeps the empty board.
+    resign: dict(threshold, min_ply, playout) for the self-play games (Engine.set_resign): a game ends as a loss of the mover
+    once a ply's search value falls below -threshold; the share `playout` of the games plays on and gives the false-positive
+    rate that every episode's log line reports.  The arena, which decides promotions, plays every game to its end."""
     torch.manual_seed(seed)
     n = C.BOARD_SIZE
     rank, world = parallel.rank_world()
@@ -44,7 +47,7 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
     # train.py:95-104), rank 0 takes the optimizer steps and its weights are broadcast; only rank 0 writes model_dir
     manager = SelfPlayManager(candidate, device, mcts_params={"num_simulations": sims, "c_puct": C.SELF_PLAY_EXPLORATION_CONSTANT},
                               seed=seed, subtree_reuse=subtree_reuse, gather_to=0 if world > 1 else None, trunk=trunk,
-                              start_positions=start_positions)
+                              start_positions=start_positions, resign=resign)
     evaluator = ModelEvaluator(game_class=Gomoku, print_games=False, device=device, seed=seed)
     promoter = ModelPromoter(model_dir, evaluator, lambda: GomokuNet(board_size=n), device, threshold=PROMOTION_THRESHOLD)
     buffer = ReplayBuffer(capacity=C.BUFFER_CAPACITY)
@@ -82,6 +85,13 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
             loss = losses[-1].get("loss") if losses else None
             history.append(dict(metrics, episode=ep, examples=len(data), loss=loss,
                                 promoted=promoted, seconds=time.perf_counter() - t0))
+            rs = manager.last_resign_stats
+            if rs is not None:           # this rank's games
+                history[-1]["resign"] = rs
+                fp = rs["false_positive_rate"]
+                log(f"[train] episode {ep}: {rs['resigned']} of {rs['games']} games resigned; {rs['exempt']} played out, "
+                    f"{rs['exempt_crossed']} of them crossed the threshold, {rs['false_positives']} of those did not lose: "
+                    f"false-positive rate {'n/a' if fp is None else format(fp, '.1%')}")
             log(f"[train] episode {ep}: {len(data)} examples, loss {'n/a' if loss is None else format(loss, '.4f')}, "
                 f"arena {metrics['wins']}/{metrics['losses']}/{metrics['draws']} -> {win_rate:.2%}"
                 f"{' (promoted)' if promoted else ''}, {history[-1]['seconds']:.1f}s")
@@ -106,7 +116,19 @@ def main():
     ap.add_argument("--start-positions", default=None, metavar="FILE.npz",
                     help="self-play games continue these positions instead of starting on the empty board: arrays boards "
                          "[count, n*n] (0 / 1 X / 2 O), players [count] (1 / 2), lasts [count] (-1 none); game g takes position g mod count")
+    ap.add_argument("--resign-threshold", type=float, default=None, metavar="T",
+                    help="self-play games resign: a game ends as a loss of the mover once a ply's search value is below -T (0 < T <= 1)")
+    ap.add_argument("--resign-min-ply", type=int, default=0, help="no resignation before this ply")
+    ap.add_argument("--resign-playout", type=float, default=None, metavar="SHARE",
+                    help="share of the games that play on past the threshold, to measure its false-positive rate "
+                         "(default 0.1 when --resign-threshold is given)")
     a = ap.parse_args()
+    resign = None
+    if a.resign_threshold is not None:
+        resign = {"threshold": a.resign_threshold, "min_ply": a.resign_min_ply,
+                  "playout": 0.1 if a.resign_playout is None else a.resign_playout}
+    elif a.resign_playout is not None or a.resign_min_ply:
+        ap.error("--resign-min-ply and --resign-playout need --resign-threshold")
     start_positions = None
     if a.start_positions:
         with np.load(a.start_positions) as z:
@@ -121,7 +143,8 @@ def main():
         td.init_process_group("nccl", device_id=torch.device("cuda", local))
         a.device = f"cuda:{local}"
     run(a.episodes, a.games, a.sims, a.eval_games, a.device, model_dir=a.model_dir, device_replay=a.device_replay,
-        subtree_reuse=a.subtree_reuse, trunk=a.trunk, eval_sims=C.NUM_EVAL_SIMULATIONS, start_positions=start_positions)
+        subtree_reuse=a.subtree_reuse, trunk=a.trunk, eval_sims=C.NUM_EVAL_SIMULATIONS, start_positions=start_positions,
+        resign=resign)
     if world > 1:
         td.barrier()
         td.destroy_process_group()

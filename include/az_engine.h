@@ -405,6 +405,54 @@ int az_set_start_positions(az_engine *e, int count, const uint8_t *boards /* [co
                            const uint8_t *players, const int16_t *lasts, int64_t first);
 int az_get_start_positions(const az_engine *e);   /* count in force, 0 = none */
 
+/* The search value per record, and opt-in resignation (AlphaGo Zero resigned below a value threshold and let a share of its
+ * games play out to measure the false positives; the reference plays every game to the end, self_play.py:52-58).
+ *
+ * Search value of a ply.  After the search of a ply let a* be the legal cell with the largest root visit count N, the lowest
+ * cell index on ties (the N that pi is made from, mcts.py:144-160).  v = W[a*] / (double)N[a*]: one IEEE float64 division of
+ * the root row's own fields (az_search's `W` and `visits`), from the mover's point of view.  N[a*] >= 1: every ply ends with
+ * num_simulations >= 1 visits under the root, retained roots of subtree reuse included.  (float)v is recorded for every
+ * record of every episode, resignation on or off: az_selfplay_values returns it game-major then ply, in exactly the order
+ * and count of az_selfplay_records; az_selfplay_pack_values writes the same floats to a DEVICE buffer in the order
+ * az_selfplay_pack packs.  AZ_ERR_STATE without an episode.  The packed record format is unchanged, and the values of other
+ * ranks are not exchanged: az_dist_gather_records carries the packed records only.
+ *
+ * Rule.  az_set_resign(threshold in (0, 1], min_ply >= 0, playout_permille in 0..1000); threshold = 0 switches resignation
+ * off, which is the default.  A ply of game g CROSSES when ply >= min_ply (the absolute ply = stones on the board, as
+ * everywhere) and v < -threshold, strictly, in float64.  Game g is EXEMPT when
+ *     az_resign_mix(key(g)) % 1000 < playout_permille,
+ * key(g) = the low 32 bits of seed0 + g, the global name of the game that the leaf-symmetry hash uses, so exemption does not
+ * depend on slots, lanes or ranks (a rank playing the id block [lo, hi) passes seed0 + lo).  The move of a crossing ply is
+ * made like any other: pi, the sampled action, the record, the move applied, the terminal test.  Then, if that move did not
+ * end the game and the game is not exempt, the game ends with the opponent of the mover as winner: result = 3 - mover,
+ * nply = ply + 1.  A natural end (win or full board) by that very move takes precedence; a cut by max_plies stays a cut
+ * unless the ply crossed -- on a crossing ply the resignation is the result.
+ *   Prefix property: a game played with resignation on is the same-seed game played with it off, truncated after its first
+ *   crossing ply m: the records of plies 0..m are byte-identical, nply = m + 1, result = the other colour (z follows from the
+ *   result as always).  An exempt game is the whole game, unchanged.
+ * For every game the first crossing ply is kept, exempt games included: az_selfplay_resign_info gives cross_ply[g] (absolute
+ * ply, -1 = none; all -1 while resignation is off) and exempt[g] (0 / 1) per game of the last episode; either may be NULL;
+ * AZ_ERR_STATE without an episode, like az_selfplay_games.  The false-positive rate of a threshold is read from the exempt
+ * games that crossed: those whose crossing side did not lose.
+ * Applies to az_selfplay* and az_arena.  A resigned arena game shows in results[g] / nply[g] and in the tally like any other
+ * decided game; NO arena game is exempt (playout_permille is ignored there; az_selfplay_resign_info after an arena reports
+ * exempt = 0).  az_search, az_search_batch, az_search_callback, az_net_eval and az_rules_replay ignore the setting.  Combines
+ * with every search option (evaluation cache, subtree reuse -- the slot of a resigned game starts its next game from a fresh
+ * root --, virtual-loss batching, leaf symmetry, both nets, emulated trunks, deep engines, start positions) and with both
+ * the lock-step pipeline and the persistent search kernel.  az_set_resign: AZ_ERR_INVALID for arguments out of range (the
+ * previous setting is kept), AZ_ERR_STATE while an episode is open. */
+/* mix, murmur3's 32-bit finaliser, in uint32_t arithmetic:
+ *     x ^= x >> 16;  x *= 0x85EBCA6B;  x ^= x >> 13;  x *= 0xC2B2AE35;  x ^= x >> 16;
+ * az_resign_mix and az_resign_exempt are host-side helpers (they need no GPU, like az_rng_*): the mix itself, and 1 / 0 for
+ * whether the game named `key` is exempt under playout_permille. */
+uint32_t az_resign_mix(uint32_t x);
+int az_resign_exempt(uint32_t key, int playout_permille);
+int az_set_resign(az_engine *e, double threshold, int min_ply, int playout_permille);
+int az_get_resign(const az_engine *e, double *threshold, int *min_ply, int *playout_permille);
+int az_selfplay_values(az_engine *e, float *values);
+int az_selfplay_pack_values(az_engine *e, float *values_dev);
+int az_selfplay_resign_info(az_engine *e, int32_t *cross_ply, uint8_t *exempt);
+
 /* Opt-in: fp32-emulating conv trunks.  AZ_TRUNK_F32 (default) computes the net's forward (net.py:55-72) on the float32
  * matrix instruction in the build's canonical fp order: bit-identical to the oracle.  The other two run every conv but the
  * first (99 % of the net's arithmetic) and the 1x1 head convs on the 16 x faster 16-bit matrix instructions with split
