@@ -25,6 +25,10 @@ Fixture families:
   G8 resnet_ckpt_5.npz      the VALUES of one historical ResidualBlock checkpoint of the reference (weights-only load of
                             alphazero/models/old/model_20250728_225053.pt: data, no code) + the outputs of the BUILD's torch module
                             loaded with them (the reference ships no forward for this variant)  (python make_golden.py resnet)
+  G11 tree_ties_{n}x{k}.npz MCTS.run with tied-prior evaluators (the constant nets of tests/ties.py, whose P and v come from the
+                            build's oracle net forward) at 3x3, 7x7, 8x8, 9x9, 13x13, 15x15: root N / W / pi / action, and how
+                            many selections had two or more maximal children, at the root and below it; every case has such
+                            selections below the root and every noise-free case at the root  (python make_golden.py ties)
 """
 import json
 import os
@@ -658,7 +662,175 @@ def worker_edge():
         **{key: np.array([c[key] for c in recs]) for key in recs[0]})
 
 
+# --------------------------------------------------------------------------
+# G11 tree_ties_{n}x{k}.npz: MCTS.run with evaluators whose priors TIE (the constant nets of tests/ties.py), so that the
+# order rule of mcts.py:70-74 -- max returns the first maximal child, row-major legal order -- decides the search.
+#   python tests/golden/make_golden.py ties
+# --------------------------------------------------------------------------
+# (pattern, vbias, stones on the board, root noise, S, c_puct); at 3x3 `stones` is capped at 4
+TIE_CASES = [
+    ("uniform", 0.0, 0, False, 200, 2.0),
+    ("uniform", -0.5, 0, False, 120, 2.0),
+    ("uniform", 0.25, 4, True, 120, 2.0),
+    ("uniform", -0.5, 8, True, 400, 0.3),
+    ("three", 0.0, 3, False, 160, 0.3),
+    ("three", -0.5, 6, False, 200, 2.0),
+    ("three", 0.25, 0, True, 120, 2.0),
+    ("checker", 0.0, 5, False, 160, 0.3),
+    ("checker", -0.5, 10, False, 200, 2.0),
+    ("checker", 0.25, 7, False, 120, 2.0),
+]
+TIE_CASES_MIRROR = [           # n >= 9: the deciding tie inside one lane of a tree row (cells j and j + 64)
+    ("mirror", 0.0, 0, False, 200, 2.0),
+    ("mirror", -0.5, 4, False, 160, 0.3),
+]
+TIE_S_3x3 = {200: 300, 400: 300}      # 3x3: S large enough that the search runs into wins and full boards everywhere
+TIE_S_7x7 = {160: 100}                 # 7x7: six cases whose tree fits the persistent kernel's LDS (120 simulations do, 160 do not)
+TIE_S_LARGE = {120: 300, 160: 300, 200: 400}      # 13x13, 15x15: more simulations than cells, or flat priors never leave the root
+TIE_DEEP_3x3 = [("uniform", 0.0, 0, False, 1100, 2.0), ("three", -0.5, 0, False, 1100, 2.0)]      # more than 1024 simulations
+
+
+def tie_raw_tables(n):
+    """Prior tables no net produces (the callback seam takes them 'exactly as given'): one with exact zeros, one that does not
+    sum to 1.  -> [(P float32[n*n], v, S, c_puct)]"""
+    j = np.arange(n * n)
+    zeros = np.where(j % 3 == 0, 0.0, 1.0 / 64).astype(np.float32)
+    unnorm = ((j % 2 + 1) * 0.125).astype(np.float32)
+    return [(zeros, 0.25, 200, 2.0), (unnorm, -0.25, 160, 0.3)]
+
+
+def worker_ties(n, k):
+    sys.path.insert(0, REF)
+    import constants
+    constants.BOARD_SIZE, constants.WIN_LENGTH = n, k
+    import random
+    import importlib.util
+    import mcts as mcts_mod
+    from games import Gomoku
+    from mcts import MCTS
+    X = constants.X
+    nn = n * n
+    root_dir = os.path.dirname(os.path.dirname(HERE))
+    sys.path.insert(0, root_dir)
+    from oracle import oracle as orc                       # the build's own net forward: P and v of a constant net
+    spec = importlib.util.spec_from_file_location("ties", os.path.join(os.path.dirname(HERE), "ties.py"))
+    ties = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ties)
+
+    def abs_board(state):
+        b = np.zeros(nn, dtype=np.uint8)
+        for r in range(n):
+            for q in range(n):
+                if state.board[r][q] is not None:
+                    b[r * n + q] = 1 if state.board[r][q] == X else 2
+        return b
+
+    class Capture:
+        root = None
+    tied = dict(root=0, below=0)
+    class RecNode(mcts_mod.Node):
+        def __init__(self, state, parent=None, prior=1.0):
+            super().__init__(state, parent, prior)
+            if parent is None:
+                Capture.root = self
+        def select(self, c_puct):
+            # the generator's own count of the selections the order rule decides: the key of mcts.py:73, evaluated as there
+            keys = [ch.Q + c_puct * ch.prior * np.sqrt(self.N + 1e-8) / (1 + ch.N) for ch in self.children.values()]
+            m = max(keys)
+            if sum(1 for s_ in keys if s_ == m) >= 2:
+                tied["root" if self.parent is None else "below"] += 1
+            return super().select(c_puct)
+    mcts_mod.Node = RecNode
+
+    o = orc.Oracle(n, k, 1)
+    rng = random.Random(7000 + n)
+
+    def position(stones):
+        while True:
+            s = Gomoku()
+            for _ in range(stones):
+                s = s.apply_action(rng.choice(s.get_legal_actions()))
+                if s.is_terminal():
+                    break
+            if not s.is_terminal():
+                return s
+
+    def run(s, P, v, S, c_puct, noise, seed, T):
+        tied["root"] = tied["below"] = 0
+        np.random.seed(seed)
+        m = MCTS(lambda state: (P.reshape(n, n).copy(), v), num_simulations=S, c_puct=c_puct)
+        pi, a = m.run(s, temperature=T, add_root_noise=noise)
+        N = np.zeros(nn, dtype=np.int32); W = np.zeros(nn, dtype=np.float64); Pr = np.zeros(nn, dtype=np.float32)
+        for (r, c), ch in Capture.root.children.items():
+            N[r * n + c] = ch.N; W[r * n + c] = ch.W; Pr[r * n + c] = np.float32(ch.prior)
+        return dict(pi=pi.astype(np.float32).reshape(nn), action=a[0] * n + a[1], N=N, W=W, Pr=Pr,
+                    tied_root=tied["root"], tied_below=tied["below"])
+
+    table = list(TIE_CASES) + (list(TIE_CASES_MIRROR) if n >= 9 else []) + (TIE_DEEP_3x3 if n == 3 else [])
+    cases = []
+    for i, (pattern, vbias, stones, noise, S, c_puct) in enumerate(table):
+        if n == 3:
+            stones, S = min(stones, 4), TIE_S_3x3.get(S, S)
+        if n == 7:
+            S = TIE_S_7x7.get(S, S)
+        if n >= 13:
+            S = TIE_S_LARGE.get(S, S)
+        levels = ties.levels_of(pattern, n, seed=7100 + n)
+        net = orc.Net(n, ties.constant_state_dict(n, levels, vbias))
+        seed = 7200 + 17 * i + n
+        T = ties.temperature(stones, noise)
+        what = f"{n}x{n} case {i} {pattern} vbias={vbias} stones={stones} noise={noise} S={S} c_puct={c_puct}"
+        for attempt in range(20 if stones else 1):          # positions are drawn until the reference alone meets the condition
+            s = position(stones)
+            board = abs_board(s)
+            pl = 1 if s.current_player == X else 2
+            la = -1 if s.last_action is None else s.last_action[0] * n + s.last_action[1]
+            _, P, v = net.eval(o.encode(board, pl, la))
+            r = run(s, P, v, S, c_puct, noise, seed, T)
+            print(f"{what}: tied_root={r['tied_root']} tied_below={r['tied_below']} distinct N={len(np.unique(r['N']))}", flush=True)
+            if r["tied_below"] > 0 and (noise or r["tied_root"] > 0):
+                break
+        assert r["tied_below"] > 0 and (noise or r["tied_root"] > 0), f"{what}: the order rule decides nothing here; choose other inputs"
+        assert int(r["N"].sum()) == S
+        cases.append(dict(board=board, player=pl, last=la, noise=int(noise), seed=seed, T=T, S=S, c_puct=c_puct,
+                          levels=levels, vbias=np.float32(vbias), P=P, v=np.float32(v), pattern=pattern,
+                          N=r["N"], W=r["W"], prior=r["Pr"], pi=r["pi"], action=r["action"],
+                          tied_root=r["tied_root"], tied_below=r["tied_below"]))
+    out = {key: np.array([c[key] for c in cases]) for key in cases[0]}
+    if n == 9:
+        raw = []
+        for i, (P, v, S, c_puct) in enumerate(tie_raw_tables(n)):
+            s = position(4)
+            seed = 7300 + i
+            r = run(s, P, v, S, c_puct, False, seed, ties.temperature(4, False))
+            print(f"9x9 raw table {i}: tied_root={r['tied_root']} tied_below={r['tied_below']}", flush=True)
+            assert r["tied_root"] > 0 and r["tied_below"] > 0
+            raw.append(dict(board=abs_board(s), player=1 if s.current_player == X else 2,
+                            last=s.last_action[0] * n + s.last_action[1], seed=seed, T=ties.temperature(4, False), S=S,
+                            c_puct=c_puct, P=P, v=np.float32(v), N=r["N"], W=r["W"], prior=r["Pr"], pi=r["pi"],
+                            action=r["action"], tied_root=r["tied_root"], tied_below=r["tied_below"]))
+        out.update({"raw_" + key: np.array([c[key] for c in raw]) for key in raw[0]})
+    path = os.path.join(HERE, f"tree_ties_{n}x{k}.npz")
+    np.savez_compressed(path, n=n, k=k, alpha=0.3, w=0.25, **out)
+    size = os.path.getsize(path)
+    assert size < 64 * 1024, f"{path}: {size} bytes"
+    print(f"{os.path.basename(path)}: {len(cases)} cases, {size} bytes", flush=True)
+
+
+TIE_SIZES = ((3, 3), (7, 4), (8, 5), (9, 5), (13, 5), (15, 5))
+
+
 if __name__ == "__main__":
+    if len(sys.argv) == 2 and sys.argv[1] == "ties":
+        env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
+        procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "ties", str(n), str(k)], env=env, cwd="/tmp")
+                 for n, k in TIE_SIZES]
+        rc = [p.wait() for p in procs]
+        print("done", rc)
+        sys.exit(max(rc))
+    if len(sys.argv) == 4 and sys.argv[1] == "ties":
+        worker_ties(int(sys.argv[2]), int(sys.argv[3]))
+        sys.exit(0)
     if len(sys.argv) == 2 and sys.argv[1] == "edge":
         env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
         sys.exit(subprocess.call([sys.executable, os.path.abspath(__file__), "edge", "worker"], env=env, cwd="/tmp"))

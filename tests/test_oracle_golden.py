@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
+from tests.ties import TIE_SIZES, constant_state_dict
 from tests.util import SIZES, load, weights_from_fixture, synth_eval_codes, GOLDEN
 
 
@@ -79,6 +80,38 @@ def test_tree_search_bit_exact_vs_reference(n, k):
         assert np.array_equal(r["P"], z["P"][i])
         assert r["nexp"] == int(z["nexp"][i]) and r["maxd"] == int(z["maxd"][i])
         assert r["action"] == int(z["action"][i])
+        np.testing.assert_allclose(r["pi"], z["pi"][i], rtol=0, atol=1e-6)
+
+
+@pytest.mark.parametrize("n,k", TIE_SIZES)
+def test_tied_prior_search_bit_exact_vs_reference(n, k):
+    """G11: MCTS.run with constant nets -- a few discrete prior levels, one value for every position -- where the order rule of
+    mcts.py:70-74 (max returns the first maximal child, row-major legal order) decides the search: N, W (float64), priors and
+    action are bit-exact.  The stored counters say that it does decide: in every case selections below the root had two or more
+    maximal children, and in every noise-free case selections at the root had."""
+    z = load(f"tree_ties_{n}x{k}.npz")
+    count = len(z["seed"])
+    assert 8 <= count <= 12 + 2 * (n == 3)           # (3x3 carries the two deep cases as well)
+    enc = orc.Oracle(n, k, 1)
+    for i in range(count):
+        S, board, pl, last = int(z["S"][i]), z["board"][i], int(z["player"][i]), int(z["last"][i])
+        what = f"{n}x{n} case {i} ({z['pattern'][i]}, vbias {float(z['vbias'][i])}, S {S}, c_puct {float(z['c_puct'][i])})"
+        assert int(z["tied_below"][i]) > 0, f"{what}: no tied selection below the root"
+        assert z["noise"][i] or int(z["tied_root"][i]) > 0, f"{what}: no tied selection at the root"
+        net = orc.Net(n, constant_state_dict(n, z["levels"][i], float(z["vbias"][i])))
+        logits, P, v = net.eval(enc.encode(board, pl, last))
+        stale = f"{what}: the fixture is stale, regenerate it (python tests/golden/make_golden.py ties)"
+        assert np.array_equal(logits, z["levels"][i]), f"{what}: the logits of a constant net are its policy_fc bias"
+        assert np.array_equal(P, z["P"][i]) and np.float32(v) == z["v"][i], stale
+        rs = np.random.RandomState(int(z["seed"][i]))
+        noise = rs.dirichlet([0.3] * int((board == 0).sum())) if z["noise"][i] else None
+        u = rs.random_sample()
+        r = orc.Oracle(n, k, S, c_puct=float(z["c_puct"][i])).search(net, board, pl, last, float(z["T"][i]), noise, u)
+        assert np.array_equal(r["N"], z["N"][i]), f"{what}: visit counts"
+        assert r["N"].sum() == S
+        assert np.array_equal(r["W"], z["W"][i]), f"{what}: W"
+        assert np.array_equal(r["P"], z["prior"][i]), f"{what}: priors"
+        assert r["action"] == int(z["action"][i]), f"{what}: action"
         np.testing.assert_allclose(r["pi"], z["pi"][i], rtol=0, atol=1e-6)
 
 
