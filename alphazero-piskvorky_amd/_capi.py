@@ -35,6 +35,7 @@ EXPORTS = [
     "az_set_start_positions", "az_get_start_positions",
     "az_set_resign", "az_get_resign", "az_selfplay_values", "az_selfplay_pack_values", "az_selfplay_resign_info",
     "az_resign_mix", "az_resign_exempt",
+    "az_set_external_evaluator", "az_get_external_evaluator", "az_ext_capacity", "az_ext_stats",
     "az_dist_unique_id", "az_dist_init", "az_dist_rank", "az_dist_world", "az_dist_counts", "az_dist_gather_records",
     "az_dist_allreduce_sum", "az_dist_broadcast",
 ]
@@ -79,6 +80,14 @@ class az_arena_args(C.Structure):
 class az_arena_result(C.Structure):
     _fields_ = [("wins", C.c_int32), ("losses", C.c_int32), ("draws", C.c_int32), ("total", C.c_int32),
                 ("win_rate", C.c_double)]
+
+
+_EVAL_BATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
+
+
+class az_ext_evaluator(C.Structure):
+    _fields_ = [("planes_dev", C.c_void_p), ("policy_dev", C.c_void_p), ("value_dev", C.c_void_p),
+                ("capacity", C.c_int32), ("fn", _EVAL_BATCH_FN), ("user", C.c_void_p)]
 
 
 _LIB = None
@@ -140,6 +149,11 @@ def lib():
             L.az_resign_mix.argtypes = [C.c_uint32]
             L.az_resign_mix.restype = C.c_uint32
             L.az_resign_exempt.argtypes = [C.c_uint32, C.c_int]
+        if hasattr(L, "az_set_external_evaluator"):
+            L.az_set_external_evaluator.argtypes = [C.c_void_p, C.POINTER(az_ext_evaluator)]
+            L.az_get_external_evaluator.argtypes = [C.c_void_p]
+            L.az_ext_capacity.argtypes = [C.c_void_p]
+            L.az_ext_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         _LIB = L
     return _LIB
 
@@ -228,8 +242,15 @@ class Engine:
             raise AzError(f"{'az_create_deep' if self.deep else 'az_create'} failed ({rc}): {lib().az_last_error(None).decode()}")
         self.record_bytes = int(lib().az_record_bytes(self.h))
         self.last_records = 0
+        self._ext_cb = None           # the ctypes callback of the external evaluator: kept alive while the engine holds it
+        self._ext_err = []
 
     def _check(self, rc, what):
+        err = self.__dict__.get("_ext_err")
+        if err:                       # the external evaluator raised inside the call: its exception, not the engine's code
+            ex = err[0]
+            del err[:]
+            raise ex
         if rc:
             raise AzError(f"{what} failed ({rc}): {lib().az_last_error(self.h).decode()}")
 
@@ -473,6 +494,54 @@ class Engine:
         self.last_records = int(nply.sum())
         return dict(wins=res.wins, losses=res.losses, draws=res.draws, total=res.total, win_rate=res.win_rate,
                     results=results, actions=actions, nply=nply)
+
+    # ---- batched external evaluator ----
+    def set_external_evaluator(self, planes_ptr, policy_ptr, value_ptr, capacity, fn):
+        """Opt-in: every net evaluation of selfplay*, arena, search and search_batch goes to fn(net, count) -> None
+        (az_set_external_evaluator).  planes_ptr / policy_ptr / value_ptr: DEVICE buffers [capacity, 4, n, n], [capacity, n*n]
+        and [capacity] of float32 on the engine's GPU, capacity >= ext_capacity().  When fn is called the first `count`
+        entries of the planes are complete; when it returns, the same entries of policy and value must be complete in
+        device memory (synchronise your stream).  fn runs on the calling thread; an exception it raises ends the engine
+        call and is raised again from it.  See include/az_engine.h."""
+        if not callable(fn):
+            raise TypeError("fn must be callable: fn(net, count) -> None")
+        if not (planes_ptr and policy_ptr and value_ptr):
+            raise ValueError("planes_ptr, policy_ptr and value_ptr must be device pointers (tensor.data_ptr())")
+        capacity = int(capacity)
+        if capacity < 1:
+            raise ValueError(f"capacity must be positive, got {capacity}")
+        err = self.__dict__.setdefault("_ext_err", [])
+
+        def _cb(user, net, count):
+            try:
+                fn(int(net), int(count))
+                return 0
+            except Exception as ex:       # nothing may propagate through the C frames
+                err.append(ex)
+                return 1
+
+        cb = _EVAL_BATCH_FN(_cb)
+        ev = az_ext_evaluator(int(planes_ptr), int(policy_ptr), int(value_ptr), capacity, cb, None)
+        self._check(lib().az_set_external_evaluator(self.h, C.byref(ev)), "az_set_external_evaluator")
+        self._ext_cb = cb
+
+    def clear_external_evaluator(self):
+        """Back to the engine's own evaluator (its nets, or the synthetic one)."""
+        self._check(lib().az_set_external_evaluator(self.h, None), "az_set_external_evaluator")
+        self._ext_cb = None
+
+    def external_evaluator(self):
+        return bool(lib().az_get_external_evaluator(self.h))
+
+    def ext_capacity(self):
+        """Items a request can hold: slots x leaves per batch; the evaluator's buffers must hold as many."""
+        return int(lib().az_ext_capacity(self.h))
+
+    def ext_stats(self):
+        """dict(requests, items) of the last (or open) episode / call: calls of the evaluator and items handed out."""
+        r, i = C.c_int64(0), C.c_int64(0)
+        self._check(lib().az_ext_stats(self.h, C.byref(r), C.byref(i)), "az_ext_stats")
+        return dict(requests=int(r.value), items=int(i.value))
 
     def set_subtree_reuse(self, on):
         """Opt-in: keep the chosen child's subtree for the next ply (mcts.py:17-22 TODO); see include/az_engine.h."""

@@ -41,6 +41,94 @@ def make_policy_value_fn(controller):
     return PolicyValueFn(controller)
 
 
+class BatchPolicyValueFn:
+    """The evaluator seam for ANY net on the engine's GPU, every game at once (az_set_external_evaluator):
+        fn(planes: cuda float32 tensor [count, 4, n, n], net: int) -> (policy [count, n*n] or [count, n, n], value [count] or [count, 1])
+    planes are Gomoku.encode of the positions that wait for an evaluation (games.py:86-129; plane 0 the side to move), a view
+    into this object's buffer that is valid during the call only; policy is used as priors exactly as given (mcts.py:63) and
+    value is for the side to move.  net is 0, in the arena 0 = candidate / 1 = baseline.  The object owns the three device
+    buffers the engine reads and writes, sizes them from Engine.ext_capacity(), copies fn's results in and synchronises the
+    current torch stream before it returns to the engine.  MCTS, SelfPlayManager(evaluator=...) and
+    ModelEvaluator(evaluators=...) take one."""
+
+    def __init__(self, fn, device=None):
+        if not callable(fn):
+            raise TypeError("fn must be callable: fn(planes [count, 4, n, n], net) -> (policy, value)")
+        self.fn = fn
+        self.device = torch.device("cuda", device_index(device))
+        self._buffers = {}            # per attached engine: (planes, policy, value)
+
+    def __call__(self, planes, net=0):
+        return self.fn(planes, net)
+
+    def attach(self, engine):
+        """Make this object the evaluator of `engine`; call again after set_virtual_loss (the capacity follows it)."""
+        n, nn, cap = engine.n, engine.nn, engine.ext_capacity()
+        if device_index(self.device) != engine.device:
+            raise ValueError(f"the evaluator lives on {self.device}, the engine on cuda:{engine.device}")
+        planes = torch.zeros((cap, 4, n, n), dtype=torch.float32, device=self.device)
+        policy = torch.zeros((cap, nn), dtype=torch.float32, device=self.device)
+        value = torch.zeros(cap, dtype=torch.float32, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()
+
+        def serve(net, count):
+            with torch.cuda.device(self.device):
+                P, v = self.fn(planes[:count], net)
+                policy[:count].copy_(torch.as_tensor(P, dtype=torch.float32).reshape(count, nn))
+                value[:count].copy_(torch.as_tensor(v, dtype=torch.float32).reshape(count))
+                torch.cuda.current_stream(self.device).synchronize()      # complete in device memory before the engine reads
+
+        engine.set_external_evaluator(planes.data_ptr(), policy.data_ptr(), value.data_ptr(), cap, serve)
+        self._buffers[id(engine)] = (planes, policy, value)
+        return engine
+
+    def detach(self, engine):
+        engine.clear_external_evaluator()
+        self._buffers.pop(id(engine), None)
+
+
+def make_batch_policy_value_fn(module_or_pair, device=None):
+    """BatchPolicyValueFn for any nn.Module with the reference's forward contract, planes [B, 4, n, n] -> (logits [B, n*n],
+    value [B, 1] or [B]) (net.py:55-72): evaluated under torch.no_grad() with softmax over the n*n logits, as
+    controller.py:44-49 does for one state.  A pair is (candidate, baseline) for the arena.
+    The number of positions that wait for the net changes from request to request, and a convolution library that tunes or
+    compiles per input shape would do so for every new count: the module is therefore shown batches of a few sizes only --
+    the request copied into a scratch tensor of the next power of two rows (at least 16; rows behind the request hold
+    zeros or older positions, their results are dropped)."""
+    mods = tuple(module_or_pair) if isinstance(module_or_pair, (tuple, list)) else (module_or_pair,)
+    if len(mods) not in (1, 2) or not all(isinstance(m, torch.nn.Module) for m in mods):
+        raise TypeError("make_batch_policy_value_fn takes an nn.Module or a (candidate, baseline) pair of them")
+    if device is None:
+        device = next(mods[0].parameters()).device
+    scratch = {}
+
+    def fn(planes, net):
+        count = planes.shape[0]
+        rows = 16
+        while rows < count:
+            rows *= 2
+        key = (rows, tuple(planes.shape[1:]), planes.device)
+        if key not in scratch:
+            scratch[key] = torch.zeros((rows,) + tuple(planes.shape[1:]), dtype=planes.dtype, device=planes.device)
+        batch = scratch[key]
+        batch[:count].copy_(planes)
+        with torch.no_grad():
+            logits, value = mods[net if len(mods) == 2 else 0](batch)
+            return torch.softmax(logits[:count], dim=1), value[:count]
+
+    return BatchPolicyValueFn(fn, device)
+
+
+def merge_batch_evaluators(evaluators):
+    """One BatchPolicyValueFn from a (candidate, baseline) pair of them: request `net` goes to evaluators[net]."""
+    if isinstance(evaluators, BatchPolicyValueFn):
+        return evaluators
+    pair = tuple(evaluators)
+    if len(pair) != 2 or not all(isinstance(x, BatchPolicyValueFn) for x in pair):
+        raise TypeError("evaluators must be a BatchPolicyValueFn or a (candidate, baseline) pair of them")
+    return BatchPolicyValueFn(lambda planes, net: pair[net].fn(planes, net), pair[0].device)
+
+
 def model_kind(net):
     from .net import GomokuResNet
     return "resnet" if isinstance(net, GomokuResNet) else "plain"

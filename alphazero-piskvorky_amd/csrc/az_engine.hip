@@ -101,6 +101,14 @@ struct az_engine {
     int trunk_mode = AZ_TRUNK_F32; // az_set_trunk_mode: AZ_TRUNK_BF16X3 / AZ_TRUNK_F16X2 = the convs on the 16-bit MFMAs with split operands
     int persist_gp = 0;            // games per workgroup of the persistent search kernel for the open episode, 0 = lock-step pipeline
     DevBuf cache;                  // evaluation cache shared by the lanes (az_set_eval_cache)
+    // az_set_external_evaluator: the caller's buffers and callback, the request's item map and count on the device, and
+    // the requests / items of the last (or open) episode
+    struct Ext {
+        bool on = false;
+        az_ext_evaluator ev{};
+        DevBuf map, count;
+        int64_t requests = 0, items = 0;
+    } ext;
     // az_search_batch, all sized by the slots: the wave's positions, temperatures and compact root statistics, and the all-zero
     // noise_off table that makes row g of the [wave][n*n] noise upload the tape of game g
     DevBuf bt_cells, bt_players, bt_lasts, bt_T, bt_zero_off, bt_visits, bt_W, bt_prior, bt_pi, bt_action;
@@ -125,6 +133,8 @@ struct az_engine {
         bool open = false;
         int num_games = 0, max_plies = 0;
         bool add_noise = true, arena = false, preset = false, profile = true;
+        bool ext = false;          // the episode's evaluations go to the external evaluator (az_set_external_evaluator)
+        int ext_net = -1;          // net id its requests carry instead of the items' own (az_search*: the slot argument), -1 = the items'
         az_counters c{};
         int64_t reused_roots = 0;
         unsigned game_key0 = 0;
@@ -791,7 +801,7 @@ extern "C" void az_destroy(az_engine *e)
     DevBuf *shared[] = {&e->T_table, &e->log_table, &e->sqrt_table, &e->noise_off, &e->next_game, &e->noise, &e->u,
                         &e->rec_planes, &e->rec_last, &e->rec_action, &e->rec_mover, &e->rec_pi, &e->rec_visits, &e->g_nply,
                         &e->g_result, &e->src_index, &e->rec_value, &e->g_cross, &e->cache, &e->start_tab, &e->bt_cells, &e->bt_players, &e->bt_lasts, &e->bt_T,
-                        &e->bt_zero_off, &e->bt_visits, &e->bt_W, &e->bt_prior, &e->bt_pi, &e->bt_action};
+                        &e->bt_zero_off, &e->bt_visits, &e->bt_W, &e->bt_prior, &e->bt_pi, &e->bt_action, &e->ext.map, &e->ext.count};
     for (DevBuf *b : shared) dev_free(*b);
     for (int s = 0; s < 2; s++) {
         PackedNet &p = e->net[s];
@@ -969,6 +979,7 @@ struct EpisodeSpec {
     bool batch = false;       // preset by az_search_batch: the ply runs over the preset slots only, throughput kernel choices as in self-play
     bool profile = true;      // this episode may be timed with HIP events (only when az_set_profiling is on)
     unsigned game_key0 = 0;   // low 32 bits of seed0: the leaf-symmetry hash names game g by its seed, seed0 + g
+    int ext_net = -1;         // external evaluator: the net id of the requests (az_search*: the slot argument), -1 = the items' own
 };
 
 static int host_threads()
@@ -1000,14 +1011,26 @@ static int lane_fail(Lane &L, int code, const char *fmt, ...)
 
 static int episode_begin(az_engine *e, const EpisodeSpec &sp)
 {
-    const bool net = e->cfg.eval_kind == AZ_EVAL_NET;
+    const bool ext = e->ext.on;            // the evaluator is outside the engine: no weights, no cache, priors as given
+    const bool net = !ext && e->cfg.eval_kind == AZ_EVAL_NET;
     if (net && !e->net[0].loaded) return fail(e, AZ_ERR_NO_WEIGHTS, "weights slot 0 not loaded");
     if (net && sp.arena && !e->net[1].loaded) return fail(e, AZ_ERR_NO_WEIGHTS, "weights slot 1 (baseline) not loaded");
+    if (ext) {
+        const int need = e->cfg.slots * e->vl;       // az_set_virtual_loss may have raised it since the evaluator was set
+        if (e->ext.ev.capacity < need) stop_tapes(e);    // az_selfplay_begin has started them already
+        if (e->ext.ev.capacity < need)
+            return fail(e, AZ_ERR_INVALID, "the external evaluator's buffers hold %d items, %d slots x %d leaves per batch need %d",
+                        e->ext.ev.capacity, e->cfg.slots, e->vl, need);
+        int rc = dev_alloc(e, e->ext.map, (size_t)need * sizeof(int), false);
+        if (!rc) rc = dev_alloc(e, e->ext.count, 16, true);
+        if (rc) return rc;
+        e->ext.requests = e->ext.items = 0;
+    }
     each_state(e, [&](DevState &d) {
         d.max_plies = sp.max_plies; d.add_noise = sp.add_noise ? 1 : 0; d.arena = sp.arena ? 1 : 0;
         d.total_games = sp.num_games; d.reuse = e->reuse; d.game_key0 = sp.game_key0;
-        d.cache = (float *)e->cache.p; d.cache_mask = e->cache_mask; d.cache_gen = e->cache_gen;
-        d.ext_eval = 0;
+        d.cache = ext ? nullptr : (float *)e->cache.p; d.cache_mask = e->cache_mask; d.cache_gen = e->cache_gen;
+        d.ext_eval = ext ? 1 : 0;
         // start positions are for the games k_refill claims: a preset episode (az_search, az_search_batch) brings its own
         const bool sps = !sp.preset && e->start_count > 0;
         d.start_pos = sps ? (const StartPos *)e->start_tab.p : nullptr;
@@ -1020,7 +1043,7 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
     });
     // persistent search kernel: plain net or synthetic evaluator, the reference's sequential search, trees that fit into LDS
     e->persist_gp = 0;
-    if (e->persist_allowed && !e->vl_kernel && e->trunk_mode == AZ_TRUNK_F32) {
+    if (e->persist_allowed && !ext && !e->vl_kernel && e->trunk_mode == AZ_TRUNK_F32) {
         const int synth = e->cfg.eval_kind == AZ_EVAL_SYNTHETIC ? 1 : 0;
         const int S = e->cfg.num_simulations;
         if (!sp.arena && (!sp.preset || sp.batch) && e->ops->search_prepare(S, 2, synth, e->cfg.model)) e->persist_gp = 2;
@@ -1030,6 +1053,7 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
     r = az_engine::Run();
     r.num_games = sp.num_games; r.max_plies = sp.max_plies; r.add_noise = sp.add_noise; r.arena = sp.arena;
     r.preset = sp.preset; r.profile = sp.profile;
+    r.ext = ext; r.ext_net = sp.ext_net;
     r.game_key0 = sp.game_key0;
     if (!sp.preset && e->start_count > 0) {
         r.start.resize(sp.num_games);
@@ -1215,6 +1239,131 @@ static int lane_plies(az_engine *e, Lane &L, int max_steps)
     return AZ_OK;
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// external evaluator (az_set_external_evaluator): the plies of an episode whose evaluations leave the engine
+// ------------------------------------------------------------------------------------------------
+// Whatever an external episode put into the lanes' states goes back on EVERY way out of it (episode end, a failed call, an
+// evaluator that gave up): with ext_eval left set, a later native episode would feed raw logits to the tree step as priors.
+static int active_slots(const az_engine *e);
+static void ext_restore(az_engine *e)
+{
+    each_state(e, [&](DevState &d) { d.ext_eval = 0; d.cache = (float *)e->cache.p; });
+}
+
+// the evaluator gave up (or a HIP call failed) in the middle of a ply: the episode is closed and every slot left idle
+static void ext_abort(az_engine *e)
+{
+    (void)hipStreamSynchronize(e->stream);
+    for (Lane &L : e->lanes) {
+        (void)hipMemsetAsync(L.s_status.p, 0, L.s_status.bytes, e->stream);
+        (void)hipMemsetAsync(L.leaf_kind.p, 0, L.leaf_kind.bytes, e->stream);
+        if (L.it_status.p) (void)hipMemsetAsync(L.it_status.p, 0, L.it_status.bytes, e->stream);
+        L.active = 0;
+    }
+    (void)hipStreamSynchronize(e->stream);
+    e->run.open = false;
+    e->have_episode = false;
+    stop_tapes(e);
+    ext_restore(e);
+}
+
+// All lanes play up to max_steps plies TOGETHER from the calling thread, kernel by kernel on the engine's stream: every
+// evaluation step gathers the pending items of all lanes into one request per net, hands it to the caller's evaluator and
+// scatters its answers before the lanes' tree steps run.  No lane threads (the evaluator is only ever called on the caller's
+// thread), no captured graph (the host is in the loop at every step), no persistent search kernel.
+static int ext_plies(az_engine *e, int max_steps)
+{
+    az_engine::Run &r = e->run;
+    const az_ext_evaluator &ev = e->ext.ev;
+    const int nnets = r.arena ? 2 : 1, nb = ply_batches(e);
+    hipStream_t s = e->stream;
+    struct Play { Lane *L; LaunchCtx lc; int item_base; };
+    int rc = AZ_OK;
+#define EXTCHECK(call)                                                                             \
+    do {                                                                                           \
+        hipError_t _r = (call);                                                                    \
+        if (_r != hipSuccess) {                                                                    \
+            rc = fail(e, AZ_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_r), __FILE__, __LINE__); \
+            ext_abort(e);                                                                          \
+            return rc;                                                                             \
+        }                                                                                          \
+    } while (0)
+    for (int step = 0; step < max_steps && active_slots(e) > 0; step++) {
+        std::vector<Play> play;
+        int item_base = 0;
+        for (Lane &L : e->lanes) {
+            if (L.active > 0) {
+                Play p{&L, ctx_of_impl(e, L), item_base};
+                p.lc.stream = s;
+                p.lc.synthetic = 0;                    // the tree step consumes rows, whatever az_config.eval_kind says
+                p.lc.d.B = L.cur;                      // the first L.cur slots: all of them, or after a compacting refill the active ones
+                p.lc.dv.B = L.cur * L.d.L;
+                play.push_back(p);
+            }
+            item_base += L.d.B * L.d.L;
+        }
+        for (Play &p : play) {
+            Lane &L = *p.L;
+            if (e->tapes) {       // the tapes of this ply must be on the device, as in lane_plies
+                hipEvent_t tev = nullptr;
+                const auto tw0 = std::chrono::steady_clock::now();
+                EXTCHECK(e->tapes->need(L.plies_played + e->tapes->ahead, &tev));
+                if (tev && hipEventQuery(tev) != hipSuccess) EXTCHECK(hipEventSynchronize(tev));
+                L.tape_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count();
+                if (tev) EXTCHECK(hipStreamWaitEvent(s, tev, 0));
+            }
+            hipLaunchKernelGGL(k_begin, dim3((p.lc.d.B + 255) / 256), dim3(256), 0, s, p.lc.d);
+        }
+        for (int idx = 0; idx < nb; idx++) {
+            for (int net = 0; net < nnets; net++) {
+                int first = 1, count = 0;
+                for (Play &p : play) {
+                    e->ops->ext_gather(p.lc, net, p.item_base, first, ev.capacity, ev.planes_dev, (int *)e->ext.map.p, (int *)e->ext.count.p);
+                    first = 0;
+                }
+                EXTCHECK(hipMemcpyAsync(&count, e->ext.count.p, 4, hipMemcpyDeviceToHost, s));
+                EXTCHECK(hipStreamSynchronize(s));
+                EXTCHECK(hipGetLastError());
+                if (count <= 0) continue;             // nothing waits for this net: no call
+                e->ext.requests += 1;
+                e->ext.items += count;
+                const int cb = ev.fn(ev.user, r.ext_net >= 0 ? r.ext_net : net, count);
+                if (cb) {
+                    rc = fail(e, AZ_ERR_INVALID, "the evaluator returned %d", cb);
+                    ext_abort(e);
+                    return rc;
+                }
+                for (Play &p : play) e->ops->ext_scatter(p.lc, p.item_base, count, (const int *)e->ext.map.p, ev.policy_dev, ev.value_dev);
+            }
+            for (Play &p : play) launch_step(e, p.lc, idx);
+        }
+        for (Play &p : play) {
+            Lane &L = *p.L;
+            e->ops->move(p.lc);
+            L.steps += nb;
+            L.plies += L.active;
+            if (r.preset) {
+                L.active = 0;
+            } else {
+                hipLaunchKernelGGL(k_refill, dim3(1), dim3(1024), 0, s, p.lc.d, 1 << 30, e->compact ? 1 : 0);
+                EXTCHECK(hipMemcpyAsync(&L.active, L.active_dev.p, 4, hipMemcpyDeviceToHost, s));
+                EXTCHECK(hipStreamSynchronize(s));     // k_refill writes the lane's own counter cell, read back before the next lane's
+            }
+        }
+        if (e->tapes) EXTCHECK(hipMemcpyAsync(e->tapes->h_done, e->g_nply.p, (size_t)r.num_games * 4, hipMemcpyDeviceToHost, s));
+        EXTCHECK(hipStreamSynchronize(s));
+        EXTCHECK(hipGetLastError());
+        for (Play &p : play) {
+            Lane &L = *p.L;
+            if (!r.preset && e->compact && !e->reuse && L.active > 0) L.cur = L.active;
+            L.plies_played++;
+        }
+    }
+#undef EXTCHECK
+    return AZ_OK;
+}
+
 // every lane plays up to max_steps plies, each on its own host thread (the caller's thread drives lane 0).  With
 // profiling on the lanes play one after another instead, so that the HIP events time each kernel alone on the GPU.
 static int episode_plies(az_engine *e, int max_steps)
@@ -1226,6 +1375,10 @@ static int episode_plies(az_engine *e, int max_steps)
     auto t0 = std::chrono::steady_clock::now();
     if (max_steps == 0) {
         // nothing to play (callers read the counters this way): no threads
+    } else if (r.ext) {
+        const int rc = ext_plies(e, max_steps);
+        r.c.seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return rc;
     } else if (sequential) {
         for (Lane &L : e->lanes)
             if (lane_plies(e, L, max_steps)) break;
@@ -1297,7 +1450,7 @@ static int read_counters(az_engine *e, az_counters &c)
     c.step_seconds = step_ms * 1e-3;
     c.root_evals = c.plies - reused;      // a retained root (subtree reuse) is not evaluated again
     c.records = c.plies;
-    c.trunk_boards = c.expansions + c.root_evals - c.cache_hits;     // evaluations the net kernels actually ran
+    c.trunk_boards = e->run.ext ? 0 : c.expansions + c.root_evals - c.cache_hits;     // evaluations the net kernels actually ran
     c.games = e->run.num_games;
     return AZ_OK;
 }
@@ -1340,7 +1493,8 @@ static int episode_end(az_engine *e, az_counters *out)
     for (int g = 0; g < r.num_games; g++) plies += e->h_nply[g];
     r.c.plies = r.c.records = plies;
     r.c.root_evals = plies - r.reused_roots;
-    r.c.trunk_boards = r.c.expansions + r.c.root_evals - r.c.cache_hits;
+    r.c.trunk_boards = r.ext ? 0 : r.c.expansions + r.c.root_evals - r.c.cache_hits;
+    if (r.ext) ext_restore(e);
     e->last = r.c;
     e->episode_games = r.num_games;
     e->have_episode = true;
@@ -1355,7 +1509,7 @@ static int run_episode(az_engine *e, const EpisodeSpec &sp, az_counters *out)
     int rc = episode_begin(e, sp);
     if (!rc) rc = episode_plies(e, 1 << 30);
     if (!rc) rc = episode_end(e, out);
-    if (rc) { e->run.open = false; stop_tapes(e); }
+    if (rc) { e->run.open = false; stop_tapes(e); ext_restore(e); }
     return rc;
 }
 
@@ -1438,7 +1592,7 @@ extern "C" int az_selfplay_end(az_engine *e, az_counters *out)
     if (!e) return AZ_ERR_INVALID;
     DEVICE_GUARD(e);
     const int rc = episode_end(e, out);
-    if (rc) { e->run.open = false; stop_tapes(e); }      // a failed episode is closed too: the engine stays usable
+    if (rc) { e->run.open = false; stop_tapes(e); ext_restore(e); }      // a failed episode is closed too: the engine stays usable
     return rc;
 }
 
@@ -1450,7 +1604,7 @@ extern "C" int az_selfplay(az_engine *e, const az_selfplay_args *a, az_counters 
     int rc = az_selfplay_begin(e, a);
     if (!rc) rc = episode_plies(e, 1 << 30);
     if (!rc) rc = episode_end(e, out);
-    if (rc) { e->run.open = false; stop_tapes(e); }
+    if (rc) { e->run.open = false; stop_tapes(e); ext_restore(e); }
     return rc;
 }
 
@@ -1724,6 +1878,7 @@ extern "C" int az_search(az_engine *e, int slot, const uint8_t *board, int playe
     HIPCHECK(e, hipStreamSynchronize(e->stream));
     EpisodeSpec sp;
     sp.num_games = 1; sp.max_plies = 0; sp.add_noise = noise != nullptr; sp.arena = false; sp.preset = true; sp.profile = false;
+    sp.ext_net = slot;
     // the arena flag only selects the net through s_player; a search with the baseline net uses slot 1 weights as slot 0
     PackedNet saved0 = e->net[0];
     const float *sv2w = L0.d.v2w[0], *sv2b = L0.d.v2b[0];
@@ -1795,7 +1950,7 @@ extern "C" int az_search_batch(az_engine *e, int slot, int count, const uint8_t 
         if (st >= nn) return fail(e, AZ_ERR_INVALID, "az_search_batch: position %d: no legal action", i);
         if (lasts[i] >= nn || (lasts[i] >= 0 && bd[lasts[i]] == 0)) return fail(e, AZ_ERR_INVALID, "az_search_batch: position %d: bad last action", i);
     }
-    if (e->cfg.eval_kind == AZ_EVAL_NET && !e->net[slot].loaded) return fail(e, AZ_ERR_NO_WEIGHTS, "weights slot %d not loaded", slot);
+    if (!e->ext.on && e->cfg.eval_kind == AZ_EVAL_NET && !e->net[slot].loaded) return fail(e, AZ_ERR_NO_WEIGHTS, "weights slot %d not loaded", slot);
     if (K > BATCH_MAX_LANES) return fail(e, AZ_ERR_INVALID, "az_search_batch: more than %d lanes", BATCH_MAX_LANES);
     DEVICE_GUARD(e);
     const int Wv = std::min(count, e->cfg.slots);           // positions per wave: everything below is sized by it, not by count
@@ -1839,7 +1994,9 @@ extern "C" int az_search_batch(az_engine *e, int slot, int count, const uint8_t 
     });
     EpisodeSpec sp;
     sp.max_plies = 0; sp.add_noise = noise != nullptr; sp.arena = false; sp.preset = true; sp.batch = true; sp.profile = false;
+    sp.ext_net = slot;
     az_counters total{};
+    int64_t ext_requests = 0, ext_items = 0;       // az_ext_stats reports the whole call, like the counters
     std::vector<double> hu(wn);
     for (int w0 = 0; w0 < count; w0 += Wv) {
         const int m = std::min(Wv, count - w0);
@@ -1888,6 +2045,7 @@ extern "C" int az_search_batch(az_engine *e, int slot, int count, const uint8_t 
         az_counters c{};
         if ((rc = run_episode(e, sp, &c))) return rc;
         add_counters(total, c);
+        ext_requests += e->ext.requests; ext_items += e->ext.items;
         // the lanes' streams are drained: every slot's root row and record into the compact staging, one copy per output
         e->ops->gather_roots(e->stream, bl, e->lanes[0].d, (const unsigned char *)e->bt_cells.p, visits ? (int *)e->bt_visits.p : nullptr, W ? (double *)e->bt_W.p : nullptr,
                              prior ? (float *)e->bt_prior.p : nullptr, pi ? (float *)e->bt_pi.p : nullptr,
@@ -1902,6 +2060,7 @@ extern "C" int az_search_batch(az_engine *e, int slot, int count, const uint8_t 
         HIPCHECK(e, hipGetLastError());
     }
     e->last = total;
+    if (e->ext.on) { e->ext.requests = ext_requests; e->ext.items = ext_items; }
     return AZ_OK;
 }
 
@@ -2092,6 +2251,7 @@ extern "C" int az_set_subtree_reuse(az_engine *e, int on)
     if (!e) return AZ_ERR_INVALID;
     if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_subtree_reuse: an episode is open");
     if (on && e->vl > 1) return fail(e, AZ_ERR_INVALID, "subtree reuse and virtual-loss batching cannot be combined");
+    if (on && e->ext.on) return fail(e, AZ_ERR_INVALID, "subtree reuse and the external evaluator cannot be combined");
     if (on && e->R > REUSE_MAX_ROWS)
         return fail(e, AZ_ERR_INVALID, "subtree reuse supports at most %d simulations per move", REUSE_MAX_ROWS - 1);
     e->reuse = on ? 1 : 0;
@@ -2183,6 +2343,7 @@ extern "C" int az_set_leaf_symmetry(az_engine *e, int on)
     if (!e) return AZ_ERR_INVALID;
     if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_leaf_symmetry: an episode is open");
     if (on && e->cfg.eval_kind != AZ_EVAL_NET) return fail(e, AZ_ERR_INVALID, "random-symmetry leaf evaluation needs the net evaluator");
+    if (on && e->ext.on) return fail(e, AZ_ERR_INVALID, "random-symmetry leaf evaluation and the external evaluator cannot be combined");
     e->leaf_symmetry = on ? 1 : 0;
     for (Lane &L : e->lanes) L.d.leaf_sym = on ? (int *)L.leaf_sym.p : nullptr;
     each_state(e, [&](DevState &d) { (void)d; });        // refresh the item views
@@ -2222,6 +2383,41 @@ extern "C" int az_emul_split(int mode, float x, uint16_t *parts)
 }
 
 extern "C" int az_get_persistent(const az_engine *e) { return e ? e->persist_gp : AZ_ERR_INVALID; }
+
+// ---- batched external evaluator ----
+extern "C" int az_ext_capacity(const az_engine *e) { return e ? e->cfg.slots * e->vl : AZ_ERR_INVALID; }
+
+extern "C" int az_get_external_evaluator(const az_engine *e) { return e ? (e->ext.on ? 1 : 0) : AZ_ERR_INVALID; }
+
+extern "C" int az_set_external_evaluator(az_engine *e, const az_ext_evaluator *ev)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_external_evaluator: an episode is open");
+    if (!ev) {
+        e->ext.on = false;
+        e->ext.ev = az_ext_evaluator{};
+        return AZ_OK;
+    }
+    if (!ev->planes_dev || !ev->policy_dev || !ev->value_dev || !ev->fn)
+        return fail(e, AZ_ERR_INVALID, "az_set_external_evaluator: null buffer or callback");
+    if ((uintptr_t)ev->planes_dev & 15u) return fail(e, AZ_ERR_INVALID, "az_set_external_evaluator: planes_dev must be 16-byte aligned");
+    if (e->reuse) return fail(e, AZ_ERR_INVALID, "subtree reuse and the external evaluator cannot be combined");
+    if (e->leaf_symmetry) return fail(e, AZ_ERR_INVALID, "random-symmetry leaf evaluation and the external evaluator cannot be combined");
+    if (ev->capacity < e->cfg.slots * e->vl)
+        return fail(e, AZ_ERR_INVALID, "az_set_external_evaluator: capacity %d is below az_ext_capacity = %d slots x %d leaves per batch",
+                    ev->capacity, e->cfg.slots, e->vl);
+    e->ext.ev = *ev;
+    e->ext.on = true;
+    return AZ_OK;
+}
+
+extern "C" int az_ext_stats(const az_engine *e, int64_t *requests, int64_t *items)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (requests) *requests = e->ext.requests;
+    if (items) *items = e->ext.items;
+    return AZ_OK;
+}
 
 // MCTS.run with the evaluator outside the engine: the policy_value_fn seam of mcts.py:87-93 for evaluators that are not
 // this engine's net (any callable in the reference).  The tree kernels run on the GPU as always; each of the

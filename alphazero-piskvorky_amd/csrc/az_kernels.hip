@@ -214,11 +214,22 @@ void build_positions(hipStream_t stream, int count, const unsigned char *cells, 
     dim3 g((count + 3) / 4), b(256);
     hipLaunchKernelGGL(k_build_positions<N>, g, b, 0, stream, count, cells, players, lasts, table);
 }
+
+void ext_gather(const LaunchCtx &c, int net, int item_base, int first, int capacity, float *planes, int *map, int *count)
+{
+    hipLaunchKernelGGL(k_ext_gather<N>, dim3(1), dim3(EXT_GATHER_THREADS), 0, c.stream, c.dv, net, item_base, first, capacity, planes, map, count);
+}
+
+void ext_scatter(const LaunchCtx &c, int item_base, int count, const int *map, const float *policy, const float *value)
+{
+    dim3 g((count + 3) / 4), b(256);
+    hipLaunchKernelGGL(k_ext_scatter<N>, g, b, 0, c.stream, c.dv, item_base, count, map, policy, value);
+}
 }   // namespace
 
 const SizeOps *AZ_CAT(az_size_ops_, AZ_N)()
 {
     static const SizeOps ops = {trunk, trunk_split, split_scratch_floats, fc, step, step_vl, root_cache, search_prepare, search, move, eval_tail_l,
-                                set_positions, gather_roots, build_positions};
+                                set_positions, gather_roots, build_positions, ext_gather, ext_scatter};
     return &ops;
 }

@@ -5,6 +5,7 @@
 #include "az_net_emul.h"
 #include "az_search.h"
 #include "az_batch.h"
+#include "az_ext.h"
 
 struct LaunchCtx {
     hipStream_t stream;
@@ -44,6 +45,10 @@ struct SizeOps {
     void (*gather_roots)(hipStream_t, const BatchLanes &, const DevState &, const unsigned char *cells, int *visits, double *W, float *prior, float *pi, int *action);
     // az_set_start_positions: `count` positions given as cells -> the table k_refill starts games from
     void (*build_positions)(hipStream_t, int count, const unsigned char *cells, const unsigned char *players, const short *lasts, StartPos *table);
+    // az_set_external_evaluator (az_ext.h), over the items of one lane (LaunchCtx.dv): the items waiting for net `net` appended
+    // to the request (first: a new request), and the evaluator's priors and values of `count` entries back into their rows
+    void (*ext_gather)(const LaunchCtx &, int net, int item_base, int first, int capacity, float *planes, int *map, int *count);
+    void (*ext_scatter)(const LaunchCtx &, int item_base, int count, const int *map, const float *policy, const float *value);
 };
 
 const SizeOps *az_size_ops(int n);     // nullptr for unsupported sizes

@@ -688,6 +688,14 @@ __device__ __forceinline__ void vl_leaf_eval(const DevState &d, size_t it, const
         for (int i = 0; i < G::CPL; i++) x[i] = lane + 64 * i < G::nn ? lg[lane + 64 * i] : 0.0f;
     }
     const float h_l = d.vhid[it * 64 + lane];
+    if (d.ext_eval) {
+        // the evaluator lives outside the engine (az_set_external_evaluator): the row holds the priors it returned, as they
+        // are, and the first hidden entry its value -- no softmax, no value head, no cache, no weights
+#pragma unroll
+        for (int i = 0; i < G::CPL; i++) P[i] = x[i];
+        v = __shfl(h_l, 0, 64);
+        return;
+    }
     const float w2_l = d.v2w[netid][lane];
     const float b2 = d.v2b[netid][0];
     if (d.cache && fresh) cache_insert<N>(d, lme, lopp, leaf_last, cache_net_key(netid, d.leaf_sym ? d.leaf_sym[it] : 0), lane, x, h_l);

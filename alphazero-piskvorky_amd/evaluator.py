@@ -8,7 +8,7 @@ import torch
 from . import constants as _c
 from . import parallel
 from ._capi import AZ_MAX_SIMULATIONS, Engine
-from .controller import device_index, model_kind
+from .controller import device_index, make_batch_policy_value_fn, merge_batch_evaluators, model_kind
 from .mcts import numpy_log_table
 from .self_play import check_resign
 
@@ -19,8 +19,12 @@ def temperature_schedule(move: int) -> float:
 
 class ModelEvaluator:
     def __init__(self, game_class=None, print_games=False, device=None, seed=None, virtual_loss=1, eval_cache=0,
-                 start_positions=None, resign: dict = None):
+                 start_positions=None, resign: dict = None, evaluators=None):
         self.game_class = game_class
+        # opt-in: the arena's evaluations leave the engine (az_set_external_evaluator).  A (candidate, baseline) pair of
+        # controller.BatchPolicyValueFn, one BatchPolicyValueFn that serves both nets by its `net` argument, or True = the
+        # two controllers' own torch modules, wrapped at every evaluate().
+        self.evaluators = evaluators if evaluators is None or evaluators is True else merge_batch_evaluators(evaluators)
         self.print_games = print_games
         self.device = device if device is not None else torch.device("cuda")
         self.seed = seed
@@ -56,8 +60,13 @@ class ModelEvaluator:
             self._engine.set_eval_cache(self.eval_cache)
             self._key = key
         eng = self._engine
-        eng.load_weights(candidate_controller.net.state_dict(), 0)
-        eng.load_weights(baseline_controller.net.state_dict(), 1)
+        if self.evaluators is None:
+            eng.load_weights(candidate_controller.net.state_dict(), 0)
+            eng.load_weights(baseline_controller.net.state_dict(), 1)
+        elif self.evaluators is True:
+            make_batch_policy_value_fn((candidate_controller.net, baseline_controller.net), self.device).attach(eng)
+        elif not eng.external_evaluator():
+            self.evaluators.attach(eng)
         T = np.array([float(temperature_schedule(m)) for m in range(n * n + 2)], dtype=np.float64)
         seed0 = self.seed if self.seed is not None else int(np.random.randint(0, 2 ** 31 - 1))
         if self.seed is None:

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import constants as _c
 from ._capi import AZ_MAX_SIMULATIONS, Engine
-from .controller import PolicyValueFn, device_index, model_kind, weights_version
+from .controller import BatchPolicyValueFn, PolicyValueFn, device_index, model_kind, weights_version
 
 
 def numpy_log_table(S):
@@ -23,7 +23,10 @@ class MCTS:
         # make_policy_value_fn(controller): the leaves are evaluated inside the HIP engine.  Any other callable keeps the
         # reference's plugin seam (mcts.py:87-93): the tree stays on the GPU and every evaluation is one host round trip
         # (az_search_callback) -- compatible, not fast.
-        self._external = not isinstance(policy_value_fn, PolicyValueFn)
+        # A BatchPolicyValueFn keeps the seam AND the speed: any torch net on the same GPU evaluates the leaves of all
+        # searches together on device buffers (az_set_external_evaluator), run() and run_many() through az_search_batch.
+        self._batched = isinstance(policy_value_fn, BatchPolicyValueFn)
+        self._external = not self._batched and not isinstance(policy_value_fn, PolicyValueFn)
         self.policy_value_fn = policy_value_fn
         self.num_simulations = num_simulations
         self.c_puct = c_puct
@@ -80,18 +83,43 @@ class MCTS:
         u = np.random.random_sample()
         if self._external:
             r = self._run_external(root_state, temperature, noise, u)
+        elif self._batched:
+            rb = self._eng_batch(n, root_state.win_length, 1).search_batch(
+                np.asarray(root_state.cells, np.uint8).reshape(1, n * n), [root_state.player_code()], [root_state.last_index()],
+                float(temperature), None if noise is None else [noise], [u])
+            r = {key: val[0] for key, val in rb.items()}
         else:
             eng = self._eng(n, root_state.win_length)
             r = eng.search(root_state.cells, root_state.player_code(), root_state.last_index(), float(temperature), noise, u)
-        a = r["action"]
+        a = int(r["action"])
         self.last_visits = r["N"].reshape(n, n)
         return r["pi"].reshape(n, n), (a // n, a % n)
 
     # ---- many positions at once (az_search_batch) ----
     BATCH_MIN_SLOTS, BATCH_MAX_SLOTS = 64, 1024
 
+    def _eng_batched_eval(self, n, k, count):
+        """the engine of a BatchPolicyValueFn: no weights, the evaluator attached; slots as _eng_batch"""
+        slots = 1 if count == 1 else self.BATCH_MIN_SLOTS
+        while slots < min(count, self.BATCH_MAX_SLOTS):
+            slots *= 2
+        eng = self._batch_engine
+        if eng is None or (eng.n, eng.k) != (n, k) or eng.slots < slots:
+            if eng is not None:
+                eng.close()
+            eng = self._batch_engine = Engine(n, k, self.num_simulations, slots, c_puct=self.c_puct,
+                                              dirichlet_alpha=self.dirichlet_alpha, dirichlet_weight=self.dirichlet_weight,
+                                              device=device_index(self.policy_value_fn.device),
+                                              log_table=numpy_log_table(self.num_simulations),
+                                              deep=self.num_simulations > AZ_MAX_SIMULATIONS)
+            eng.set_virtual_loss(self.virtual_loss)
+            self.policy_value_fn.attach(eng)
+        return eng
+
     def _eng_batch(self, n, k, count):
         """run_many's engine: slots = the next power of two >= count inside [64, 1024]; grows with a larger batch, never shrinks"""
+        if self._batched:
+            return self._eng_batched_eval(n, k, count)
         ctrl = self.policy_value_fn.controller
         slots = self.BATCH_MIN_SLOTS
         while slots < min(count, self.BATCH_MAX_SLOTS):

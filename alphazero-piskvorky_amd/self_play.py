@@ -8,7 +8,7 @@ import torch
 from . import constants as _c
 from . import parallel
 from ._capi import AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine, resign_permille
-from .controller import device_index, model_kind
+from .controller import BatchPolicyValueFn, device_index, model_kind
 from .mcts import numpy_log_table
 
 
@@ -65,8 +65,16 @@ class SelfPlayManager:
                  concurrent_games: int = None, augmentation: int = AZ_AUG_REFERENCE4, seed: int = None,
                  engines_per_gpu: int = None, subtree_reuse: bool = False, gather_to: int = None,
                  eval_cache: int = 0, virtual_loss: int = 1, trunk: str = "f32", leaf_symmetry: bool = False,
-                 start_positions=None, resign: dict = None):
+                 start_positions=None, resign: dict = None, evaluator: BatchPolicyValueFn = None):
         self.controller = controller
+        # opt-in: a controller.BatchPolicyValueFn evaluates every leaf instead of the engine's own net kernels (any torch
+        # net on the same GPU; az_set_external_evaluator).  Not with subtree_reuse or leaf_symmetry; eval_cache and trunk
+        # have no effect while it is set.
+        if evaluator is not None and not isinstance(evaluator, BatchPolicyValueFn):
+            raise TypeError("evaluator must be a controller.BatchPolicyValueFn (make_batch_policy_value_fn)")
+        if evaluator is not None and (subtree_reuse or leaf_symmetry):
+            raise ValueError("an external evaluator combines with neither subtree_reuse nor leaf_symmetry")
+        self.evaluator = evaluator
         self.device = device
         self.mcts_params = mcts_params or {"num_simulations": 100}
         self.temperature_schedule = temperature_schedule
@@ -103,6 +111,8 @@ class SelfPlayManager:
             self._engine.set_virtual_loss(self.virtual_loss)
             self._engine.set_eval_cache(self.eval_cache)
             self._engine.set_leaf_symmetry(self.leaf_symmetry)
+            if self.evaluator is not None:
+                self.evaluator.attach(self._engine)
             self._engine_key = key
         return self._engine
 
@@ -155,7 +165,8 @@ class SelfPlayManager:
             raise ValueError(f"subtree_reuse supports at most {REUSE_MAX_SIMULATIONS} simulations per move (got {sims}): "
                              "the retained tree is renumbered in a 1024-row table")
         eng = self._eng(n, k, max(1, min(self.concurrent_games, max(mine, 1))))
-        eng.load_weights(self.controller.net.state_dict(), 0)
+        if self.evaluator is None:
+            eng.load_weights(self.controller.net.state_dict(), 0)
         eng.set_subtree_reuse(self.subtree_reuse)
         if eng.trunk_mode() != self.trunk:
             eng.set_trunk_mode(self.trunk)

@@ -15,7 +15,7 @@ import torch
 
 from . import constants as C
 from . import parallel
-from .controller import NeuralNetworkController
+from .controller import NeuralNetworkController, make_batch_policy_value_fn
 from .evaluator import ModelEvaluator
 from .games import Gomoku
 from .net import GomokuNet
@@ -27,7 +27,7 @@ PROMOTION_THRESHOLD = 0.55          # promoter.py:19, strict ">" with draws coun
 
 
 def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=None, log=print, device_replay=False,
-        subtree_reuse=False, trunk="f32", eval_sims=None, start_positions=None, resign=None):
+        subtree_reuse=False, trunk="f32", eval_sims=None, start_positions=None, resign=None, torch_eval=False):
     """eval_sims: simulations per move in the arena (evaluator.py:53-62 takes NUM_EVAL_SIMULATIONS = 200 whatever the
     self-play count is; main() passes that constant); None = as many as self-play, which keeps small test runs short.
     device_replay=True keeps the examples on the GPU from the episode-end gather to the optimizer step (packed records
@@ -36,7 +36,10 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
     (Engine.set_start_positions); the arena keeps the empty board.
     resign: dict(threshold, min_ply, playout) for the self-play games (Engine.set_resign): a game ends as a loss of the mover
     once a ply's search value falls below -threshold; the share `playout` of the games plays on and gives the false-positive
-    rate that every episode's log line reports.  The arena, which decides promotions, plays every game to its end."""
+    rate that every episode's log line reports.  The arena, which decides promotions, plays every game to its end.
+    torch_eval=True: the searches of self-play and the arena are evaluated by the controllers' own torch modules on the GPU
+    (controller.make_batch_policy_value_fn, az_set_external_evaluator) instead of the engine's net kernels -- the loop a
+    changed net.py runs on before it has kernels of its own."""
     torch.manual_seed(seed)
     n = C.BOARD_SIZE
     rank, world = parallel.rank_world()
@@ -47,8 +50,10 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
     # train.py:95-104), rank 0 takes the optimizer steps and its weights are broadcast; only rank 0 writes model_dir
     manager = SelfPlayManager(candidate, device, mcts_params={"num_simulations": sims, "c_puct": C.SELF_PLAY_EXPLORATION_CONSTANT},
                               seed=seed, subtree_reuse=subtree_reuse, gather_to=0 if world > 1 else None, trunk=trunk,
-                              start_positions=start_positions, resign=resign)
-    evaluator = ModelEvaluator(game_class=Gomoku, print_games=False, device=device, seed=seed)
+                              start_positions=start_positions, resign=resign,
+                              evaluator=make_batch_policy_value_fn(candidate.net, device) if torch_eval else None)
+    evaluator = ModelEvaluator(game_class=Gomoku, print_games=False, device=device, seed=seed,
+                               evaluators=True if torch_eval else None)
     promoter = ModelPromoter(model_dir, evaluator, lambda: GomokuNet(board_size=n), device, threshold=PROMOTION_THRESHOLD)
     buffer = ReplayBuffer(capacity=C.BUFFER_CAPACITY)
     ring = None
@@ -122,6 +127,9 @@ def main():
     ap.add_argument("--resign-playout", type=float, default=None, metavar="SHARE",
                     help="share of the games that play on past the threshold, to measure its false-positive rate "
                          "(default 0.1 when --resign-threshold is given)")
+    ap.add_argument("--torch-eval", action="store_true",
+                    help="evaluate the searches with the controller's own torch module as a batched external evaluator "
+                         "(any net; no HIP trunk needed) instead of the engine's net kernels")
     a = ap.parse_args()
     resign = None
     if a.resign_threshold is not None:
@@ -144,7 +152,7 @@ def main():
         a.device = f"cuda:{local}"
     run(a.episodes, a.games, a.sims, a.eval_games, a.device, model_dir=a.model_dir, device_replay=a.device_replay,
         subtree_reuse=a.subtree_reuse, trunk=a.trunk, eval_sims=C.NUM_EVAL_SIMULATIONS, start_positions=start_positions,
-        resign=resign)
+        resign=resign, torch_eval=a.torch_eval)
     if world > 1:
         td.barrier()
         td.destroy_process_group()

@@ -165,6 +165,57 @@ int az_search_callback(az_engine *e, const uint8_t *board, int player, int last,
                        double u, az_eval_callback fn, void *user, float *pi, int32_t *action, int32_t *visits, double *W,
                        float *prior);
 
+/* Opt-in: batched external evaluator -- the same seam (mcts.py:87-93: ANY callable evaluates) for every game at once and on
+ * device buffers, so that self-play, the arena and batched search run at the tree kernels' speed with any net that lives on
+ * the same GPU (a torch module the engine has no kernels for).  While one is set, every net evaluation of az_selfplay*
+ * (begin / step / end included), az_arena, az_search and az_search_batch -- the root evaluations and the expanded leaves --
+ * goes through it; az_search_callback, az_net_eval and az_rules_replay ignore the setting.  No weights are needed
+ * (AZ_ERR_NO_WEIGHTS is not raised on this path) and az_config.eval_kind is overridden.
+ *
+ * One evaluation step (per ply 1 root step, then num_simulations steps, ceil(num_simulations / L) with virtual-loss
+ * batching): a gather kernel collects the pending items of ALL lanes that need net `net` into one compact request, in
+ * ascending (lane, slot, leaf-of-batch) order -- their encoded planes into planes_dev, an item -> slot map and the count stay
+ * on the device; the engine synchronises its stream; it calls fn(user, net, count) ON THE CALLING THREAD (no library host
+ * thread ever calls fn); a scatter kernel puts policy_dev / value_dev of the `count` entries back; the tree step runs.  A step
+ * with no pending item makes no call.  A duplicate pending leaf of a virtual-loss batch is handed out once.  There are no
+ * cache hits: the evaluation cache is bypassed, as for az_search_callback.  net: 0 in self-play; in the arena at most two
+ * requests per step, 0 (candidate) then 1 (baseline), each homogeneous; in az_search / az_search_batch the `slot` argument.
+ *
+ * Synchronisation is the evaluator's side of the contract: when fn is called the planes are complete in device memory (the
+ * engine has synchronised its stream); when fn RETURNS, policy_dev and value_dev of entries 0 .. count-1 must be complete in
+ * device memory -- an evaluator that works on a stream of its own (torch) synchronises that stream before it returns.  The
+ * engine does no cross-stream ordering of its own.  fn returns 0; anything else aborts the call with AZ_ERR_INVALID ("the
+ * evaluator returned %d"), the episode is closed, the slots are left idle and the engine stays usable.
+ *
+ * On this path all lanes of the engine advance together from the calling thread, kernel by kernel on one stream: no
+ * captured graph, no lane threads, and the persistent search kernel is never chosen (az_get_persistent == 0).  Slot refill
+ * and compaction between plies work as always.  Combines with virtual-loss batching (1..32: L leaves per game cut the round
+ * trips by L), start positions, resignation and the search value per record, deep engines, both step APIs, every board size
+ * and max_plies.  NOT with subtree reuse or random-symmetry leaf evaluation (out of scope here): AZ_ERR_INVALID, whichever
+ * is set first.  The emulated trunk mode and the evaluation cache setting are irrelevant while the evaluator is external and
+ * back in force once it is cleared (ev = NULL: the engine's own evaluator again).
+ *
+ * Errors: AZ_ERR_STATE while an episode is open; AZ_ERR_INVALID for a NULL buffer or fn, a planes_dev that is not 16-byte
+ * aligned, or capacity < az_ext_capacity(e) = slots x leaves per batch -- checked again when an episode begins, because
+ * az_set_virtual_loss may have changed L since.  Counters: the tree counters as always; trunk_launches, trunk_boards,
+ * nn_seconds and trunk_seconds are 0; az_ext_stats gives the requests made (calls of fn) and the items handed out in the
+ * last (or open) episode / call: items == expansions + root_evals, every evaluation is handed out exactly once. */
+typedef int (*az_eval_batch_fn)(void *user, int net, int count);   /* 0 = ok; anything else aborts the call */
+typedef struct {
+    float *planes_dev;   /* [capacity][4][n][n]  written by the engine: games.py:86-129 encode, plane 0 the side to move,
+                            1 the opponent, 2 the last move one-hot (all zero when there is none), 3 zeros; every float of
+                            entries 0 .. count-1, nothing behind them                                                */
+    float *policy_dev;   /* [capacity][n*n]      written by the evaluator: priors, used exactly as given (mcts.py:63;
+                            no mask, no renormalisation), as az_search_callback                                      */
+    float *value_dev;    /* [capacity]           written by the evaluator: value for the side to move of that item   */
+    int32_t capacity;    /* >= az_ext_capacity(e) = slots x leaves per batch (az_set_virtual_loss)                   */
+    az_eval_batch_fn fn; void *user;
+} az_ext_evaluator;
+int az_set_external_evaluator(az_engine *e, const az_ext_evaluator *ev);   /* NULL: the engine's own evaluator again */
+int az_get_external_evaluator(const az_engine *e);                        /* 1 / 0 */
+int az_ext_capacity(const az_engine *e);
+int az_ext_stats(const az_engine *e, int64_t *requests, int64_t *items);   /* of the last (or open) episode / call */
+
 /* ---- self-play episode: SelfPlayManager.generate_self_play + _worker (self_play.py:29-77,110-159) ----
  * Plays games with ids [0, num_games); game g draws its randomness from numpy-compatible
  * RandomState(seed0 + g) (dirichlet then one uniform per ply) unless a tape is given.
