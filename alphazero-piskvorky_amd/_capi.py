@@ -35,6 +35,7 @@ EXPORTS = [
     "az_set_start_positions", "az_get_start_positions",
     "az_set_resign", "az_get_resign", "az_selfplay_values", "az_selfplay_pack_values", "az_selfplay_resign_info",
     "az_resign_mix", "az_resign_exempt",
+    "az_set_playout_cap", "az_get_playout_cap", "az_playout_cap_full", "az_selfplay_sims", "az_selfplay_export_count",
     "az_set_external_evaluator", "az_get_external_evaluator", "az_ext_capacity", "az_ext_stats",
     "az_dist_unique_id", "az_dist_init", "az_dist_rank", "az_dist_world", "az_dist_counts", "az_dist_gather_records",
     "az_dist_allreduce_sum", "az_dist_broadcast",
@@ -149,6 +150,12 @@ def lib():
             L.az_resign_mix.argtypes = [C.c_uint32]
             L.az_resign_mix.restype = C.c_uint32
             L.az_resign_exempt.argtypes = [C.c_uint32, C.c_int]
+        if hasattr(L, "az_set_playout_cap"):
+            L.az_set_playout_cap.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+            L.az_get_playout_cap.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+            L.az_playout_cap_full.argtypes = [C.c_uint32, C.c_int, C.c_int]
+            L.az_selfplay_sims.argtypes = [C.c_void_p, C.c_void_p]
+            L.az_selfplay_export_count.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         if hasattr(L, "az_set_external_evaluator"):
             L.az_set_external_evaluator.argtypes = [C.c_void_p, C.POINTER(az_ext_evaluator)]
             L.az_get_external_evaluator.argtypes = [C.c_void_p]
@@ -211,6 +218,20 @@ def resign_permille(playout):
     if not 0.0 <= playout <= 1.0:
         raise ValueError(f"playout must be a share in [0, 1], got {playout}")
     return int(round(1000 * playout))
+
+
+def playout_cap_full(key, ply, permille):
+    """True when ply `ply` (absolute) of the game named key = low 32 bits of seed0 + g gets the full search under a playout
+    cap with `permille` full plies per thousand (az_playout_cap_full; needs no GPU)."""
+    return bool(lib().az_playout_cap_full(int(key) & 0xFFFFFFFF, int(ply), int(permille)))
+
+
+def playout_cap_permille(full):
+    """The share of full plies, as az_set_playout_cap takes it: round(1000 * full), 0 <= full <= 1."""
+    full = float(full)
+    if not 0.0 <= full <= 1.0:
+        raise ValueError(f"full must be a share in [0, 1], got {full}")
+    return int(round(1000 * full))
 
 
 class Engine:
@@ -624,6 +645,36 @@ class Engine:
         cross = np.full(G, -1, np.int32); ex = np.zeros(G, np.uint8)
         self._check(lib().az_selfplay_resign_info(self.h, _p(cross), _p(ex)), "az_selfplay_resign_info")
         return cross, ex.astype(bool)
+
+    # ---- playout cap randomisation ----
+    def set_playout_cap(self, fast_sims, full=0.25, export_full_only=True):
+        """Opt-in: only a pseudo-random share `full` of the self-play plies, named by game seed and ply, gets the full search
+        with root noise; the others are searched with fast_sims simulations and no noise.  With export_full_only the packed
+        export (pack_into, pack_values_into, the dist_* exchange) carries the records of full plies only.  fast_sims = 0
+        switches it off.  See include/az_engine.h."""
+        fast_sims = int(fast_sims)
+        if fast_sims < 0:
+            raise ValueError(f"fast_sims must be 0 (off) or 1..num_simulations, got {fast_sims}")
+        self._check(lib().az_set_playout_cap(self.h, fast_sims, playout_cap_permille(full), 1 if export_full_only else 0),
+                    "az_set_playout_cap")
+
+    def playout_cap(self):
+        """The setting in force: dict(fast_sims, full, export_full_only); fast_sims 0 = off."""
+        f, p, x = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(lib().az_get_playout_cap(self.h, C.byref(f), C.byref(p), C.byref(x)), "az_get_playout_cap")
+        return dict(fast_sims=int(f.value), full=int(p.value) / 1000.0, export_full_only=bool(x.value))
+
+    def sims(self):
+        """int32 simulations of every record of the last episode, in the order of records() (az_selfplay_sims)."""
+        s = np.zeros(self.last_records, np.int32)
+        self._check(lib().az_selfplay_sims(self.h, _p(s)), "az_selfplay_sims")
+        return s
+
+    def export_count(self):
+        """Records pack_into writes for the last episode: all of them, or the full plies' only (az_selfplay_export_count)."""
+        n = C.c_int64(0)
+        self._check(lib().az_selfplay_export_count(self.h, C.byref(n)), "az_selfplay_export_count")
+        return int(n.value)
 
     def set_trunk_mode(self, mode):
         """Opt-in: "bf16x3" / "f16x2" = fp32-emulating conv trunks on the 16-bit matrix cores (tolerance instead of

@@ -58,6 +58,7 @@ struct Lane {
     DevBuf board, s_game, s_ply, s_player, s_last, s_status, s_net, edges, rows_used, cnt, active_dev, carried;   // per slot
     DevBuf path, depth, leaf_kind, leaf, leaf_last, logits, vhid, pol_feat, dbg, scratch, it_status, it_net, leaf_sym;       // per evaluation item
     DevBuf inflight;               // per slot, deep engines with virtual-loss batching only: in-flight count of every edge
+    DevBuf budget, cp_board, cp_state;     // per slot, playout cap: the ply's simulation budget, and the staging of k_refill's partition
     // one ply (k_begin, (S+1) x {trunk, fc, step}, k_move) captured once as a hipGraph and replayed every ply:
     // 3(S+1)+2 launches (6(S+1)+2 with the split trunk) become one submission.  Indexed [split trunk][arena].
     struct PlyGraph {
@@ -67,6 +68,8 @@ struct Lane {
     std::vector<hipEvent_t> ev;    // profiling events
     // progress of the open episode
     int active = 0;                // active slots after the last refill
+    int n_full = 0;                // playout cap: how many of them search a FULL ply next (the first n_full after a compacting refill)
+    int refill_out[2] = {0, 0};    // what k_refill reports: active slots, FULL ones among them
     int cur = 0;                   // slots the next ply is launched over: all of them, or (after a compacting refill) the active ones
     int plies_played = 0;          // plies this lane has played in the open episode
     int64_t steps = 0, trunk_launches = 0, plies = 0;
@@ -126,6 +129,9 @@ struct az_engine {
     // az_set_resign: 0 = off
     double resign_thr = 0.0;
     int resign_min_ply = 0, resign_permille = 0;
+    // az_set_playout_cap: 0 = off; and what the last episode ran under (az_selfplay_sims and the export filter go by the hash)
+    int cap_fast = 0, cap_permille = 0, cap_export_full = 0;
+    int h_cap_fast = 0, h_cap_permille = 0, h_cap_export_full = 0;
     PackedNet net[2];
     az_counters last{};
     // running episode (az_selfplay_begin .. az_selfplay_end)
@@ -138,6 +144,7 @@ struct az_engine {
         az_counters c{};
         int64_t reused_roots = 0;
         unsigned game_key0 = 0;
+        int cap_fast = 0, cap_permille = 0, cap_export_full = 0;     // the playout cap of this episode (self-play only), 0 = off
         std::vector<int> start;    // ply every game starts at (az_set_start_positions); empty = 0 for all
     } run;
     bool profile = false;          // HIP events around every trunk / FC launch (az_set_profiling); lanes then play one after another
@@ -707,6 +714,7 @@ static int create_engine(const az_config *cfg, az_engine **out, bool deep)
         ALLOC(rows_used, B * 4);
         ALLOC(cnt, B * CNT_STRIDE * sizeof(unsigned long long)); ALLOC(active_dev, 16);
         ALLOC(carried, B * 4);
+        ALLOC(budget, B * 4); ALLOC(cp_board, B * 8 * sizeof(u64)); ALLOC(cp_state, B * 4 * 4);
 #undef ALLOC
         DevState &d = L.d;
         d.B = (int)B; d.R = e->R; d.S = cfg->num_simulations; d.k = cfg->win_length;
@@ -723,6 +731,8 @@ static int create_engine(const az_config *cfg, az_engine **out, bool deep)
         d.key_stride = 1; d.T_game = nullptr;
         d.start_pos = nullptr; d.start_count = 0; d.start_first = 0;
         d.resign_thr = 0.0; d.resign_min_ply = 0; d.resign_permille = 0; d.rec_value = nullptr; d.g_cross = nullptr;
+        d.cap_fast = 0; d.cap_permille = 0;
+        d.s_budget = (int *)L.budget.p; d.cp_board = (u64 *)L.cp_board.p; d.cp_state = (int *)L.cp_state.p;
         if (!rc) rc = alloc_items(e, L, 1);
     }
     if (!rc) rc = dev_alloc(e, e->next_game, 16);
@@ -792,7 +802,8 @@ extern "C" void az_destroy(az_engine *e)
     for (Lane &L : e->lanes) {
         DevBuf *all[] = {&L.board, &L.s_game, &L.s_ply, &L.s_player, &L.s_last, &L.s_status, &L.s_net, &L.edges, &L.rows_used,
                          &L.path, &L.depth, &L.leaf_kind, &L.leaf, &L.leaf_last, &L.logits, &L.vhid, &L.pol_feat, &L.cnt,
-                         &L.active_dev, &L.carried, &L.dbg, &L.scratch, &L.it_status, &L.it_net, &L.leaf_sym, &L.inflight};
+                         &L.active_dev, &L.carried, &L.dbg, &L.scratch, &L.it_status, &L.it_net, &L.leaf_sym, &L.inflight,
+                         &L.budget, &L.cp_board, &L.cp_state};
         for (DevBuf *b : all) dev_free(*b);
         for (hipEvent_t ev : L.ev) (void)hipEventDestroy(ev);
         for (int i = 0; i < 4; i++)
@@ -1040,10 +1051,14 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
         d.resign_thr = sp.preset ? 0.0 : e->resign_thr;
         d.resign_min_ply = sp.preset ? 0 : e->resign_min_ply;
         d.resign_permille = sp.preset || sp.arena ? 0 : e->resign_permille;
+        // the playout cap is for self-play games only: the arena and the preset searches run every ply in full
+        d.cap_fast = sp.preset || sp.arena ? 0 : e->cap_fast;
+        d.cap_permille = d.cap_fast ? e->cap_permille : 0;
     });
+    const bool capped = !sp.preset && !sp.arena && e->cap_fast > 0;
     // persistent search kernel: plain net or synthetic evaluator, the reference's sequential search, trees that fit into LDS
     e->persist_gp = 0;
-    if (e->persist_allowed && !ext && !e->vl_kernel && e->trunk_mode == AZ_TRUNK_F32) {
+    if (e->persist_allowed && !ext && !e->vl_kernel && !capped && e->trunk_mode == AZ_TRUNK_F32) {
         const int synth = e->cfg.eval_kind == AZ_EVAL_SYNTHETIC ? 1 : 0;
         const int S = e->cfg.num_simulations;
         if (!sp.arena && (!sp.preset || sp.batch) && e->ops->search_prepare(S, 2, synth, e->cfg.model)) e->persist_gp = 2;
@@ -1055,6 +1070,7 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
     r.preset = sp.preset; r.profile = sp.profile;
     r.ext = ext; r.ext_net = sp.ext_net;
     r.game_key0 = sp.game_key0;
+    if (capped) { r.cap_fast = e->cap_fast; r.cap_permille = e->cap_permille; r.cap_export_full = e->cap_export_full; }
     if (!sp.preset && e->start_count > 0) {
         r.start.resize(sp.num_games);
         for (int g = 0; g < sp.num_games; g++) {
@@ -1069,20 +1085,21 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
     const int K = (int)e->lanes.size();
     const int share = (sp.num_games + K - 1) / K;
     for (Lane &L : e->lanes) {
-        L.active = 0; L.cur = L.d.B; L.plies_played = 0; L.steps = L.trunk_launches = L.plies = 0;
+        L.active = 0; L.n_full = 0; L.refill_out[0] = L.refill_out[1] = 0; L.cur = L.d.B; L.plies_played = 0; L.steps = L.trunk_launches = L.plies = 0;
         L.trunk_ms = L.nn_ms = L.step_ms = 0.0; L.tape_wait_s = 0.0; L.rc = AZ_OK; L.err.clear();
         HIPCHECK(e, hipMemsetAsync(L.cnt.p, 0, L.cnt.bytes, L.stream));
         HIPCHECK(e, hipMemsetAsync(L.carried.p, 0xFF, L.carried.bytes, L.stream));      // -1: every slot starts from a fresh root
         if (!sp.preset) {
             HIPCHECK(e, hipMemsetAsync(L.s_status.p, 0, L.s_status.bytes, L.stream));
             hipLaunchKernelGGL(k_refill, dim3(1), dim3(1024), 0, L.stream, L.d, share, e->compact ? 1 : 0);
-            HIPCHECK(e, hipMemcpyAsync(&L.active, L.active_dev.p, 4, hipMemcpyDeviceToHost, L.stream));
+            HIPCHECK(e, hipMemcpyAsync(L.refill_out, L.active_dev.p, 8, hipMemcpyDeviceToHost, L.stream));
         } else {
             if (L.preset_m == 0) HIPCHECK(e, hipMemsetAsync(L.s_status.p, 0, L.s_status.bytes, L.stream));
             L.active = L.preset_m;
             if (sp.batch && L.preset_m > 0) L.cur = L.preset_m;
         }
         HIPCHECK(e, hipStreamSynchronize(L.stream));
+        if (!sp.preset) { L.active = L.refill_out[0]; L.n_full = L.refill_out[1]; }
         if (!sp.preset && e->compact && !e->reuse) L.cur = L.active;       // the active slots are the first L.active ones
     }
     r.open = true;
@@ -1092,7 +1109,17 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
 
 // Evaluation batches of one ply: the root's evaluation, then the simulations -- one per batch in the reference's
 // sequential loop (mcts.py:123-141), `vl` per batch with virtual-loss batching.
-static int ply_batches(const az_engine *e) { return 1 + (e->vl_kernel ? (e->cfg.num_simulations + e->vl - 1) / e->vl : e->cfg.num_simulations); }
+static int sims_batches(const az_engine *e, int sims) { return 1 + (e->vl_kernel ? (sims + e->vl - 1) / e->vl : sims); }
+static int ply_batches(const az_engine *e) { return sims_batches(e, e->cfg.num_simulations); }
+
+// The two phases of a ply under the playout cap (az_set_playout_cap).  Phase A, the batches a FAST search needs, runs over
+// every slot of the ply; phase B, the remaining batches of a FULL search, over the first slots_b ones only: the FULL slots
+// after a compacting refill, every slot without compaction (the budgets keep the FAST ones idle), none when no ply is FULL.
+struct CapPly {
+    int nb_a = 0, slots_b = 0;
+    bool split_b = false;          // the trunk choice of phase B, made for its own slot count
+};
+static int cap_batches(const az_engine *e, const CapPly *cap) { return !cap ? ply_batches(e) : (cap->slots_b > 0 ? ply_batches(e) : cap->nb_a); }
 
 // the tree kernel that consumes evaluation batch `idx` (0 = the root evaluation) and selects the leaves of batch idx + 1
 static void launch_step(const az_engine *e, const LaunchCtx &lc, int idx)
@@ -1110,7 +1137,8 @@ static void launch_step(const az_engine *e, const LaunchCtx &lc, int idx)
 // trunk, between trunk and FC, between FC and tree step and after the tree step; the persistent search kernel is timed as
 // a whole by the first four (it contains the trunk, the FC layers and the tree steps of every batch).  A failed event record
 // returns its error at once, with the rest of the ply not enqueued.
-static hipError_t launch_ply(az_engine *e, const LaunchCtx &lc, bool use_split, int nnets, bool net, const hipEvent_t *ev = nullptr)
+static hipError_t launch_ply(az_engine *e, const LaunchCtx &lc, bool use_split, int nnets, bool net, const hipEvent_t *ev = nullptr,
+                             const CapPly *cap = nullptr)
 {
     const DevState &d = lc.d;
     hipError_t rc = hipSuccess;
@@ -1124,16 +1152,20 @@ static hipError_t launch_ply(az_engine *e, const LaunchCtx &lc, bool use_split, 
         return rc;
     }
     if (net && d.cache) e->ops->root_cache(lc);
-    const int nb = ply_batches(e);
+    const int nb = cap_batches(e, cap), nb_a = cap ? cap->nb_a : nb;
+    LaunchCtx lcb = lc;                // phase B of a capped ply: the same kernels over fewer slots
+    if (cap) { lcb.d.B = cap->slots_b; lcb.dv.B = cap->slots_b * d.L; }
     for (int idx = 0; idx < nb; idx++) {
+        const LaunchCtx &c = idx < nb_a ? lc : lcb;
+        const bool split = idx < nb_a ? use_split : cap->split_b;
         if (net) {
             if (!record(4 * idx)) return rc;
-            for (int id = 0; id < nnets; id++) { if (use_split) e->ops->trunk_split(lc, id); else e->ops->trunk(lc, id); }
+            for (int id = 0; id < nnets; id++) { if (split) e->ops->trunk_split(c, id); else e->ops->trunk(c, id); }
             if (!record(4 * idx + 1)) return rc;
-            for (int id = 0; id < nnets; id++) e->ops->fc(lc, id);
+            for (int id = 0; id < nnets; id++) e->ops->fc(c, id);
             if (!record(4 * idx + 2)) return rc;
         }
-        launch_step(e, lc, idx);
+        launch_step(e, c, idx);
         if (!record(4 * idx + 3)) return rc;
     }
     e->ops->move(lc);
@@ -1200,32 +1232,42 @@ static int lane_plies(az_engine *e, Lane &L, int max_steps)
         }
         // a deep search (S > DEFAULT_MAX_S) is launched kernel by kernel instead of as one graph of ~3 (S + 1) nodes per ply
         // (measured, DESIGN 7b: 5x5 / 1024 slots / S = 1000 runs as fast eagerly as from the graph; a 15x15 search costs 2.5 %)
-        if (e->use_graph && !prof && full && S <= DEFAULT_MAX_S) {
+        // a capped ply (az_set_playout_cap) is launched kernel by kernel as well: the width of its second phase changes from
+        // ply to ply, and a graph would have to be captured for every width (DESIGN 7g has the cost of the eager launch)
+        CapPly cap;
+        if (r.cap_fast) {
+            cap.nb_a = sims_batches(e, r.cap_fast);
+            cap.slots_b = L.n_full == 0 ? 0 : (e->compact ? L.n_full : L.cur);
+            cap.split_b = e->split_max > 0 && L.scratch.p && L.n_full * e->vl <= e->split_max && e->trunk_mode == AZ_TRUNK_F32;
+        }
+        const int nrun = cap_batches(e, r.cap_fast ? &cap : nullptr);      // evaluation batches this ply launches
+        if (e->use_graph && !prof && full && S <= DEFAULT_MAX_S && !r.cap_fast) {
             hipGraphExec_t exec = nullptr;
             int rcg = ply_graph(e, L, lc, use_split, nnets, net, &exec);
             if (rcg) return rcg;
             HIPCHECK_L(L, hipGraphLaunch(exec, L.stream));
         } else {
-            HIPCHECK_L(L, launch_ply(e, lc, use_split, nnets, net, prof ? L.ev.data() : nullptr));
+            HIPCHECK_L(L, launch_ply(e, lc, use_split, nnets, net, prof ? L.ev.data() : nullptr, r.cap_fast ? &cap : nullptr));
         }
-        if (net) L.trunk_launches += e->persist_gp ? 1 : (int64_t)nnets * nbat;
-        L.steps += nbat;
+        if (net) L.trunk_launches += e->persist_gp ? 1 : (int64_t)nnets * nrun;
+        L.steps += nrun;
         L.plies += L.active;
         if (r.preset) {
             L.active = 0;
         } else {
             hipLaunchKernelGGL(k_refill, dim3(1), dim3(1024), 0, L.stream, d, 1 << 30, e->compact ? 1 : 0);
-            HIPCHECK_L(L, hipMemcpyAsync(&L.active, L.active_dev.p, 4, hipMemcpyDeviceToHost, L.stream));
+            HIPCHECK_L(L, hipMemcpyAsync(L.refill_out, L.active_dev.p, 8, hipMemcpyDeviceToHost, L.stream));
         }
         if (e->tapes)         // finished games need no further tape (g_nply only ever goes from 0 to the game's length, so
                               // a snapshot that lands late can only cost the producer some extra work)
             HIPCHECK_L(L, hipMemcpyAsync(e->tapes->h_done, e->g_nply.p, (size_t)r.num_games * 4, hipMemcpyDeviceToHost, L.stream));
         HIPCHECK_L(L, hipStreamSynchronize(L.stream));
         HIPCHECK_L(L, hipGetLastError());
+        if (!r.preset) { L.active = L.refill_out[0]; L.n_full = L.refill_out[1]; }
         if (!r.preset && e->compact && !e->reuse && L.active > 0) L.cur = L.active;
         L.plies_played++;
         if (prof) {
-            for (int i = 0; i < (e->persist_gp ? 1 : nbat); i++) {
+            for (int i = 0; i < (e->persist_gp ? 1 : nrun); i++) {
                 float a = 0.f, b = 0.f, c = 0.f;
                 HIPCHECK_L(L, hipEventElapsedTime(&a, L.ev[4 * i], L.ev[4 * i + 1]));
                 HIPCHECK_L(L, hipEventElapsedTime(&b, L.ev[4 * i + 1], L.ev[4 * i + 2]));
@@ -1469,6 +1511,7 @@ static int episode_end(az_engine *e, az_counters *out)
     HIPCHECK(e, az_memcpy(e->stream, e->h_cross.data(), e->g_cross.p, (size_t)r.num_games * 4, hipMemcpyDeviceToHost));
     e->h_key0 = r.game_key0;
     e->h_permille = r.arena || r.preset ? 0 : e->resign_permille;
+    e->h_cap_fast = r.cap_fast; e->h_cap_permille = r.cap_permille; e->h_cap_export_full = r.cap_export_full;
     if (r.preset) {
         e->h_nply.assign(r.num_games, 1);   // a preset search plays exactly one ply; the game itself is not finished by it
     } else {
@@ -1667,13 +1710,26 @@ extern "C" int az_selfplay_clear(az_engine *e)
 }
 
 // source index (game * nn + absolute ply) of every record of the last episode, game-major then ply, on the device
+// ... of every record the export carries: with az_set_playout_cap(export_full_only = 1) the records of FULL plies only
+static bool exported(const az_engine *e, int g, int ply)
+{
+    return !(e->h_cap_fast && e->h_cap_export_full) || az_playout_cap_full(e->h_key0 + (uint32_t)g, ply, e->h_cap_permille);
+}
 static int upload_src_index(az_engine *e, int64_t *records)
 {
     std::vector<int> src;
     for (int g = 0; g < e->episode_games; g++)
-        for (int m = 0; m < e->h_nply[g]; m++) src.push_back(g * e->nn + e->h_start[g] + m);
+        for (int m = 0; m < e->h_nply[g]; m++)
+            if (exported(e, g, e->h_start[g] + m)) src.push_back(g * e->nn + e->h_start[g] + m);
     *records = (int64_t)src.size();
     return src.empty() ? AZ_OK : upload(e, e->src_index, src.data(), src.size() * 4);
+}
+static int64_t export_records(const az_engine *e)
+{
+    int64_t n = 0;
+    for (int g = 0; g < e->episode_games; g++)
+        for (int m = 0; m < e->h_nply[g]; m++) n += exported(e, g, e->h_start[g] + m) ? 1 : 0;
+    return n;
 }
 
 extern "C" int64_t az_record_bytes(const az_engine *e) { return e ? record_bytes(e->nn) : 0; }
@@ -1750,6 +1806,59 @@ extern "C" int az_get_resign(const az_engine *e, double *threshold, int *min_ply
     if (threshold) *threshold = e->resign_thr;
     if (min_ply) *min_ply = e->resign_min_ply;
     if (playout_permille) *playout_permille = e->resign_permille;
+    return AZ_OK;
+}
+
+// ---- playout cap randomisation ----
+extern "C" int az_playout_cap_full(uint32_t key, int ply, int full_permille)
+{
+    return (int)(az_resign_mix(key ^ az_resign_mix((uint32_t)ply + 0x9E3779B9u)) % 1000u) < full_permille ? 1 : 0;
+}
+
+extern "C" int az_set_playout_cap(az_engine *e, int fast_sims, int full_permille, int export_full_only)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_playout_cap: an episode is open (az_selfplay_end first)");
+    if (fast_sims == 0) {
+        e->cap_fast = e->cap_permille = e->cap_export_full = 0;
+        return AZ_OK;
+    }
+    if (fast_sims < 1 || fast_sims > e->cfg.num_simulations || full_permille < 0 || full_permille > 1000 ||
+        (export_full_only != 0 && export_full_only != 1))
+        return fail(e, AZ_ERR_INVALID, "az_set_playout_cap: fast_sims %d (0 = off, else 1..%d), full_permille %d (0..1000), export_full_only %d (0 / 1)",
+                    fast_sims, e->cfg.num_simulations, full_permille, export_full_only);
+    if (e->reuse) return fail(e, AZ_ERR_INVALID, "the playout cap and subtree reuse cannot be combined");
+    if (e->ext.on) return fail(e, AZ_ERR_INVALID, "the playout cap and the external evaluator cannot be combined");
+    e->cap_fast = fast_sims; e->cap_permille = full_permille; e->cap_export_full = export_full_only;
+    return AZ_OK;
+}
+
+extern "C" int az_get_playout_cap(const az_engine *e, int *fast_sims, int *full_permille, int *export_full_only)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (fast_sims) *fast_sims = e->cap_fast;
+    if (full_permille) *full_permille = e->cap_permille;
+    if (export_full_only) *export_full_only = e->cap_export_full;
+    return AZ_OK;
+}
+
+extern "C" int az_selfplay_sims(az_engine *e, int32_t *sims)
+{
+    if (!e || !e->have_episode) return fail(e, AZ_ERR_STATE, "no episode has been run");
+    if (!sims) return fail(e, AZ_ERR_INVALID, "az_selfplay_sims: null buffer");
+    size_t r = 0;
+    for (int g = 0; g < e->episode_games; g++)
+        for (int m = 0; m < e->h_nply[g]; m++)
+            sims[r++] = e->h_cap_fast && !az_playout_cap_full(e->h_key0 + (uint32_t)g, e->h_start[g] + m, e->h_cap_permille)
+                            ? e->h_cap_fast : e->cfg.num_simulations;
+    return AZ_OK;
+}
+
+extern "C" int az_selfplay_export_count(az_engine *e, int64_t *records)
+{
+    if (!e || !e->have_episode) return fail(e, AZ_ERR_STATE, "no episode has been run");
+    if (!records) return fail(e, AZ_ERR_INVALID, "az_selfplay_export_count: null buffer");
+    *records = export_records(e);
     return AZ_OK;
 }
 
@@ -2252,6 +2361,7 @@ extern "C" int az_set_subtree_reuse(az_engine *e, int on)
     if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_subtree_reuse: an episode is open");
     if (on && e->vl > 1) return fail(e, AZ_ERR_INVALID, "subtree reuse and virtual-loss batching cannot be combined");
     if (on && e->ext.on) return fail(e, AZ_ERR_INVALID, "subtree reuse and the external evaluator cannot be combined");
+    if (on && e->cap_fast) return fail(e, AZ_ERR_INVALID, "the playout cap and subtree reuse cannot be combined");
     if (on && e->R > REUSE_MAX_ROWS)
         return fail(e, AZ_ERR_INVALID, "subtree reuse supports at most %d simulations per move", REUSE_MAX_ROWS - 1);
     e->reuse = on ? 1 : 0;
@@ -2402,6 +2512,7 @@ extern "C" int az_set_external_evaluator(az_engine *e, const az_ext_evaluator *e
         return fail(e, AZ_ERR_INVALID, "az_set_external_evaluator: null buffer or callback");
     if ((uintptr_t)ev->planes_dev & 15u) return fail(e, AZ_ERR_INVALID, "az_set_external_evaluator: planes_dev must be 16-byte aligned");
     if (e->reuse) return fail(e, AZ_ERR_INVALID, "subtree reuse and the external evaluator cannot be combined");
+    if (e->cap_fast) return fail(e, AZ_ERR_INVALID, "the playout cap and the external evaluator cannot be combined");
     if (e->leaf_symmetry) return fail(e, AZ_ERR_INVALID, "random-symmetry leaf evaluation and the external evaluator cannot be combined");
     if (ev->capacity < e->cfg.slots * e->vl)
         return fail(e, AZ_ERR_INVALID, "az_set_external_evaluator: capacity %d is below az_ext_capacity = %d slots x %d leaves per batch",
@@ -2465,7 +2576,7 @@ extern "C" int az_search_callback(az_engine *e, const uint8_t *board, int player
     // or a later az_selfplay / az_arena would feed raw logits to the tree step as priors
     each_state(e, [&](DevState &d) {
         d.max_plies = 0; d.add_noise = noise ? 1 : 0; d.arena = 0; d.total_games = 1; d.reuse = 0; d.game_key0 = 0;
-        d.cache = nullptr; d.ext_eval = 1;
+        d.cache = nullptr; d.ext_eval = 1; d.cap_fast = 0; d.cap_permille = 0;
     });
     struct Restore {
         az_engine *e; bool had_cache;
@@ -2648,9 +2759,7 @@ extern "C" int az_dist_world(const az_engine *e) { return e ? e->dist_world : AZ
 static int64_t dist_local_records(const az_engine *e)
 {
     if (!e->have_episode) return 0;
-    int64_t n = 0;
-    for (int g = 0; g < e->episode_games; g++) n += e->h_nply[g];
-    return n;
+    return export_records(e);      // what az_selfplay_pack writes
 }
 
 static int dist_counts(az_engine *e, const Rccl *R, std::vector<int64_t> &counts)

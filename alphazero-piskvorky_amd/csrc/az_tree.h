@@ -108,8 +108,19 @@ struct DevState {
     int *g_cross;          // [G] first crossing ply of the game, exempt games included; -1 = none
     int resign_min_ply;
     int resign_permille;   // game g is exempt (plays on) when fmix32(key(g)) % 1000 < resign_permille; no arena game is
+    // --- opt-in playout cap randomisation (az_set_playout_cap): self-play episodes only, cap_fast = 0 on every other path ---
+    int cap_fast;          // simulations of a FAST ply; 0 = off: nothing below is read or written
+    int cap_permille;      // ply p of game g is FULL when fmix32(key(g) ^ fmix32(p + 0x9E3779B9)) % 1000 < cap_permille
+    int *s_budget;         // [B] written by k_begin for the slot's ply: +S = a FULL ply, -cap_fast = a FAST one (no root noise)
+    u64 *cp_board;         // [B][8] / [B][4] staging of k_refill's full-first partition: board; game, ply, player, last
+    int *cp_state;
 };
 __device__ __forceinline__ int game_key(const DevState &d, int game) { return (int)(d.game_key0 + d.key_stride * (unsigned)game); }
+// az_set_playout_cap's rule, a function of the game's global name and the absolute ply only (the host's az_playout_cap_full)
+__device__ __forceinline__ bool cap_full_ply(const DevState &d, int game, int ply)
+{
+    return az_fmix32((unsigned)game_key(d, game) ^ az_fmix32((unsigned)ply + 0x9E3779B9u)) % 1000u < (unsigned)d.cap_permille;
+}
 
 template <int N>
 struct TreeGeo {
@@ -322,6 +333,7 @@ __global__ void k_begin(DevState d)
         lf[4 + i] = pl == 1 ? bd[4 + i] : bd[i];
     }
     d.leaf_last[it] = d.s_last[b];
+    if (d.cap_fast) d.s_budget[b] = cap_full_ply(d, d.s_game[b], d.s_ply[b]) ? d.S : -d.cap_fast;   // this ply's simulations
     if (d.leaf_sym) d.leaf_sym[it] = leaf_sym_of(game_key(d, d.s_game[b]), d.s_ply[b], 0);
     d.leaf_kind[it] = (d.reuse && d.carried[b] >= 0) ? LEAF_REUSE : LEAF_ROOT;
     d.depth[it] = 0;
@@ -369,6 +381,7 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
     const int game = d.s_game[bb];
     const int ply = d.s_ply[bb];
     const int carried = d.reuse ? d.carried[bb] : -1;
+    const int budget_raw = d.cap_fast ? d.s_budget[bb] : d.S;     // playout cap (kernel-argument test, uniform): < 0 = a FAST ply
     const Plane lme = pl_load(d.leaf + (size_t)bb * 8), lopp = pl_load(d.leaf + (size_t)bb * 8 + 4);
     const Plane bX = pl_load(d.board + (size_t)bb * 8), bO = pl_load(d.board + (size_t)bb * 8 + 4);
     unsigned *path = d.path + (size_t)bb * G::PATH;
@@ -396,6 +409,8 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
     __syncthreads();
     if (!inb || status != SLOT_ACTIVE) return;
     Edge *rows = d.edges + (size_t)b * d.R * G::RW;
+    const int budget = budget_raw < 0 ? -budget_raw : budget_raw;     // simulations of this slot's ply: S unless the cap says less
+    const bool root_noise = d.add_noise && budget_raw > 0;            // a FAST ply uses the priors as they are
 
     // ---------------- stage 1: evaluation -> expand -> backup ----------------
     if (kind == LEAF_REUSE) {
@@ -484,7 +499,7 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
                 v = az_tanhf(acc + (netid ? b2b : b2a));
                 }
             }
-            if (kind == LEAF_ROOT && d.add_noise) {
+            if (kind == LEAF_ROOT && root_noise) {
                 // mcts.py:113-116; float32 multiply, float64 add, float32 store
                 Plane occ;
 #pragma unroll
@@ -537,7 +552,8 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
     }
 
     // ---------------- stage 2: selection (mcts.py:124-129) ----------------
-    if (!do_select || rootN < carried) {          // a retained root tops its visits up to S: idle until simulation `carried`
+    // a retained root tops its visits up to S: idle until simulation `carried`; a slot whose budget is spent stays idle
+    if (!do_select || rootN < carried || rootN >= budget) {
         if (lane == 0) d.leaf_kind[b] = LEAF_NONE;
         return;
     }
@@ -744,6 +760,10 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
     // DEEP: in-flight counts of this slot's edges (L == 1 never has any: no array, nothing read or written)
     unsigned char *infl = DEEP && L > 1 ? inflight_arg(inflight...) + (size_t)b * d.R * G::RW : nullptr;
     const int pl = d.s_player[b], slast = d.s_last[b], netid = d.s_net[b], game = d.s_game[b], ply = d.s_ply[b];
+    // playout cap: this slot's simulations, < 0 = a FAST ply (no root noise); it selects min(L, budget - done) leaves per batch
+    const int budget_raw = d.cap_fast ? d.s_budget[b] : d.S;
+    const bool root_noise = d.add_noise && budget_raw > 0;
+    nb_next = min(nb_next, max((budget_raw < 0 ? -budget_raw : budget_raw) - sims_done, 0));
     const Plane bX = pl_load(d.board + (size_t)b * 8), bO = pl_load(d.board + (size_t)b * 8 + 4);
     float *vals = vals_lds[wv];
     unsigned *pend = pend_lds[wv];
@@ -764,7 +784,7 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
             const int leaf_last = d.leaf_last[it];
             float P[G::CPL];
             vl_leaf_eval<N, SYNTH>(d, it, lme, lopp, leaf_last, netid, kind_raw == kind, lane, P, v);
-            if (kind == LEAF_ROOT && d.add_noise) {
+            if (kind == LEAF_ROOT && root_noise) {
                 // mcts.py:113-116; float32 multiply, float64 add, float32 store
                 Plane occ;
 #pragma unroll
@@ -1179,12 +1199,13 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
 //           kernels can be launched over the active slots only.  A workgroup of a slot without a game would exit at once, but
 //           it still needs its LDS allocation to be dispatched and so queues behind the other lanes' working workgroups: in
 //           the tail of an episode that head-of-line blocking cost 30 % of a ply.  Invisible in the results (records go by
-//           game id).  Not with subtree reuse (the tree outlives the ply).
+//           game id).  Not with subtree reuse (the tree outlives the ply).  With the playout cap on (d.cap_fast) the order is
+//           active FULL, active FAST, idle, and d.active[1] = the number of FULL ones (written without compaction as well).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_refill(DevState d, int claim_cap, int compact)
 {
-    __shared__ int wsum[16];
-    __shared__ int base_s, take_s, cap_s, active_s, cbase_s;
+    __shared__ int wsum[16], wsum2[16];
+    __shared__ int base_s, take_s, cap_s, active_s, cbase_s, fbase_s;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (tid == 0) { cap_s = claim_cap; active_s = 0; }
     __syncthreads();
@@ -1245,6 +1266,62 @@ __global__ __launch_bounds__(1024) void k_refill(DevState d, int claim_cap, int 
         __syncthreads();
     }
     if (tid == 0) *d.active = active_s;
+    if (d.cap_fast) {
+        // Playout cap: the number of active slots whose coming ply is FULL goes next to *d.active, and the compaction is a
+        // stable three-way partition -- active FULL, active FAST, idle -- so that the second phase of the ply (the batches
+        // only a FULL search has) is launched over the first d.active[1] slots.  A FAST slot can move UP, onto a slot not
+        // yet read, so the partition goes through the staging arrays: FULL slots are placed there from the front and FAST
+        // slots from the back (entry d.B - 1 - j holds the j-th FAST slot; the two ends cannot meet, there are at most d.B
+        // active slots), which needs no count beforehand, and everything is copied back afterwards.  Without compaction
+        // only the count is made.
+        if (tid == 0) { cbase_s = 0; fbase_s = 0; }
+        __syncthreads();
+        for (int c0 = 0; c0 < d.B; c0 += 1024) {
+            const int b = c0 + tid;
+            const bool act = b < d.B && d.s_status[b] == SLOT_ACTIVE;
+            int g = 0, p = 0;
+            if (act) { g = d.s_game[b]; p = d.s_ply[b]; }
+            const bool fl = act && cap_full_ply(d, g, p), fs = act && !fl;
+            const u64 balf = __ballot(fl), bals = __ballot(fs);
+            const u64 below = (1ull << lane) - 1ull;
+            if (lane == 0) { wsum[wv] = __popcll(balf); wsum2[wv] = __popcll(bals); }
+            __syncthreads();
+            int offf = 0, totf = 0, offs = 0, tots = 0;
+            for (int w = 0; w < 16; w++) {
+                offf += w < wv ? wsum[w] : 0; totf += wsum[w];
+                offs += w < wv ? wsum2[w] : 0; tots += wsum2[w];
+            }
+            const int basef = cbase_s, bases = fbase_s;
+            __syncthreads();
+            if (act && compact) {
+                const int nb = fl ? basef + offf + __popcll(balf & below) : d.B - 1 - (bases + offs + __popcll(bals & below));
+                for (int q = 0; q < 8; q++) d.cp_board[(size_t)nb * 8 + q] = d.board[(size_t)b * 8 + q];
+                d.cp_state[nb * 4 + 0] = g; d.cp_state[nb * 4 + 1] = p;
+                d.cp_state[nb * 4 + 2] = d.s_player[b]; d.cp_state[nb * 4 + 3] = d.s_last[b];
+            }
+            if (tid == 0) { cbase_s = basef + totf; fbase_s = bases + tots; }
+            __syncthreads();
+        }
+        const int n_full = cbase_s, n_act = n_full + fbase_s;
+        if (tid == 0) d.active[1] = n_full;
+        if (!compact) return;
+        __threadfence_block();
+        __syncthreads();
+        for (int b = tid; b < d.B; b += 1024) {
+            if (b < n_act) {
+                const int src = b < n_full ? b : d.B - 1 - (b - n_full);
+                for (int q = 0; q < 8; q++) d.board[(size_t)b * 8 + q] = d.cp_board[(size_t)src * 8 + q];
+                d.s_game[b] = d.cp_state[src * 4 + 0]; d.s_ply[b] = d.cp_state[src * 4 + 1];
+                d.s_player[b] = d.cp_state[src * 4 + 2]; d.s_last[b] = d.cp_state[src * 4 + 3];
+                d.s_status[b] = SLOT_ACTIVE;
+                d.carried[b] = -1;
+            } else {
+                d.s_status[b] = SLOT_IDLE;
+                d.s_game[b] = -1;
+            }
+        }
+        return;
+    }
     if (!compact || d.reuse) return;
     if (tid == 0) cbase_s = 0;
     __syncthreads();

@@ -108,7 +108,10 @@ def gather_packed_records(engine, device, dst=None, force=False):
         engine.dist_gather_records(-1 if dst is None else int(dst), out.data_ptr() if receive else 0)
         return out[: total * engine.record_bytes], counts
     last_exchange = "torch.distributed" if _dist_on(force) else "local"
-    count = engine.last_records
+    # what pack_into writes: every record, or under a playout cap the full plies' only (an engine object without the filter
+    # exports all of them)
+    export_count = getattr(engine, "export_count", None)
+    count = export_count() if export_count is not None and engine.last_records else engine.last_records
     packed = torch.zeros(max(count, 1) * engine.record_bytes, dtype=torch.uint8, device=device)
     if count:
         engine.pack_into(packed.data_ptr())

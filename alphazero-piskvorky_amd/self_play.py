@@ -7,7 +7,7 @@ import torch
 
 from . import constants as _c
 from . import parallel
-from ._capi import AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine, resign_permille
+from ._capi import AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine, playout_cap_permille, resign_permille
 from .controller import BatchPolicyValueFn, device_index, model_kind
 from .mcts import numpy_log_table
 
@@ -59,13 +59,62 @@ def check_resign(resign):
     return out
 
 
+def check_playout_cap(cap, num_simulations=None):
+    """None, or the dict a seam takes: fast_sims >= 1 (at most num_simulations when that is given), optional share `full` of
+    the plies that get the full search (default 0.25) and train_on_fast (default False: only full plies become examples)."""
+    if cap is None:
+        return None
+    extra = set(cap) - {"fast_sims", "full", "train_on_fast"}
+    if extra or "fast_sims" not in cap:
+        raise ValueError(f"playout_cap takes fast_sims, full and train_on_fast (fast_sims is required), got {sorted(cap)}")
+    out = {"fast_sims": int(cap["fast_sims"]), "full": float(cap.get("full", 0.25)),
+           "train_on_fast": bool(cap.get("train_on_fast", False))}
+    if out["fast_sims"] < 1 or (num_simulations is not None and out["fast_sims"] > num_simulations):
+        raise ValueError(f"playout_cap fast_sims must be 1..num_simulations"
+                         f"{'' if num_simulations is None else f' = {num_simulations}'}, got {out['fast_sims']}")
+    playout_cap_permille(out["full"])
+    return out
+
+
+def _mix32(x):
+    """murmur3's 32-bit finaliser on a uint32 array (az_resign_mix)"""
+    x = np.asarray(x, np.uint32).copy()
+    x ^= x >> np.uint32(16); x *= np.uint32(0x85EBCA6B); x ^= x >> np.uint32(13); x *= np.uint32(0xC2B2AE35); x ^= x >> np.uint32(16)
+    return x
+
+
+def playout_cap_full_plies(seed0, nply, ply0, full) -> np.ndarray:
+    """bool per record, game-major then ply like Engine.records(): the ply was FULL by the rule of az_set_playout_cap
+    (az_playout_cap_full, restated on arrays).  seed0: seed of the first game; nply[g]: plies game g searched; ply0[g]: the
+    absolute ply it started at (0 from the empty board); full: the share of full plies."""
+    nply, ply0 = np.asarray(nply, np.int64), np.broadcast_to(np.asarray(ply0, np.int64), np.shape(nply))
+    game = np.repeat(np.arange(len(nply), dtype=np.int64), nply)
+    ply = np.arange(int(nply.sum()), dtype=np.int64) - np.repeat(np.cumsum(nply) - nply, nply) + ply0[game]
+    key = ((int(seed0) + game) & 0xFFFFFFFF).astype(np.uint32)
+    inner = _mix32(((ply + 0x9E3779B9) & 0xFFFFFFFF).astype(np.uint32))
+    return (_mix32(key ^ inner) % np.uint32(1000)).astype(np.int64) < playout_cap_permille(full)
+
+
+def playout_cap_stats(sims, full) -> dict:
+    """What an episode says about its playout cap: sims, the simulations of every record (Engine.sims()), and full, whether the
+    record's ply was FULL by the hash (playout_cap_full_plies; with fast_sims = num_simulations the simulations cannot tell).
+    The records, those of full plies -- what the export filter lets through --, and the mean simulations per ply (the cost of
+    the episode's searches, num_simulations without a cap)."""
+    sims, full = np.asarray(sims, np.int64), np.asarray(full, bool)
+    if sims.shape != full.shape or sims.ndim != 1:
+        raise ValueError("sims and full must be one-dimensional and of one length")
+    return {"records": int(len(sims)), "full_records": int(full.sum()),
+            "mean_sims_per_ply": float(sims.mean()) if len(sims) else None}
+
+
 class SelfPlayManager:
     def __init__(self, controller, device, mcts_params: dict = None,
                  temperature_schedule: Callable[[int], float] = default_temperature_schedule,
                  concurrent_games: int = None, augmentation: int = AZ_AUG_REFERENCE4, seed: int = None,
                  engines_per_gpu: int = None, subtree_reuse: bool = False, gather_to: int = None,
                  eval_cache: int = 0, virtual_loss: int = 1, trunk: str = "f32", leaf_symmetry: bool = False,
-                 start_positions=None, resign: dict = None, evaluator: BatchPolicyValueFn = None):
+                 start_positions=None, resign: dict = None, evaluator: BatchPolicyValueFn = None,
+                 playout_cap: dict = None):
         self.controller = controller
         # opt-in: a controller.BatchPolicyValueFn evaluates every leaf instead of the engine's own net kernels (any torch
         # net on the same GPU; az_set_external_evaluator).  Not with subtree_reuse or leaf_symmetry; eval_cache and trunk
@@ -77,6 +126,13 @@ class SelfPlayManager:
         self.evaluator = evaluator
         self.device = device
         self.mcts_params = mcts_params or {"num_simulations": 100}
+        # opt-in playout cap randomisation: dict(fast_sims, full=0.25, train_on_fast=False); only the share `full` of the plies
+        # gets num_simulations and root noise and becomes training examples, the rest is searched with fast_sims and moves
+        # the game along (az_set_playout_cap).  Not with subtree_reuse or an external evaluator.
+        self.playout_cap = check_playout_cap(playout_cap, self.mcts_params.get("num_simulations", 100))
+        if self.playout_cap is not None and (subtree_reuse or evaluator is not None):
+            raise ValueError("a playout cap combines with neither subtree_reuse nor an external evaluator")
+        self.last_playout_cap_stats = None    # playout_cap_stats() of this rank's games of the last episode (None while the cap is off)
         self.temperature_schedule = temperature_schedule
         self.concurrent_games = concurrent_games or _c.CONCURRENT_GAMES
         self.augmentation = augmentation      # 4 = the reference's rotations (self_play.py:94-108), 8 = full dihedral group, 1 = none
@@ -118,7 +174,8 @@ class SelfPlayManager:
 
     def generate_self_play(self, num_games: int, num_workers: int = None, flatten=False) -> list:
         """Returns list[(state f32 (4,n,n) CPU tensor, pi f32 (n,n) ndarray, z int)] in (game, ply, k) order
-        (self_play.py:110-159; num_workers / flatten are accepted and unused like the reference's `flatten`)."""
+        (self_play.py:110-159; num_workers / flatten are accepted and unused like the reference's `flatten`).  With a playout
+        cap: the examples of the full plies only, unless the cap says train_on_fast."""
         packed, total, eng, dev, n = self.generate_packed(num_games)
         aug = self.augmentation
         states = torch.empty((total * aug, 4, n, n), dtype=torch.float32, device=dev)
@@ -181,10 +238,25 @@ class SelfPlayManager:
         elif eng.resign()["threshold"]:
             eng.set_resign(0.0)
         self.last_resign_stats = None
+        self.playout_cap = check_playout_cap(self.playout_cap, sims)
+        if self.playout_cap is not None:
+            # the engine's export filter does the selection: the packed records below are the full plies' unless train_on_fast
+            eng.set_playout_cap(self.playout_cap["fast_sims"], self.playout_cap["full"],
+                                export_full_only=not self.playout_cap["train_on_fast"])
+        elif eng.playout_cap()["fast_sims"]:
+            eng.set_playout_cap(0)
+        self.last_playout_cap_stats = None
         if mine > 0:
             self.last_counters = eng.selfplay(mine, seed0=seed0 + lo, temperature_table=T)
             if self.resign is not None:
                 self.last_resign_stats = self._resign_stats(eng, lo, mine)
+            if self.playout_cap is not None:
+                ply0 = 0
+                if self.start_positions is not None:
+                    boards, players, _ = self.start_positions
+                    ply0 = (np.asarray(boards).reshape(len(players), -1) != 0).sum(axis=1)[(lo + np.arange(mine)) % len(players)]
+                full = playout_cap_full_plies(seed0 + lo, eng.games()[0], ply0, self.playout_cap["full"])
+                self.last_playout_cap_stats = playout_cap_stats(eng.sims(), full)
         else:
             eng.clear_episode()       # no games for this rank: it must not send the engine's previous episode again
         packed, counts = parallel.gather_packed_records(eng, dev, dst=self.gather_to)

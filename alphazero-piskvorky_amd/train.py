@@ -27,7 +27,8 @@ PROMOTION_THRESHOLD = 0.55          # promoter.py:19, strict ">" with draws coun
 
 
 def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=None, log=print, device_replay=False,
-        subtree_reuse=False, trunk="f32", eval_sims=None, start_positions=None, resign=None, torch_eval=False):
+        subtree_reuse=False, trunk="f32", eval_sims=None, start_positions=None, resign=None, torch_eval=False,
+        playout_cap=None):
     """eval_sims: simulations per move in the arena (evaluator.py:53-62 takes NUM_EVAL_SIMULATIONS = 200 whatever the
     self-play count is; main() passes that constant); None = as many as self-play, which keeps small test runs short.
     device_replay=True keeps the examples on the GPU from the episode-end gather to the optimizer step (packed records
@@ -37,6 +38,9 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
     resign: dict(threshold, min_ply, playout) for the self-play games (Engine.set_resign): a game ends as a loss of the mover
     once a ply's search value falls below -threshold; the share `playout` of the games plays on and gives the false-positive
     rate that every episode's log line reports.  The arena, which decides promotions, plays every game to its end.
+    playout_cap: dict(fast_sims, full) for the self-play games (Engine.set_playout_cap): only the share `full` of the plies gets
+    `sims` simulations with root noise and becomes examples; the rest is searched with fast_sims simulations.  With
+    device_replay the ring receives the engine's filtered export.  The arena and the promoter are untouched.
     torch_eval=True: the searches of self-play and the arena are evaluated by the controllers' own torch modules on the GPU
     (controller.make_batch_policy_value_fn, az_set_external_evaluator) instead of the engine's net kernels -- the loop a
     changed net.py runs on before it has kernels of its own."""
@@ -50,7 +54,7 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
     # train.py:95-104), rank 0 takes the optimizer steps and its weights are broadcast; only rank 0 writes model_dir
     manager = SelfPlayManager(candidate, device, mcts_params={"num_simulations": sims, "c_puct": C.SELF_PLAY_EXPLORATION_CONSTANT},
                               seed=seed, subtree_reuse=subtree_reuse, gather_to=0 if world > 1 else None, trunk=trunk,
-                              start_positions=start_positions, resign=resign,
+                              start_positions=start_positions, resign=resign, playout_cap=playout_cap,
                               evaluator=make_batch_policy_value_fn(candidate.net, device) if torch_eval else None)
     evaluator = ModelEvaluator(game_class=Gomoku, print_games=False, device=device, seed=seed,
                                evaluators=True if torch_eval else None)
@@ -97,6 +101,11 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
                 log(f"[train] episode {ep}: {rs['resigned']} of {rs['games']} games resigned; {rs['exempt']} played out, "
                     f"{rs['exempt_crossed']} of them crossed the threshold, {rs['false_positives']} of those did not lose: "
                     f"false-positive rate {'n/a' if fp is None else format(fp, '.1%')}")
+            ps = manager.last_playout_cap_stats
+            if ps is not None and ps["records"]:           # this rank's games
+                history[-1]["playout_cap"] = ps
+                log(f"[train] episode {ep}: {ps['full_records']} of {ps['records']} plies searched in full "
+                    f"({ps['full_records'] / ps['records']:.1%}), {ps['mean_sims_per_ply']:.1f} simulations per ply on average")
             log(f"[train] episode {ep}: {len(data)} examples, loss {'n/a' if loss is None else format(loss, '.4f')}, "
                 f"arena {metrics['wins']}/{metrics['losses']}/{metrics['draws']} -> {win_rate:.2%}"
                 f"{' (promoted)' if promoted else ''}, {history[-1]['seconds']:.1f}s")
@@ -127,6 +136,11 @@ def main():
     ap.add_argument("--resign-playout", type=float, default=None, metavar="SHARE",
                     help="share of the games that play on past the threshold, to measure its false-positive rate "
                          "(default 0.1 when --resign-threshold is given)")
+    ap.add_argument("--playout-cap-fast", type=int, default=None, metavar="F",
+                    help="playout cap randomisation: self-play plies outside the full share are searched with F simulations "
+                         "and no root noise, and give no examples")
+    ap.add_argument("--playout-cap-full", type=float, default=None, metavar="P",
+                    help="share of the self-play plies that get the full search (default 0.25 when --playout-cap-fast is given)")
     ap.add_argument("--torch-eval", action="store_true",
                     help="evaluate the searches with the controller's own torch module as a batched external evaluator "
                          "(any net; no HIP trunk needed) instead of the engine's net kernels")
@@ -137,6 +151,11 @@ def main():
                   "playout": 0.1 if a.resign_playout is None else a.resign_playout}
     elif a.resign_playout is not None or a.resign_min_ply:
         ap.error("--resign-min-ply and --resign-playout need --resign-threshold")
+    playout_cap = None
+    if a.playout_cap_fast is not None:
+        playout_cap = {"fast_sims": a.playout_cap_fast, "full": 0.25 if a.playout_cap_full is None else a.playout_cap_full}
+    elif a.playout_cap_full is not None:
+        ap.error("--playout-cap-full needs --playout-cap-fast")
     start_positions = None
     if a.start_positions:
         with np.load(a.start_positions) as z:
@@ -152,7 +171,7 @@ def main():
         a.device = f"cuda:{local}"
     run(a.episodes, a.games, a.sims, a.eval_games, a.device, model_dir=a.model_dir, device_replay=a.device_replay,
         subtree_reuse=a.subtree_reuse, trunk=a.trunk, eval_sims=C.NUM_EVAL_SIMULATIONS, start_positions=start_positions,
-        resign=resign, torch_eval=a.torch_eval)
+        resign=resign, torch_eval=a.torch_eval, playout_cap=playout_cap)
     if world > 1:
         td.barrier()
         td.destroy_process_group()

@@ -504,6 +504,50 @@ int az_selfplay_values(az_engine *e, float *values);
 int az_selfplay_pack_values(az_engine *e, float *values_dev);
 int az_selfplay_resign_info(az_engine *e, int32_t *cross_ply, uint8_t *exempt);
 
+/* Opt-in playout cap randomisation (KataGo, Wu 2019: only a random share of the plies gets the full search and serves as a
+ * policy target; the other plies are played with a small search that only moves the game along and feeds the outcome z).
+ *
+ * Rule.  az_set_playout_cap(fast_sims, full_permille, export_full_only).  fast_sims = 0 switches the cap off, which is the
+ * default; the other arguments are then ignored.  Otherwise 1 <= fast_sims <= num_simulations, 0 <= full_permille <= 1000
+ * and export_full_only in {0, 1}.  Ply p of game g is FULL when
+ *     az_resign_mix(key(g) ^ az_resign_mix((uint32_t)p + 0x9E3779B9u)) % 1000 < full_permille,
+ * p = the absolute ply (stones on the board, as everywhere), key(g) = the low 32 bits of seed0 + g, the global name of the
+ * game that the leaf-symmetry hash and the resignation exemption use: fullness does not depend on slots, lanes, ranks,
+ * compaction or refill order.  az_playout_cap_full(key, ply, full_permille) is the host-side helper (no GPU needed): 1 / 0.
+ *   A FULL ply is the search as without the cap: num_simulations simulations and the ply's root noise from the tape.
+ *   A FAST ply is the same search with fast_sims simulations and NO root noise: the priors are used as az_search(noise =
+ *   NULL) and the arena use them.  The ply's noise on the tape is generated and skipped: everything indexed by ply stays
+ *   where it is (the noise offsets, u[g][ply], the temperature table, explicit noise_tape / u_tape arguments).  pi, the
+ *   sampled action, the record, the search value W[a*] / N[a*], the resignation test and the terminal test are made exactly
+ *   as for any ply, from a root with fast_sims visits.
+ * So full_permille = 1000 is the episode with the cap off, byte for byte, and fast_sims = num_simulations differs from it
+ * only by the missing noise on the FAST plies.
+ * Applies to az_selfplay and az_selfplay_begin / _step / _end only; az_arena, az_search, az_search_batch,
+ * az_search_callback, az_net_eval and az_rules_replay ignore the setting.  Combines with virtual-loss batching (a slot
+ * selects min(L, budget - done) leaves per batch and none once done >= budget: what a search with num_simulations = budget
+ * does), the evaluation cache, leaf symmetry (evaluation index s + 1 is simulation s, as always), both nets, the synthetic
+ * evaluator, the emulated trunks, deep engines, start positions, resignation and max_plies.  Refused with AZ_ERR_INVALID,
+ * whichever is set first: subtree reuse (a retained root can already hold more than fast_sims visits) and the external
+ * evaluator.  While the cap is on the persistent search kernel is never chosen (az_get_persistent == 0).
+ * AZ_ERR_INVALID for arguments out of range (the previous setting is kept), AZ_ERR_STATE while an episode is open.
+ *
+ * Records.  Every ply, FAST or FULL, is a record as always and z is valid for all of them: az_selfplay_games, _records,
+ * _values and _resign_info are unchanged in order and count.  az_selfplay_sims returns the simulations of every record,
+ * game-major then ply, in exactly the order and count of az_selfplay_records (every entry num_simulations with the cap
+ * off); AZ_ERR_STATE without an episode.  The device keeps no per-record array for it: the host restates the rule above
+ * from the episode's seed0, each game's first ply and its length.
+ * Export.  With export_full_only = 1, az_selfplay_pack, az_selfplay_pack_values, az_dist_counts and
+ * az_dist_gather_records carry the records of FULL plies only, in their usual order; with 0 they carry every record and the
+ * caller filters by az_selfplay_sims.  az_selfplay_export_count returns how many records az_selfplay_pack writes, cap on or
+ * off.  The packed record format is unchanged.
+ * Counters.  simulations is the sum of the budgets actually run; root_evals, plies and records are as always; steps counts
+ * the evaluation batches actually launched per lane (a ply without a FULL slot launches only the FAST search's batches). */
+int az_playout_cap_full(uint32_t key, int ply, int full_permille);
+int az_set_playout_cap(az_engine *e, int fast_sims, int full_permille, int export_full_only);
+int az_get_playout_cap(const az_engine *e, int *fast_sims, int *full_permille, int *export_full_only);
+int az_selfplay_sims(az_engine *e, int32_t *sims);
+int az_selfplay_export_count(az_engine *e, int64_t *records);
+
 /* Opt-in: fp32-emulating conv trunks.  AZ_TRUNK_F32 (default) computes the net's forward (net.py:55-72) on the float32
  * matrix instruction in the build's canonical fp order: bit-identical to the oracle.  The other two run every conv but the
  * first (99 % of the net's arithmetic) and the 1x1 head convs on the 16 x faster 16-bit matrix instructions with split
