@@ -36,6 +36,7 @@ EXPORTS = [
     "az_set_resign", "az_get_resign", "az_selfplay_values", "az_selfplay_pack_values", "az_selfplay_resign_info",
     "az_resign_mix", "az_resign_exempt",
     "az_set_playout_cap", "az_get_playout_cap", "az_playout_cap_full", "az_selfplay_sims", "az_selfplay_export_count",
+    "az_set_forced_playouts", "az_get_forced_playouts", "az_forced_prune",
     "az_set_external_evaluator", "az_get_external_evaluator", "az_ext_capacity", "az_ext_stats",
     "az_dist_unique_id", "az_dist_init", "az_dist_rank", "az_dist_world", "az_dist_counts", "az_dist_gather_records",
     "az_dist_allreduce_sum", "az_dist_broadcast",
@@ -156,6 +157,11 @@ def lib():
             L.az_playout_cap_full.argtypes = [C.c_uint32, C.c_int, C.c_int]
             L.az_selfplay_sims.argtypes = [C.c_void_p, C.c_void_p]
             L.az_selfplay_export_count.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        if hasattr(L, "az_set_forced_playouts"):
+            L.az_set_forced_playouts.argtypes = [C.c_void_p, C.c_double, C.c_int]
+            L.az_get_forced_playouts.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
+            L.az_forced_prune.argtypes = [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.az_forced_prune.restype = C.c_int64
         if hasattr(L, "az_set_external_evaluator"):
             L.az_set_external_evaluator.argtypes = [C.c_void_p, C.POINTER(az_ext_evaluator)]
             L.az_get_external_evaluator.argtypes = [C.c_void_p]
@@ -232,6 +238,25 @@ def playout_cap_permille(full):
     if not 0.0 <= full <= 1.0:
         raise ValueError(f"full must be a share in [0, 1], got {full}")
     return int(round(1000 * full))
+
+
+FORCED_K_MAX = 16.0                                            # az_set_forced_playouts
+
+
+def forced_prune(k, c_puct, visits, W, prior):
+    """Policy target pruning of one root row (az_forced_prune; needs no GPU): visits int[count], W float64[count] and prior
+    float32[count] of the LEGAL children in row-major order -> (pruned counts int32[count], visits removed).  The most visited
+    child, the lowest on ties, keeps its count."""
+    visits = np.ascontiguousarray(visits, np.int32)
+    W = np.ascontiguousarray(W, np.float64)
+    prior = np.ascontiguousarray(prior, np.float32)
+    if not (visits.ndim == 1 and visits.shape == W.shape == prior.shape):
+        raise ValueError("forced_prune takes three one-dimensional arrays of one length")
+    out = np.zeros(len(visits), np.int32)
+    removed = int(lib().az_forced_prune(float(k), float(c_puct), len(visits), _p(visits), _p(W), _p(prior), _p(out)))
+    if removed < 0:
+        raise ValueError(f"az_forced_prune refused its arguments (k {k} in (0, {FORCED_K_MAX:g}], counts 0..65534 with at least one visit)")
+    return out, removed
 
 
 class Engine:
@@ -663,6 +688,19 @@ class Engine:
         f, p, x = C.c_int(0), C.c_int(0), C.c_int(0)
         self._check(lib().az_get_playout_cap(self.h, C.byref(f), C.byref(p), C.byref(x)), "az_get_playout_cap")
         return dict(fast_sims=int(f.value), full=int(p.value) / 1000.0, export_full_only=bool(x.value))
+
+    # ---- forced playouts and policy target pruning ----
+    def set_forced_playouts(self, k, prune=True):
+        """Opt-in (KataGo): at every noised root a child is selected regardless of its PUCT value while its visits squared stay
+        below k * prior * (simulations so far), and with `prune` pi and the sampled move are made from counts that take those
+        visits back unless the search confirmed them.  k = 0 switches it off; KataGo uses 2.  See include/az_engine.h."""
+        self._check(lib().az_set_forced_playouts(self.h, float(k), 1 if prune else 0), "az_set_forced_playouts")
+
+    def forced_playouts(self):
+        """The setting in force: dict(k, prune); k 0.0 = off."""
+        k, p = C.c_double(0.0), C.c_int(0)
+        self._check(lib().az_get_forced_playouts(self.h, C.byref(k), C.byref(p)), "az_get_forced_playouts")
+        return dict(k=float(k.value), prune=bool(p.value))
 
     def sims(self):
         """int32 simulations of every record of the last episode, in the order of records() (az_selfplay_sims)."""

@@ -132,6 +132,9 @@ struct az_engine {
     // az_set_playout_cap: 0 = off; and what the last episode ran under (az_selfplay_sims and the export filter go by the hash)
     int cap_fast = 0, cap_permille = 0, cap_export_full = 0;
     int h_cap_fast = 0, h_cap_permille = 0, h_cap_export_full = 0;
+    // az_set_forced_playouts: 0.0 = off
+    double forced_k = 0.0;
+    int forced_prune = 0;
     PackedNet net[2];
     az_counters last{};
     // running episode (az_selfplay_begin .. az_selfplay_end)
@@ -732,6 +735,7 @@ static int create_engine(const az_config *cfg, az_engine **out, bool deep)
         d.start_pos = nullptr; d.start_count = 0; d.start_first = 0;
         d.resign_thr = 0.0; d.resign_min_ply = 0; d.resign_permille = 0; d.rec_value = nullptr; d.g_cross = nullptr;
         d.cap_fast = 0; d.cap_permille = 0;
+        d.forced_k = 0.0; d.forced_prune = 0;
         d.s_budget = (int *)L.budget.p; d.cp_board = (u64 *)L.cp_board.p; d.cp_state = (int *)L.cp_state.p;
         if (!rc) rc = alloc_items(e, L, 1);
     }
@@ -1054,6 +1058,9 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
         // the playout cap is for self-play games only: the arena and the preset searches run every ply in full
         d.cap_fast = sp.preset || sp.arena ? 0 : e->cap_fast;
         d.cap_permille = d.cap_fast ? e->cap_permille : 0;
+        // forced playouts are for the searches whose root is noised (the arena's never is); k_step exempts the cap's FAST plies
+        d.forced_k = sp.add_noise && !sp.arena ? e->forced_k : 0.0;
+        d.forced_prune = d.forced_k > 0.0 ? e->forced_prune : 0;
     });
     const bool capped = !sp.preset && !sp.arena && e->cap_fast > 0;
     // persistent search kernel: plain net or synthetic evaluator, the reference's sequential search, trees that fit into LDS
@@ -1842,6 +1849,54 @@ extern "C" int az_get_playout_cap(const az_engine *e, int *fast_sims, int *full_
     return AZ_OK;
 }
 
+// ---- forced playouts and policy target pruning ----
+extern "C" int az_set_forced_playouts(az_engine *e, double k, int prune)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_forced_playouts: an episode is open (az_selfplay_end first)");
+    if (k == 0.0) {
+        e->forced_k = 0.0; e->forced_prune = 0;
+        return AZ_OK;
+    }
+    if (!(k > 0.0 && k <= 16.0) || (prune != 0 && prune != 1))
+        return fail(e, AZ_ERR_INVALID, "az_set_forced_playouts: k %g (0 = off, else in (0, 16]), prune %d (0 / 1)", k, prune);
+    if (e->reuse) return fail(e, AZ_ERR_INVALID, "forced playouts and subtree reuse cannot be combined");
+    e->forced_k = k; e->forced_prune = prune;
+    return AZ_OK;
+}
+
+extern "C" int az_get_forced_playouts(const az_engine *e, double *k, int *prune)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (k) *k = e->forced_k;
+    if (prune) *prune = e->forced_prune;
+    return AZ_OK;
+}
+
+// k_move's pruning pass on one root row of `count` legal children, with the functions the kernel uses (az_tree.h)
+extern "C" int64_t az_forced_prune(double k, double c_puct, int count, const int32_t *visits, const double *W, const float *prior, int32_t *out)
+{
+    if (!(k > 0.0 && k <= 16.0) || count < 1 || !visits || !W || !prior || !out) return -1;
+    int64_t total = 0;
+    int star = 0;
+    for (int c = 0; c < count; c++) {
+        if (visits[c] < 0 || visits[c] > 0xFFFF) return -1;
+        total += visits[c];
+        if (visits[c] > visits[star]) star = c;            // the most visited child, the lowest on ties
+    }
+    if (total < 1 || total > 0xFFFF) return -1;
+    const double sq = sqrt((double)total + 1e-8);           // the engine's table: np.sqrt(total + 1e-8)
+    const double target = forced_score(W[star] / (double)visits[star], c_puct, prior[star], sq, visits[star]);
+    int64_t removed = 0;
+    for (int c = 0; c < count; c++) {
+        out[c] = visits[c];
+        if (c != star && visits[c] > 0)
+            out[c] = forced_pruned(k, c_puct, W[c] / (double)visits[c], prior[c], visits[c], (int)total, sq, target);
+        removed += visits[c] - out[c];
+    }
+    return removed;
+}
+
 extern "C" int az_selfplay_sims(az_engine *e, int32_t *sims)
 {
     if (!e || !e->have_episode) return fail(e, AZ_ERR_STATE, "no episode has been run");
@@ -2362,6 +2417,7 @@ extern "C" int az_set_subtree_reuse(az_engine *e, int on)
     if (on && e->vl > 1) return fail(e, AZ_ERR_INVALID, "subtree reuse and virtual-loss batching cannot be combined");
     if (on && e->ext.on) return fail(e, AZ_ERR_INVALID, "subtree reuse and the external evaluator cannot be combined");
     if (on && e->cap_fast) return fail(e, AZ_ERR_INVALID, "the playout cap and subtree reuse cannot be combined");
+    if (on && e->forced_k > 0.0) return fail(e, AZ_ERR_INVALID, "forced playouts and subtree reuse cannot be combined");
     if (on && e->R > REUSE_MAX_ROWS)
         return fail(e, AZ_ERR_INVALID, "subtree reuse supports at most %d simulations per move", REUSE_MAX_ROWS - 1);
     e->reuse = on ? 1 : 0;
@@ -2577,6 +2633,7 @@ extern "C" int az_search_callback(az_engine *e, const uint8_t *board, int player
     each_state(e, [&](DevState &d) {
         d.max_plies = 0; d.add_noise = noise ? 1 : 0; d.arena = 0; d.total_games = 1; d.reuse = 0; d.game_key0 = 0;
         d.cache = nullptr; d.ext_eval = 1; d.cap_fast = 0; d.cap_permille = 0;
+        d.forced_k = noise ? e->forced_k : 0.0; d.forced_prune = d.forced_k > 0.0 ? e->forced_prune : 0;
     });
     struct Restore {
         az_engine *e; bool had_cache;

@@ -191,6 +191,7 @@ __device__ __forceinline__ void step_lds(const DevState &d, int b, int lane, Edg
     Plane me = pl == 1 ? bX : bO;
     Plane opp = pl == 1 ? bO : bX;
     int row = 0, npar = rootN, depth = 0, last = slast, out_kind = LEAF_NONE;
+    const bool forced = d.forced_k > 0.0 && d.add_noise;      // forced playouts (kernel-argument test, uniform): the noised root only
     for (;;) {
         Plane occ;
 #pragma unroll
@@ -202,6 +203,7 @@ __device__ __forceinline__ void step_lds(const DevState &d, int b, int lane, Edg
             Edge e = rows[row * PG::ROWE + lane];
             double Q = e.N ? e.W / (double)e.N : 0.0;         // mcts.py:80 Q = W/N (0.0 while unvisited)
             best = Q + ((d.c_puct * (double)e.P) * sq) / (double)(1 + (int)e.N);
+            if (forced && row == 0 && forced_child((double)(int)e.N, d.forced_k, e.P, rootN)) best = INFINITY;
             bi = lane; bN = e.N; bC = e.child;
         }
         ST_STAMP(16);                // one level: row read, PUCT scores

@@ -114,12 +114,49 @@ struct DevState {
     int *s_budget;         // [B] written by k_begin for the slot's ply: +S = a FULL ply, -cap_fast = a FAST one (no root noise)
     u64 *cp_board;         // [B][8] / [B][4] staging of k_refill's full-first partition: board; game, ply, player, last
     int *cp_state;
+    // --- opt-in forced playouts and policy target pruning (az_set_forced_playouts): noised roots only, 0.0 on every other path ---
+    double forced_k;       // root child c is forced while n_c^2 < forced_k * P[c] * (parent count); 0.0 = off: nothing new is executed
+    int forced_prune;      // k_move makes pi and the move from the pruned counts N' (the record's visits stay the raw ones)
 };
 __device__ __forceinline__ int game_key(const DevState &d, int game) { return (int)(d.game_key0 + d.key_stride * (unsigned)game); }
 // az_set_playout_cap's rule, a function of the game's global name and the absolute ply only (the host's az_playout_cap_full)
 __device__ __forceinline__ bool cap_full_ply(const DevState &d, int game, int ply)
 {
     return az_fmix32((unsigned)game_key(d, game) ^ az_fmix32((unsigned)ply + 0x9E3779B9u)) % 1000u < (unsigned)d.cap_permille;
+}
+
+// az_set_forced_playouts: a root child with n visits (in-flight ones included) is forced -- it scores +infinity instead of its
+// PUCT value -- while n^2 < (k P) total.  No sqrt: exact in float64, and a 16-bit count squared would overflow an int.
+__host__ __device__ __forceinline__ bool forced_child(double n, double k, float P, int total)
+{
+    return n * n < (k * (double)P) * (double)total;
+}
+
+// ... and policy target pruning, shared by k_move and the host's az_forced_prune.  score(c, m) = Q_c + ((c_puct P_c) sq) / (1 + m) is
+// the child's PUCT value had it m visits, Q_c held fixed; it is monotone non-increasing in m (correctly rounded division and
+// addition are monotone), so the smallest m of a range with score < target is found by bisection.
+__host__ __device__ __forceinline__ double forced_score(double Q, double c_puct, float P, double sq, int m)
+{
+    return Q + ((c_puct * (double)P) * sq) / (double)(1 + m);
+}
+// N' of one child other than a* with n > 0 visits: at most F = ceil(sqrt((k P) total)) of them -- what the forced rule could have
+// given it -- are taken back, down to the smallest count whose score is still below `target`; a child left with one is emptied
+__host__ __device__ inline int forced_pruned(double k, double c_puct, double Q, float P, int n, int total, double sq, double target)
+{
+    if (forced_score(Q, c_puct, P, sq, n) >= target) return n;
+    const double thr = (k * (double)P) * (double)total;
+    int lo = 0, hi = n;                                       // score(hi) < target holds
+    if (thr < (double)n * (double)n) {                        // else F >= n: every visit may go
+        int F = thr > 0.0 ? (int)sqrt(thr) : 0;               // a guess, then made exact: the smallest F >= 0 with F * F >= thr
+        while (F > 0 && (double)(F - 1) * (double)(F - 1) >= thr) F--;
+        while ((double)F * (double)F < thr) F++;
+        lo = n - F;
+    }
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (forced_score(Q, c_puct, P, sq, mid) < target) hi = mid; else lo = mid + 1;
+    }
+    return (lo == 1 && lo < n) ? 0 : lo;
 }
 
 template <int N>
@@ -561,6 +598,7 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
     Plane opp = pl == 1 ? bO : bX;
     int row = 0, npar = rootN, depth = 0, last = slast, out_kind = LEAF_NONE;
     double sq_next = DEEP ? d.sqrt_table[rootN] : 0.0;
+    const bool forced = d.forced_k > 0.0 && root_noise;       // forced playouts (kernel-argument test, uniform): the noised root only
     for (;;) {
         Plane occ;
 #pragma unroll
@@ -575,6 +613,7 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
                 Edge e = rows[(size_t)row * G::RW + j];
                 double Q = e.N ? e.W / (double)e.N : 0.0;     // mcts.py:80 Q = W/N (0.0 while unvisited)
                 double sc = Q + ((d.c_puct * (double)e.P) * sq) / (double)(1 + (int)e.N);
+                if (forced && row == 0 && forced_child((double)(int)e.N, d.forced_k, e.P, rootN)) sc = INFINITY;
                 if (bi < 0 || sc > best) { best = sc; bi = j; bN = e.N; bC = e.child; }
             }
         }
@@ -845,6 +884,7 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
 
     // ---------------- stage 2: select the next batch (mcts.py:124-129 with in-flight visits counted as losses) ----------------
     const Plane rme = pl == 1 ? bX : bO, ropp = pl == 1 ? bO : bX;
+    const bool forced = d.forced_k > 0.0 && root_noise;       // forced playouts (kernel-argument test, uniform): the noised root only
     for (int j = 0; j < L; j++) {
         const size_t it = it0 + j;
         if (j >= nb_next) {
@@ -874,6 +914,7 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
                     const double wvv = e.W - (double)fl;
                     double Q = nv ? wvv / (double)nv : 0.0;
                     double sc = Q + ((d.c_puct * (double)e.P) * sq) / (double)(1 + nv);
+                    if (forced && row == 0 && forced_child((double)nv, d.forced_k, e.P, sims_done + j)) sc = INFINITY;
                     if (bi < 0 || sc > best) { best = sc; bi = c; bN = nv; bC = e.child; }
                 }
             }
@@ -1002,6 +1043,38 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
         Nj[i] = legal[i] ? (int)root[j].N & nmask : 0;
         rank[i] = legal[i] ? j - pl_rank(occ, j) : 0;
     }
+    // a* = the most visited legal cell, the lowest cell on ties: one order-independent reduction of (N << 16 | 0xFFFF - cell); N fits
+    // 16 bits, a cell 8.  Every ply ends with at least one visit under the root, so N[a*] >= 1.
+    unsigned best = 0u;
+#pragma unroll
+    for (int i = 0; i < G::CPL; i++) {
+        const unsigned key = ((unsigned)Nj[i] << 16) | (unsigned)(0xFFFF - (lane + 64 * i));
+        if (legal[i] && key > best) best = key;
+    }
+    best = wave_max_u(best);
+    const int astar = best ? 0xFFFF - (int)(best & 0xFFFFu) : 0;      // an active slot always has a legal cell
+    // ---- policy target pruning (az_set_forced_playouts, noised roots only): pi and the move are made from Np, which takes the
+    // forced visits back from every child but a* as far as its PUCT score stays below a*'s; everything else keeps the raw Nj ----
+    int Np[G::CPL];
+#pragma unroll
+    for (int i = 0; i < G::CPL; i++) Np[i] = Nj[i];
+    if (d.forced_k > 0.0 && d.forced_prune && d.add_noise && (d.cap_fast ? d.s_budget[b] : 1) > 0) {
+        int tot = 0;
+#pragma unroll
+        for (int i = 0; i < G::CPL; i++) tot += Nj[i];
+        tot = wave_sum_i(tot);
+        const double sq = d.sqrt_table[tot];
+        const Edge es = root[astar];
+        const double target = forced_score(es.W / (double)(int)(best >> 16), d.c_puct, es.P, sq, (int)(best >> 16));
+#pragma unroll
+        for (int i = 0; i < G::CPL; i++) {
+            const int j = lane + 64 * i;
+            if (legal[i] && Nj[i] > 0 && j != astar) {
+                const Edge ec = root[j];
+                Np[i] = forced_pruned(d.forced_k, d.c_puct, ec.W / (double)Nj[i], ec.P, Nj[i], tot, sq, target);
+            }
+        }
+    }
     bool uniform = false;
     double s = 1.0;
     if (T <= 1e-7) {
@@ -1009,7 +1082,7 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
         float y[G::CPL], m = -INFINITY;
 #pragma unroll
         for (int i = 0; i < G::CPL; i++) {
-            y[i] = legal[i] ? d.log_table[Nj[i]] / 1e-7f : -INFINITY;
+            y[i] = legal[i] ? d.log_table[Np[i]] / 1e-7f : -INFINITY;
             m = fmaxf(m, y[i]);
         }
         m = wave_max_f(m);
@@ -1026,7 +1099,7 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
         double m = -INFINITY;
 #pragma unroll
         for (int i = 0; i < G::CPL; i++) {
-            e[i] = legal[i] ? (double)d.log_table[Nj[i]] / T : -INFINITY;
+            e[i] = legal[i] ? (double)d.log_table[Np[i]] / T : -INFINITY;
             m = e[i] > m ? e[i] : m;
         }
         m = wave_max_d(m);
@@ -1082,17 +1155,7 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
             d.rec_visits[ri * G::nn + j] = (unsigned short)Nj[i];
         }
     }
-    // ---- search value of the ply: v = W[a*] / N[a*], a* = the most visited legal cell, the lowest cell on ties ----
-    // one order-independent reduction of (N << 16 | 0xFFFF - cell): N fits 16 bits, a cell 8.  Every ply ends with at least
-    // one visit under the root, so N[a*] >= 1.
-    unsigned best = 0u;
-#pragma unroll
-    for (int i = 0; i < G::CPL; i++) {
-        const unsigned key = ((unsigned)Nj[i] << 16) | (unsigned)(0xFFFF - (lane + 64 * i));
-        if (legal[i] && key > best) best = key;
-    }
-    best = wave_max_u(best);
-    const int astar = best ? 0xFFFF - (int)(best & 0xFFFFu) : 0;      // an active slot always has a legal cell
+    // ---- search value of the ply: v = W[a*] / N[a*] of the raw counts (a* found above) ----
     const double v = root[astar].W / (double)(int)(best >> 16);
     // resignation (az_set_resign): the ply crosses below -threshold; an exempt game only notes it and plays on
     const bool crossed = d.resign_thr > 0.0 && ply >= d.resign_min_ply && v < -d.resign_thr;

@@ -7,7 +7,7 @@ them to the engine, so np.random.seed(s) reproduces the reference's choices."""
 import numpy as np
 
 from . import constants as _c
-from ._capi import AZ_MAX_SIMULATIONS, Engine
+from ._capi import AZ_MAX_SIMULATIONS, FORCED_K_MAX, Engine
 from .controller import BatchPolicyValueFn, PolicyValueFn, device_index, model_kind, weights_version
 
 
@@ -16,8 +16,23 @@ def numpy_log_table(S):
     return np.log(np.arange(S + 1, dtype=np.float32) + 1e-8).astype(np.float32)
 
 
+def check_forced_playouts(fp):
+    """None, or the dict a seam takes: k in (0, 16] (KataGo: 2) and optional prune (default True: pi and the move are made
+    from the pruned counts)."""
+    if fp is None:
+        return None
+    extra = set(fp) - {"k", "prune"}
+    if extra or "k" not in fp:
+        raise ValueError(f"forced_playouts takes k and prune (k is required), got {sorted(fp)}")
+    out = {"k": float(fp["k"]), "prune": bool(fp.get("prune", True))}
+    if not 0.0 < out["k"] <= FORCED_K_MAX:
+        raise ValueError(f"forced_playouts k must be in (0, {FORCED_K_MAX:g}], got {out['k']}")
+    return out
+
+
 class MCTS:
-    def __init__(self, policy_value_fn, num_simulations, c_puct, dirichlet_alpha=0.3, dirichlet_weight=0.25, virtual_loss=1):
+    def __init__(self, policy_value_fn, num_simulations, c_puct, dirichlet_alpha=0.3, dirichlet_weight=0.25, virtual_loss=1,
+                 forced_playouts=None):
         if not callable(policy_value_fn):
             raise TypeError("policy_value_fn must be callable: state -> (policy [n, n], value)")
         # make_policy_value_fn(controller): the leaves are evaluated inside the HIP engine.  Any other callable keeps the
@@ -33,16 +48,26 @@ class MCTS:
         self.dirichlet_alpha = dirichlet_alpha
         self.dirichlet_weight = dirichlet_weight
         self.virtual_loss = virtual_loss      # opt-in: leaves per evaluation batch (az_set_virtual_loss); 1 = the reference's loop
+        # opt-in: dict(k, prune=True), forced playouts and policy target pruning in the searches with add_root_noise
+        # (az_set_forced_playouts); the others are untouched
+        self.forced_playouts = check_forced_playouts(forced_playouts)
         self._engine = None
         self._version = None
         self._batch_engine = None             # run_many's own engine; run() and its one-slot engine are untouched by it
         self._batch_version = None
+
+    def _forced(self, eng):
+        """a new engine takes the searches' forced-playout setting"""
+        if self.forced_playouts is not None:
+            eng.set_forced_playouts(self.forced_playouts["k"], self.forced_playouts["prune"])
+        return eng
 
     def _eng_external(self, n, k):
         if self._engine is None or (self._engine.n, self._engine.k) != (n, k):
             self._engine = Engine(n, k, self.num_simulations, 1, c_puct=self.c_puct, dirichlet_alpha=self.dirichlet_alpha,
                                   dirichlet_weight=self.dirichlet_weight, log_table=numpy_log_table(self.num_simulations),
                                   deep=self.num_simulations > AZ_MAX_SIMULATIONS)
+            self._forced(self._engine)
         return self._engine
 
     def _run_external(self, root_state, temperature, noise, u):
@@ -67,6 +92,7 @@ class MCTS:
                                   device=device_index(ctrl.device), log_table=numpy_log_table(self.num_simulations),
                                   model=model_kind(ctrl.net), deep=self.num_simulations > AZ_MAX_SIMULATIONS)
             self._engine.set_virtual_loss(self.virtual_loss)
+            self._forced(self._engine)
             self._version = None
         ver = weights_version(ctrl.net)
         if ver != self._version:
@@ -113,6 +139,7 @@ class MCTS:
                                               log_table=numpy_log_table(self.num_simulations),
                                               deep=self.num_simulations > AZ_MAX_SIMULATIONS)
             eng.set_virtual_loss(self.virtual_loss)
+            self._forced(eng)
             self.policy_value_fn.attach(eng)
         return eng
 
@@ -133,6 +160,7 @@ class MCTS:
                                         device=device_index(ctrl.device), log_table=numpy_log_table(self.num_simulations),
                                         model=model_kind(ctrl.net), deep=self.num_simulations > AZ_MAX_SIMULATIONS)
             self._batch_engine.set_virtual_loss(self.virtual_loss)
+            self._forced(self._batch_engine)
             self._batch_version = None
         ver = weights_version(ctrl.net)
         if ver != self._batch_version:

@@ -9,7 +9,7 @@ from . import constants as _c
 from . import parallel
 from ._capi import AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine, playout_cap_permille, resign_permille
 from .controller import BatchPolicyValueFn, device_index, model_kind
-from .mcts import numpy_log_table
+from .mcts import check_forced_playouts, numpy_log_table
 
 
 def default_temperature_schedule(move: int) -> float:
@@ -114,7 +114,7 @@ class SelfPlayManager:
                  engines_per_gpu: int = None, subtree_reuse: bool = False, gather_to: int = None,
                  eval_cache: int = 0, virtual_loss: int = 1, trunk: str = "f32", leaf_symmetry: bool = False,
                  start_positions=None, resign: dict = None, evaluator: BatchPolicyValueFn = None,
-                 playout_cap: dict = None):
+                 playout_cap: dict = None, forced_playouts: dict = None):
         self.controller = controller
         # opt-in: a controller.BatchPolicyValueFn evaluates every leaf instead of the engine's own net kernels (any torch
         # net on the same GPU; az_set_external_evaluator).  Not with subtree_reuse or leaf_symmetry; eval_cache and trunk
@@ -133,6 +133,14 @@ class SelfPlayManager:
         if self.playout_cap is not None and (subtree_reuse or evaluator is not None):
             raise ValueError("a playout cap combines with neither subtree_reuse nor an external evaluator")
         self.last_playout_cap_stats = None    # playout_cap_stats() of this rank's games of the last episode (None while the cap is off)
+        # opt-in forced playouts and policy target pruning: dict(k, prune=True); every noised root (with a playout cap: the full
+        # plies') guarantees its children visits by the square root of their prior, and pi is made from the counts without
+        # them (az_set_forced_playouts).  Not with subtree_reuse.  The records keep the raw visits and neither W nor the
+        # priors, so the pruned share cannot be recomputed from them: the manager reports no statistics of it
+        # (tools/forced_playouts_gain.py measures it on searched positions).
+        self.forced_playouts = check_forced_playouts(forced_playouts)
+        if self.forced_playouts is not None and subtree_reuse:
+            raise ValueError("forced playouts do not combine with subtree_reuse")
         self.temperature_schedule = temperature_schedule
         self.concurrent_games = concurrent_games or _c.CONCURRENT_GAMES
         self.augmentation = augmentation      # 4 = the reference's rotations (self_play.py:94-108), 8 = full dihedral group, 1 = none
@@ -246,6 +254,11 @@ class SelfPlayManager:
         elif eng.playout_cap()["fast_sims"]:
             eng.set_playout_cap(0)
         self.last_playout_cap_stats = None
+        self.forced_playouts = check_forced_playouts(self.forced_playouts)
+        if self.forced_playouts is not None:
+            eng.set_forced_playouts(self.forced_playouts["k"], self.forced_playouts["prune"])
+        elif eng.forced_playouts()["k"]:
+            eng.set_forced_playouts(0.0)
         if mine > 0:
             self.last_counters = eng.selfplay(mine, seed0=seed0 + lo, temperature_table=T)
             if self.resign is not None:

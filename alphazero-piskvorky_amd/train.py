@@ -28,7 +28,7 @@ PROMOTION_THRESHOLD = 0.55          # promoter.py:19, strict ">" with draws coun
 
 def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=None, log=print, device_replay=False,
         subtree_reuse=False, trunk="f32", eval_sims=None, start_positions=None, resign=None, torch_eval=False,
-        playout_cap=None):
+        playout_cap=None, forced_playouts=None):
     """eval_sims: simulations per move in the arena (evaluator.py:53-62 takes NUM_EVAL_SIMULATIONS = 200 whatever the
     self-play count is; main() passes that constant); None = as many as self-play, which keeps small test runs short.
     device_replay=True keeps the examples on the GPU from the episode-end gather to the optimizer step (packed records
@@ -41,6 +41,9 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
     playout_cap: dict(fast_sims, full) for the self-play games (Engine.set_playout_cap): only the share `full` of the plies gets
     `sims` simulations with root noise and becomes examples; the rest is searched with fast_sims simulations.  With
     device_replay the ring receives the engine's filtered export.  The arena and the promoter are untouched.
+    forced_playouts: dict(k, prune) for the self-play games (Engine.set_forced_playouts): every noised root guarantees its
+    children visits by the square root of their prior, and with prune the policy target leaves those visits out again.  The
+    arena is untouched.
     torch_eval=True: the searches of self-play and the arena are evaluated by the controllers' own torch modules on the GPU
     (controller.make_batch_policy_value_fn, az_set_external_evaluator) instead of the engine's net kernels -- the loop a
     changed net.py runs on before it has kernels of its own."""
@@ -55,6 +58,7 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
     manager = SelfPlayManager(candidate, device, mcts_params={"num_simulations": sims, "c_puct": C.SELF_PLAY_EXPLORATION_CONSTANT},
                               seed=seed, subtree_reuse=subtree_reuse, gather_to=0 if world > 1 else None, trunk=trunk,
                               start_positions=start_positions, resign=resign, playout_cap=playout_cap,
+                              forced_playouts=forced_playouts,
                               evaluator=make_batch_policy_value_fn(candidate.net, device) if torch_eval else None)
     evaluator = ModelEvaluator(game_class=Gomoku, print_games=False, device=device, seed=seed,
                                evaluators=True if torch_eval else None)
@@ -141,6 +145,11 @@ def main():
                          "and no root noise, and give no examples")
     ap.add_argument("--playout-cap-full", type=float, default=None, metavar="P",
                     help="share of the self-play plies that get the full search (default 0.25 when --playout-cap-fast is given)")
+    ap.add_argument("--forced-playouts", type=float, default=None, metavar="K",
+                    help="forced playouts at the noised roots of self-play: a root child is searched while its visits squared "
+                         "are below K x prior x simulations so far (0 < K <= 16; KataGo uses 2), and the policy target is pruned")
+    ap.add_argument("--no-target-pruning", action="store_true",
+                    help="with --forced-playouts: keep the forced visits in the policy target")
     ap.add_argument("--torch-eval", action="store_true",
                     help="evaluate the searches with the controller's own torch module as a batched external evaluator "
                          "(any net; no HIP trunk needed) instead of the engine's net kernels")
@@ -156,6 +165,11 @@ def main():
         playout_cap = {"fast_sims": a.playout_cap_fast, "full": 0.25 if a.playout_cap_full is None else a.playout_cap_full}
     elif a.playout_cap_full is not None:
         ap.error("--playout-cap-full needs --playout-cap-fast")
+    forced_playouts = None
+    if a.forced_playouts is not None:
+        forced_playouts = {"k": a.forced_playouts, "prune": not a.no_target_pruning}
+    elif a.no_target_pruning:
+        ap.error("--no-target-pruning needs --forced-playouts")
     start_positions = None
     if a.start_positions:
         with np.load(a.start_positions) as z:
@@ -171,7 +185,7 @@ def main():
         a.device = f"cuda:{local}"
     run(a.episodes, a.games, a.sims, a.eval_games, a.device, model_dir=a.model_dir, device_replay=a.device_replay,
         subtree_reuse=a.subtree_reuse, trunk=a.trunk, eval_sims=C.NUM_EVAL_SIMULATIONS, start_positions=start_positions,
-        resign=resign, torch_eval=a.torch_eval, playout_cap=playout_cap)
+        resign=resign, torch_eval=a.torch_eval, playout_cap=playout_cap, forced_playouts=forced_playouts)
     if world > 1:
         td.barrier()
         td.destroy_process_group()

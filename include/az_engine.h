@@ -548,6 +548,42 @@ int az_get_playout_cap(const az_engine *e, int *fast_sims, int *full_permille, i
 int az_selfplay_sims(az_engine *e, int32_t *sims);
 int az_selfplay_export_count(az_engine *e, int64_t *records);
 
+/* Opt-in forced playouts and policy target pruning (KataGo, Wu 2019, section 3.2: every noised root child is guaranteed a
+ * number of visits that grows with the square root of its prior and of the search so far, and the policy target afterwards
+ * drops those visits again unless the search confirmed the move by its own PUCT logic).
+ *
+ * Rule.  az_set_forced_playouts(k, prune).  k = 0 switches the option off, which is the default; otherwise 0 < k <= 16
+ * (KataGo: 2) and prune in {0, 1}.  It applies in every search whose root priors receive Dirichlet noise, and only at that
+ * root: the self-play plies that are not FAST plies of the playout cap, and az_search / az_search_batch /
+ * az_search_callback with noise != NULL.  az_arena, FAST plies and searches without noise are untouched, byte for byte;
+ * below the root selection is unchanged.
+ *   Forced selection.  At the root a legal child c is forced when
+ *       (double)n * (double)n < (k * (double)P[c]) * (double)total,
+ *   P[c] = the noised float32 prior of the root edge, n = the visit count its PUCT value uses (N, or N + in-flight visits
+ *   under virtual-loss batching), total = the parent count the selection uses (the simulations finished so far; + j for item
+ *   j of a virtual-loss batch).  A forced child scores +infinity instead of its PUCT value, and the usual order rule -- the
+ *   first maximum in row-major order -- picks the lowest forced cell.  No square root is taken: the test is exact in float64.
+ *   Pruning (prune = 1, after the search).  total = the sum of the root children's visits, sq = sqrt(total + 1e-8) as the
+ *   selection uses it, c* = the most visited legal cell (the lowest on ties), score(c, m) = Q_c + ((c_puct * (double)P[c]) *
+ *   sq) / (double)(1 + m) with Q_c = W_c / N_c held fixed, target = score(c*, N_c*).  For every other legal child with
+ *   N_c > 0: F_c = the smallest integer m >= 0 with (double)m * m >= (k * (double)P[c]) * (double)total; lo = max(0, N_c -
+ *   F_c); N'_c = the smallest m in [lo, N_c] with score(c, m) < target, or N_c when score(c, N_c) >= target; and N'_c = 1 <
+ *   N_c becomes 0.  N'_c* = N_c*; children without visits keep 0.  pi and the sampled action are made from N' exactly as
+ *   they are made from N without the option.  Everything else stays on the raw counts: the record's visits, the visits / W /
+ *   prior outputs of the searches, the search value W[a*] / N[a*], the resignation test and the counters.
+ *   With prune = 0 only the forced selection is active.
+ * az_forced_prune(k, c_puct, count, visits, W, prior, out) restates the pruning on the host for one root row of `count` legal
+ * children (no GPU needed): it writes N' to out[0 .. count) and returns the number of visits removed, or -1 for a bad
+ * argument (k outside (0, 16], count < 1, a null pointer, a negative count, or no visit at all).
+ * Combines with virtual-loss batching, the evaluation cache, leaf symmetry, both nets, the emulated trunks, the synthetic
+ * evaluator, deep engines, the external evaluator, start positions, resignation, max_plies, the playout cap (FULL plies
+ * only get the rule) and the persistent search kernel, which stays in use.  Refused with AZ_ERR_INVALID, whichever is set
+ * first: subtree reuse (a retained root's carried visits were not made under the rule).
+ * AZ_ERR_INVALID for arguments out of range (the previous setting is kept), AZ_ERR_STATE while an episode is open. */
+int az_set_forced_playouts(az_engine *e, double k, int prune);
+int az_get_forced_playouts(const az_engine *e, double *k, int *prune);
+int64_t az_forced_prune(double k, double c_puct, int count, const int32_t *visits, const double *W, const float *prior, int32_t *out);
+
 /* Opt-in: fp32-emulating conv trunks.  AZ_TRUNK_F32 (default) computes the net's forward (net.py:55-72) on the float32
  * matrix instruction in the build's canonical fp order: bit-identical to the oracle.  The other two run every conv but the
  * first (99 % of the net's arithmetic) and the 1x1 head convs on the 16 x faster 16-bit matrix instructions with split
