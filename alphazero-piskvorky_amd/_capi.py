@@ -37,6 +37,7 @@ EXPORTS = [
     "az_resign_mix", "az_resign_exempt",
     "az_set_playout_cap", "az_get_playout_cap", "az_playout_cap_full", "az_selfplay_sims", "az_selfplay_export_count",
     "az_set_forced_playouts", "az_get_forced_playouts", "az_forced_prune",
+    "az_set_gumbel", "az_get_gumbel", "az_gumbel_schedule", "az_gumbel_target", "az_gumbel_vmix", "az_rng_selfplay_tape_gumbel",
     "az_set_external_evaluator", "az_get_external_evaluator", "az_ext_capacity", "az_ext_stats",
     "az_dist_unique_id", "az_dist_init", "az_dist_rank", "az_dist_world", "az_dist_counts", "az_dist_gather_records",
     "az_dist_allreduce_sum", "az_dist_broadcast",
@@ -162,6 +163,15 @@ def lib():
             L.az_get_forced_playouts.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
             L.az_forced_prune.argtypes = [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.az_forced_prune.restype = C.c_int64
+        if hasattr(L, "az_set_gumbel"):
+            L.az_set_gumbel.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
+            L.az_get_gumbel.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+            L.az_gumbel_schedule.argtypes = [C.c_int, C.c_int, C.c_void_p]
+            L.az_gumbel_target.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_double,
+                                           C.c_double, C.c_void_p, C.POINTER(C.c_int32)]
+            L.az_gumbel_vmix.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]
+            L.az_gumbel_vmix.restype = C.c_double
+            L.az_rng_selfplay_tape_gumbel.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         if hasattr(L, "az_set_external_evaluator"):
             L.az_set_external_evaluator.argtypes = [C.c_void_p, C.POINTER(az_ext_evaluator)]
             L.az_get_external_evaluator.argtypes = [C.c_void_p]
@@ -257,6 +267,63 @@ def forced_prune(k, c_puct, visits, W, prior):
     if removed < 0:
         raise ValueError(f"az_forced_prune refused its arguments (k {k} in (0, {FORCED_K_MAX:g}], counts 0..65534 with at least one visit)")
     return out, removed
+
+
+GUMBEL_M_MAX = 64                                              # az_set_gumbel: m <= min(n * n, 64)
+GUMBEL_DEFAULTS = dict(m=16, c_visit=50.0, c_scale=1.0)
+
+
+def selfplay_tape_gumbel(seed, n, max_plies=0):
+    """One game's tape under the Gumbel root search (az_rng_selfplay_tape_gumbel; needs no GPU): per ply p, n * n - p draws of
+    RandomState(seed).gumbel() then one uniform -> (noise, u) in rng_selfplay_tape's layout."""
+    nn = n * n
+    plies = max_plies if 0 < max_plies < nn else nn
+    noise = np.zeros(sum(nn - m for m in range(plies)), np.float64)
+    u = np.zeros(nn, np.float64)
+    rc = lib().az_rng_selfplay_tape_gumbel(int(seed), n, int(max_plies), _p(noise), _p(u))
+    if rc:
+        raise AzError(f"az_rng_selfplay_tape_gumbel failed ({rc})")
+    return noise, u[:plies]
+
+
+def gumbel_schedule(k, S):
+    """The sequential-halving schedule of k candidates over S simulations (az_gumbel_schedule; needs no GPU): int32[S], entry t =
+    the visit count a root child must have to be selectable at simulation t."""
+    out = np.zeros(int(S), np.int32)
+    if lib().az_gumbel_schedule(int(k), int(S), _p(out)):
+        raise ValueError(f"az_gumbel_schedule refused its arguments (k {k} >= 0, S {S} in 1..{AZ_DEEP_MAX_SIMULATIONS})")
+    return out
+
+
+def gumbel_target(logits, g, visits, W, prior, root_value, c_visit=50.0, c_scale=1.0):
+    """Move and policy target of one Gumbel root row (az_gumbel_target; needs no GPU): logits float32, g float64, visits int, W
+    float64 and prior float32 of the LEGAL children in row-major order, root_value the root's float32 value ->
+    (pi float32[count], index of the chosen child)."""
+    logits = np.ascontiguousarray(logits, np.float32)
+    g = np.ascontiguousarray(g, np.float64)
+    visits = np.ascontiguousarray(visits, np.int32)
+    W = np.ascontiguousarray(W, np.float64)
+    prior = np.ascontiguousarray(prior, np.float32)
+    if not (logits.ndim == 1 and logits.shape == g.shape == visits.shape == W.shape == prior.shape):
+        raise ValueError("gumbel_target takes five one-dimensional arrays of one length")
+    pi = np.zeros(len(visits), np.float32)
+    a = C.c_int32(-1)
+    rc = lib().az_gumbel_target(len(visits), _p(logits), _p(g), _p(visits), _p(W), _p(prior), C.c_float(float(root_value)),
+                                float(c_visit), float(c_scale), _p(pi), C.byref(a))
+    if rc:
+        raise ValueError("az_gumbel_target refused its arguments (1..225 children, counts 0..65535 with at least one visit, "
+                         "c_visit >= 0 and c_scale > 0, finite)")
+    return pi, int(a.value)
+
+
+def gumbel_vmix(visits, W, prior, root_value):
+    """v_mix of one Gumbel root row as az_gumbel_target forms it (az_gumbel_vmix; needs no GPU)."""
+    visits = np.ascontiguousarray(visits, np.int32)
+    W = np.ascontiguousarray(W, np.float64)
+    prior = np.ascontiguousarray(prior, np.float32)
+    if not (visits.ndim == 1 and visits.shape == W.shape == prior.shape):
+        raise ValueError("gumbel_vmix takes three one-dimensional arrays of one length")
+    return float(lib().az_gumbel_vmix(len(visits), _p(visits), _p(W), _p(prior), C.c_float(float(root_value))))
 
 
 class Engine:
@@ -701,6 +768,19 @@ class Engine:
         k, p = C.c_double(0.0), C.c_int(0)
         self._check(lib().az_get_forced_playouts(self.h, C.byref(k), C.byref(p)), "az_get_forced_playouts")
         return dict(k=float(k.value), prune=bool(p.value))
+
+    # ---- Gumbel root search ----
+    def set_gumbel(self, m, c_visit=50.0, c_scale=1.0):
+        """Opt-in (Danihelka et al. 2022): every noised root samples m Gumbel-top candidates, searches them by sequential halving
+        and makes pi = softmax(logits + sigma(completed Q)); the noise tape is read as Gumbel(0, 1) draws.  m = 0 switches it
+        off; the paper uses m = 16, c_visit = 50, c_scale = 1.  See include/az_engine.h."""
+        self._check(lib().az_set_gumbel(self.h, int(m), float(c_visit), float(c_scale)), "az_set_gumbel")
+
+    def gumbel(self):
+        """The setting in force: dict(m, c_visit, c_scale); m 0 = off."""
+        m, cv, cs = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+        self._check(lib().az_get_gumbel(self.h, C.byref(m), C.byref(cv), C.byref(cs)), "az_get_gumbel")
+        return dict(m=int(m.value), c_visit=float(cv.value), c_scale=float(cs.value))
 
     def sims(self):
         """int32 simulations of every record of the last episode, in the order of records() (az_selfplay_sims)."""

@@ -51,7 +51,9 @@ __device__ __forceinline__ float az_tanhf(float x)
 
 // The float64 form keeps its hard clamp at -708 (no gradual underflow): it only feeds the tempered
 // visit-count softmax of pi, whose float32 records cannot hold anything below e^-708 relative to 1.
-__device__ __forceinline__ double az_exp(double x)
+// Also callable on the host (az_gumbel_target): the same fma chain through the compiler's builtin, correctly rounded either
+// way, so the bits are the device's as long as the translation unit keeps -ffp-contract=off.
+__host__ __device__ __forceinline__ double az_exp(double x)
 {
     if (x < -708.0) return 0.0;
     if (x > 709.0) x = 709.0;
@@ -73,7 +75,10 @@ __device__ __forceinline__ double az_exp(double x)
     p = __builtin_fma(p, r, 1.0);
     p = __builtin_fma(p, r, 1.0);
     long long k = (long long)kf;
-    return p * __longlong_as_double((long long)((u64)(k + 1023) << 52));
+    const u64 sbits = (u64)(k + 1023) << 52;
+    double scale;
+    __builtin_memcpy(&scale, &sbits, sizeof scale);
+    return p * scale;
 }
 
 __device__ __forceinline__ unsigned az_fmix32(unsigned x)

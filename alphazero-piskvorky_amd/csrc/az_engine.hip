@@ -59,6 +59,7 @@ struct Lane {
     DevBuf path, depth, leaf_kind, leaf, leaf_last, logits, vhid, pol_feat, dbg, scratch, it_status, it_net, leaf_sym;       // per evaluation item
     DevBuf inflight;               // per slot, deep engines with virtual-loss batching only: in-flight count of every edge
     DevBuf budget, cp_board, cp_state;     // per slot, playout cap: the ply's simulation budget, and the staging of k_refill's partition
+    DevBuf root_logits, root_v;            // per slot, az_set_gumbel: the root's logits row and value of the running ply (allocated by the setter)
     // one ply (k_begin, (S+1) x {trunk, fc, step}, k_move) captured once as a hipGraph and replayed every ply:
     // 3(S+1)+2 launches (6(S+1)+2 with the split trunk) become one submission.  Indexed [split trunk][arena].
     struct PlyGraph {
@@ -135,6 +136,10 @@ struct az_engine {
     // az_set_forced_playouts: 0.0 = off
     double forced_k = 0.0;
     int forced_prune = 0;
+    // az_set_gumbel: m = 0 = off; the schedule table u16[m][S] lives on the device
+    int gumbel_m = 0;
+    double gumbel_cv = 50.0, gumbel_cs = 1.0;
+    DevBuf gumbel_seq;
     PackedNet net[2];
     az_counters last{};
     // running episode (az_selfplay_begin .. az_selfplay_end)
@@ -736,6 +741,7 @@ static int create_engine(const az_config *cfg, az_engine **out, bool deep)
         d.resign_thr = 0.0; d.resign_min_ply = 0; d.resign_permille = 0; d.rec_value = nullptr; d.g_cross = nullptr;
         d.cap_fast = 0; d.cap_permille = 0;
         d.forced_k = 0.0; d.forced_prune = 0;
+        d.gumbel_m = 0; d.gumbel_cv = 0.0; d.gumbel_cs = 0.0; d.gumbel_seq = nullptr; d.root_logits = nullptr; d.root_v = nullptr;
         d.s_budget = (int *)L.budget.p; d.cp_board = (u64 *)L.cp_board.p; d.cp_state = (int *)L.cp_state.p;
         if (!rc) rc = alloc_items(e, L, 1);
     }
@@ -807,7 +813,7 @@ extern "C" void az_destroy(az_engine *e)
         DevBuf *all[] = {&L.board, &L.s_game, &L.s_ply, &L.s_player, &L.s_last, &L.s_status, &L.s_net, &L.edges, &L.rows_used,
                          &L.path, &L.depth, &L.leaf_kind, &L.leaf, &L.leaf_last, &L.logits, &L.vhid, &L.pol_feat, &L.cnt,
                          &L.active_dev, &L.carried, &L.dbg, &L.scratch, &L.it_status, &L.it_net, &L.leaf_sym, &L.inflight,
-                         &L.budget, &L.cp_board, &L.cp_state};
+                         &L.budget, &L.cp_board, &L.cp_state, &L.root_logits, &L.root_v};
         for (DevBuf *b : all) dev_free(*b);
         for (hipEvent_t ev : L.ev) (void)hipEventDestroy(ev);
         for (int i = 0; i < 4; i++)
@@ -816,7 +822,7 @@ extern "C" void az_destroy(az_engine *e)
     DevBuf *shared[] = {&e->T_table, &e->log_table, &e->sqrt_table, &e->noise_off, &e->next_game, &e->noise, &e->u,
                         &e->rec_planes, &e->rec_last, &e->rec_action, &e->rec_mover, &e->rec_pi, &e->rec_visits, &e->g_nply,
                         &e->g_result, &e->src_index, &e->rec_value, &e->g_cross, &e->cache, &e->start_tab, &e->bt_cells, &e->bt_players, &e->bt_lasts, &e->bt_T,
-                        &e->bt_zero_off, &e->bt_visits, &e->bt_W, &e->bt_prior, &e->bt_pi, &e->bt_action, &e->ext.map, &e->ext.count};
+                        &e->bt_zero_off, &e->bt_visits, &e->bt_W, &e->bt_prior, &e->bt_pi, &e->bt_action, &e->ext.map, &e->ext.count, &e->gumbel_seq};
     for (DevBuf *b : shared) dev_free(*b);
     for (int s = 0; s < 2; s++) {
         PackedNet &p = e->net[s];
@@ -1061,6 +1067,10 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
         // forced playouts are for the searches whose root is noised (the arena's never is); k_step exempts the cap's FAST plies
         d.forced_k = sp.add_noise && !sp.arena ? e->forced_k : 0.0;
         d.forced_prune = d.forced_k > 0.0 ? e->forced_prune : 0;
+        // ... and so is the Gumbel root search; the buffers it reads were set by az_set_gumbel
+        d.gumbel_m = sp.add_noise && !sp.arena ? e->gumbel_m : 0;
+        d.gumbel_cv = d.gumbel_m ? e->gumbel_cv : 0.0;
+        d.gumbel_cs = d.gumbel_m ? e->gumbel_cs : 0.0;
     });
     const bool capped = !sp.preset && !sp.arena && e->cap_fast > 0;
     // persistent search kernel: plain net or synthetic evaluator, the reference's sequential search, trees that fit into LDS
@@ -1601,6 +1611,7 @@ extern "C" int az_selfplay_begin(az_engine *e, const az_selfplay_args *a)
     } else if (e->stream_tapes) {
         e->tapes = new TapeProducer();
         e->tapes->ahead = e->start_count > 0 ? e->start_max_ply : 0;      // a game's ply runs this far ahead of the episode's
+        e->tapes->kind = e->gumbel_m > 0 ? 1 : 0;                          // az_set_gumbel: the legal-cell draws are Gumbel(0, 1)
         hipError_t trc = e->tapes->start(e->cfg.device, a->seed0, G, nn, plies, e->cfg.dirichlet_alpha, e->tape_len,
                                          (double *)e->noise.p, (double *)e->u.p, e->tape_threads);
         if (trc != hipSuccess) { stop_tapes(e); return fail(e, AZ_ERR_HIP, "tape producer: %s", hipGetErrorString(trc)); }
@@ -1610,7 +1621,7 @@ extern "C" int az_selfplay_begin(az_engine *e, const az_selfplay_args *a)
         for (int g0 = 0; g0 < G; g0 += chunk) {
             int cnt = std::min(chunk, G - g0);
             azrng::selfplay_tapes_parallel(a->seed0, g0, cnt, nn, e->cfg.dirichlet_alpha, plies, hn.data(), e->tape_len,
-                                           hu.data(), host_threads());
+                                           hu.data(), host_threads(), e->gumbel_m > 0 ? 1 : 0);
             HIPCHECK(e, az_memcpy(e->stream, (double *)e->noise.p + (size_t)g0 * e->tape_len, hn.data(), (size_t)cnt * e->tape_len * 8,
                                   hipMemcpyHostToDevice));
             HIPCHECK(e, az_memcpy(e->stream, (double *)e->u.p + (size_t)g0 * nn, hu.data(), (size_t)cnt * nn * 8, hipMemcpyHostToDevice));
@@ -1861,6 +1872,7 @@ extern "C" int az_set_forced_playouts(az_engine *e, double k, int prune)
     if (!(k > 0.0 && k <= 16.0) || (prune != 0 && prune != 1))
         return fail(e, AZ_ERR_INVALID, "az_set_forced_playouts: k %g (0 = off, else in (0, 16]), prune %d (0 / 1)", k, prune);
     if (e->reuse) return fail(e, AZ_ERR_INVALID, "forced playouts and subtree reuse cannot be combined");
+    if (e->gumbel_m > 0) return fail(e, AZ_ERR_INVALID, "forced playouts and the Gumbel root search cannot be combined");
     e->forced_k = k; e->forced_prune = prune;
     return AZ_OK;
 }
@@ -1895,6 +1907,140 @@ extern "C" int64_t az_forced_prune(double k, double c_puct, int count, const int
         removed += visits[c] - out[c];
     }
     return removed;
+}
+
+// ---- Gumbel root search: sequential halving and completed-Q policy targets ----
+// seq[t] = the visit count a root child must have to be selectable at simulation t, for k candidates and S simulations
+extern "C" int az_gumbel_schedule(int k, int S, int32_t *out)
+{
+    if (k < 0 || S < 1 || S > AZ_DEEP_MAX_SIMULATIONS || !out) return AZ_ERR_INVALID;
+    if (k <= 1) {
+        for (int t = 0; t < S; t++) out[t] = t;
+        return AZ_OK;
+    }
+    int L = 0;
+    while ((1 << L) < k) L++;                                   // ceil(log2 k)
+    std::vector<int32_t> visits((size_t)k, 0);
+    int c = k, n = 0;
+    while (n < S) {
+        const int extra = std::max(1, S / (L * c));
+        for (int x = 0; x < extra && n < S; x++)
+            for (int i = 0; i < c; i++) {
+                if (n < S) out[n++] = visits[i];
+                visits[i]++;
+            }
+        c = std::max(2, c / 2);
+    }
+    return AZ_OK;
+}
+
+extern "C" int az_set_gumbel(az_engine *e, int m, double c_visit, double c_scale)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_gumbel: an episode is open (az_selfplay_end first)");
+    if (m == 0) {
+        e->gumbel_m = 0;
+        return AZ_OK;
+    }
+    if (m < 0 || m > std::min(e->nn, 64) || !(c_visit >= 0.0) || !std::isfinite(c_visit) || !(c_scale > 0.0) || !std::isfinite(c_scale))
+        return fail(e, AZ_ERR_INVALID, "az_set_gumbel: m %d (0 = off, else 1..%d), c_visit %g (>= 0), c_scale %g (> 0)", m,
+                    std::min(e->nn, 64), c_visit, c_scale);
+    if (e->reuse) return fail(e, AZ_ERR_INVALID, "the Gumbel root search and subtree reuse cannot be combined");
+    if (e->vl > 1 || e->vl_kernel) return fail(e, AZ_ERR_INVALID, "the Gumbel root search and virtual-loss batching cannot be combined");
+    if (e->forced_k > 0.0) return fail(e, AZ_ERR_INVALID, "forced playouts and the Gumbel root search cannot be combined");
+    if (e->ext.on) return fail(e, AZ_ERR_INVALID, "the Gumbel root search and the external evaluator cannot be combined (it returns priors, not logits)");
+    if (e->cfg.eval_kind == AZ_EVAL_SYNTHETIC) return fail(e, AZ_ERR_INVALID, "the Gumbel root search needs a net: the synthetic evaluator has no logits");
+    DEVICE_GUARD(e);
+    // the schedules of k = 1 .. m candidates (a root has min(m, legal cells) of them), one row of S entries each
+    const int S = e->cfg.num_simulations;
+    std::vector<int32_t> row((size_t)S);
+    std::vector<uint16_t> tab((size_t)m * S);
+    for (int k = 1; k <= m; k++) {
+        az_gumbel_schedule(k, S, row.data());
+        for (int t = 0; t < S; t++) tab[(size_t)(k - 1) * S + t] = (uint16_t)row[t];
+    }
+    int rc = upload(e, e->gumbel_seq, tab.data(), tab.size() * sizeof(uint16_t));
+    for (Lane &L : e->lanes) {
+        if (!rc) rc = dev_alloc(e, L.root_logits, (size_t)L.d.B * e->RW * sizeof(float));
+        if (!rc) rc = dev_alloc(e, L.root_v, (size_t)L.d.B * sizeof(float));
+    }
+    if (rc) return rc;
+    HIPCHECK(e, hipStreamSynchronize(e->stream));
+    for (Lane &L : e->lanes) {
+        L.d.gumbel_seq = (const unsigned short *)e->gumbel_seq.p;
+        L.d.root_logits = (float *)L.root_logits.p;
+        L.d.root_v = (float *)L.root_v.p;
+    }
+    each_state(e, [&](DevState &d) { (void)d; });        // refresh the item views
+    e->gumbel_m = m; e->gumbel_cv = c_visit; e->gumbel_cs = c_scale;
+    return AZ_OK;
+}
+
+extern "C" int az_get_gumbel(const az_engine *e, int *m, double *c_visit, double *c_scale)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (m) *m = e->gumbel_m;
+    if (c_visit) *c_visit = e->gumbel_cv;
+    if (c_scale) *c_scale = e->gumbel_cs;
+    return AZ_OK;
+}
+
+// v_mix of one root row, as az_gumbel_target and k_move form it (NaN for a bad argument): the piece of the target whose
+// summation order a test wants to see on its own
+extern "C" double az_gumbel_vmix(int count, const int32_t *visits, const double *W, const float *prior, float root_value)
+{
+    if (count < 1 || count > 225 || !visits || !W || !prior) return NAN;
+    std::vector<double> a((size_t)count), b((size_t)count);
+    int64_t total = 0;
+    for (int c = 0; c < count; c++) {
+        if (visits[c] < 0 || visits[c] > 0xFFFF) return NAN;
+        total += visits[c];
+        a[c] = visits[c] ? (double)prior[c] : 0.0;
+        b[c] = a[c] * (visits[c] ? W[c] / (double)visits[c] : 0.0);
+    }
+    if (total < 1) return NAN;
+    return gumbel_vmix(root_value, (double)total, pw_sum(a.data(), count), pw_sum(b.data(), count));
+}
+
+// k_move's Gumbel pass on one root row of `count` legal children, with the functions the kernel uses (az_tree.h, az_device.h)
+extern "C" int az_gumbel_target(int count, const float *logits, const double *g, const int32_t *visits, const double *W,
+                                const float *prior, float root_value, double c_visit, double c_scale, float *pi, int32_t *action)
+{
+    if (count < 1 || count > 225 || !logits || !g || !visits || !W || !prior || !pi || !action) return AZ_ERR_INVALID;
+    if (!(c_visit >= 0.0) || !std::isfinite(c_visit) || !(c_scale > 0.0) || !std::isfinite(c_scale)) return AZ_ERR_INVALID;
+    int max_n = 0;
+    int64_t total = 0;
+    for (int c = 0; c < count; c++) {
+        if (visits[c] < 0 || visits[c] > 0xFFFF) return AZ_ERR_INVALID;
+        max_n = std::max(max_n, (int)visits[c]);
+        total += visits[c];
+    }
+    if (total < 1) return AZ_ERR_INVALID;
+    const double sig = gumbel_sigma(c_visit, c_scale, max_n);
+    std::vector<double> q((size_t)count), a((size_t)count), b((size_t)count), y((size_t)count);
+    int best = -1;
+    double bs = 0.0;
+    for (int c = 0; c < count; c++) {
+        q[c] = visits[c] ? W[c] / (double)visits[c] : 0.0;
+        a[c] = visits[c] ? (double)prior[c] : 0.0;
+        b[c] = a[c] * q[c];
+        if (visits[c] == max_n) {
+            const double s = gumbel_score(g[c] + (double)logits[c], sig, q[c]);
+            if (best < 0 || s > bs) { bs = s; best = c; }      // the first maximum
+        }
+    }
+    const double vmix = gumbel_vmix(root_value, (double)total, pw_sum(a.data(), count), pw_sum(b.data(), count));
+    double m = -INFINITY;
+    for (int c = 0; c < count; c++) {
+        y[c] = gumbel_score((double)logits[c], sig, visits[c] ? q[c] : vmix);
+        m = y[c] > m ? y[c] : m;
+    }
+    for (int c = 0; c < count; c++) y[c] = az_exp(y[c] - m);
+    const double s = pw_sum(y.data(), count);
+    const bool uniform = (s < 1e-8) || (s != s);
+    for (int c = 0; c < count; c++) pi[c] = (float)(uniform ? 1.0 / (double)count : y[c] / s);
+    *action = best;
+    return AZ_OK;
 }
 
 extern "C" int az_selfplay_sims(az_engine *e, int32_t *sims)
@@ -2418,6 +2564,7 @@ extern "C" int az_set_subtree_reuse(az_engine *e, int on)
     if (on && e->ext.on) return fail(e, AZ_ERR_INVALID, "subtree reuse and the external evaluator cannot be combined");
     if (on && e->cap_fast) return fail(e, AZ_ERR_INVALID, "the playout cap and subtree reuse cannot be combined");
     if (on && e->forced_k > 0.0) return fail(e, AZ_ERR_INVALID, "forced playouts and subtree reuse cannot be combined");
+    if (on && e->gumbel_m > 0) return fail(e, AZ_ERR_INVALID, "the Gumbel root search and subtree reuse cannot be combined");
     if (on && e->R > REUSE_MAX_ROWS)
         return fail(e, AZ_ERR_INVALID, "subtree reuse supports at most %d simulations per move", REUSE_MAX_ROWS - 1);
     e->reuse = on ? 1 : 0;
@@ -2446,6 +2593,11 @@ extern "C" int az_set_virtual_loss(az_engine *e, int leaves)
     if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_virtual_loss: an episode is open");
     if (leaves < 1 || leaves > VL_MAX) return fail(e, AZ_ERR_INVALID, "virtual-loss batching supports 1..%d leaves per batch", VL_MAX);
     if (leaves > 1 && e->reuse) return fail(e, AZ_ERR_INVALID, "subtree reuse and virtual-loss batching cannot be combined");
+    {
+        const char *f = getenv("AZ_VL_FORCE");
+        if (e->gumbel_m > 0 && (leaves > 1 || (f && f[0] == '1')))
+            return fail(e, AZ_ERR_INVALID, "the Gumbel root search and virtual-loss batching cannot be combined");
+    }
     DEVICE_GUARD(e);
     // deep search (S > DEFAULT_MAX_S) with batches: the in-flight counts live beside the tree, one byte per edge
     const bool need_inflight = e->deep && e->cfg.num_simulations > DEFAULT_MAX_S && leaves > 1;
@@ -2570,6 +2722,7 @@ extern "C" int az_set_external_evaluator(az_engine *e, const az_ext_evaluator *e
     if (e->reuse) return fail(e, AZ_ERR_INVALID, "subtree reuse and the external evaluator cannot be combined");
     if (e->cap_fast) return fail(e, AZ_ERR_INVALID, "the playout cap and the external evaluator cannot be combined");
     if (e->leaf_symmetry) return fail(e, AZ_ERR_INVALID, "random-symmetry leaf evaluation and the external evaluator cannot be combined");
+    if (e->gumbel_m > 0) return fail(e, AZ_ERR_INVALID, "the Gumbel root search and the external evaluator cannot be combined (it returns priors, not logits)");
     if (ev->capacity < e->cfg.slots * e->vl)
         return fail(e, AZ_ERR_INVALID, "az_set_external_evaluator: capacity %d is below az_ext_capacity = %d slots x %d leaves per batch",
                     ev->capacity, e->cfg.slots, e->vl);
@@ -2598,6 +2751,8 @@ extern "C" int az_search_callback(az_engine *e, const uint8_t *board, int player
     if (e->run.open) return fail(e, AZ_ERR_STATE, "az_search_callback: a self-play episode is open on this engine");
     if (e->vl > 1 || e->reuse || e->leaf_symmetry)
         return fail(e, AZ_ERR_INVALID, "az_search_callback: not combinable with virtual-loss batching, subtree reuse or random-symmetry leaf evaluation");
+    if (noise && e->gumbel_m > 0)
+        return fail(e, AZ_ERR_INVALID, "az_search_callback: a noised search under the Gumbel root search needs logits, the callback returns priors");
     DEVICE_GUARD(e);
     const int nn = e->nn, S = e->cfg.num_simulations;
     int stones = 0;
@@ -2634,6 +2789,7 @@ extern "C" int az_search_callback(az_engine *e, const uint8_t *board, int player
         d.max_plies = 0; d.add_noise = noise ? 1 : 0; d.arena = 0; d.total_games = 1; d.reuse = 0; d.game_key0 = 0;
         d.cache = nullptr; d.ext_eval = 1; d.cap_fast = 0; d.cap_permille = 0;
         d.forced_k = noise ? e->forced_k : 0.0; d.forced_prune = d.forced_k > 0.0 ? e->forced_prune : 0;
+        d.gumbel_m = 0; d.gumbel_cv = 0.0; d.gumbel_cs = 0.0;       // refused above with noise; without noise there is no Gumbel root
     });
     struct Restore {
         az_engine *e; bool had_cache;

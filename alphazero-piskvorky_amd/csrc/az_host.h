@@ -15,12 +15,12 @@
 
 namespace azrng {
 void selfplay_tapes_parallel(uint64_t seed0, int g0, int count, int nn, double alpha, int max_plies, double *noise,
-                             int64_t noise_stride, double *u, int threads);
+                             int64_t noise_stride, double *u, int threads, int kind);
 void uniforms(uint64_t seed, int count, double *u);
 struct Streams;
 Streams *streams_new(uint64_t seed0, int count);
 void streams_free(Streams *s);
-void streams_plies(Streams *s, int i, int nn, double alpha, int m0, int m1, double *noise_row, double *u_row);
+void streams_plies(Streams *s, int i, int nn, double alpha, int m0, int m1, double *noise_row, double *u_row, int kind);
 }
 
 // Process-wide stream pool.  The runtime maps the streams of one priority level onto a small pool of hardware queues
@@ -84,6 +84,7 @@ static StreamPool g_streams;
 struct TapeProducer {
     static constexpr int P = 2;          // plies per wave
     int ahead = 0;                       // largest start ply of a game; set before start()
+    int kind = 0;                        // what a ply's legal-cell draws are: 0 = Dirichlet, 1 = Gumbel(0, 1) (az_set_gumbel); set before start()
     int device = 0, G = 0, nn = 0, plies = 0, waves = 0, threads = 1;
     double alpha = 0.3;
     int64_t tape_len = 0;
@@ -146,7 +147,7 @@ struct TapeProducer {
                     const int g0 = next.fetch_add(8);
                     if (g0 >= G) break;
                     for (int g = g0; g < std::min(G, g0 + 8); g++)
-                        if (!done[g]) azrng::streams_plies(streams, g, nn, alpha, m0, m1, hn[b] + (size_t)g * L, hu[b] + (size_t)g * P);
+                        if (!done[g]) azrng::streams_plies(streams, g, nn, alpha, m0, m1, hn[b] + (size_t)g * L, hu[b] + (size_t)g * P, kind);
                 }
             };
             std::vector<std::thread> pool;

@@ -65,6 +65,8 @@ struct MT {
         return (a * 67108864.0 + b) / 9007199254740992.0;
     }
     double std_exponential() { return -std::log(1.0 - next_double()); }
+    // RandomState.gumbel(): loc - scale * log(-log(1 - U)) with loc 0, scale 1; one random_sample per draw, scalar libm log
+    double gumbel() { return 0.0 - 1.0 * std::log(-std::log(1.0 - next_double())); }
     double legacy_gauss()
     {
         if (has_gauss) {
@@ -129,14 +131,24 @@ struct MT {
     }
 };
 
-// One game's self-play tape: per ply m, dirichlet over nn-m cells then one uniform.
-void selfplay_tape(uint64_t seed, int nn, double alpha, int max_plies, double *noise, double *u)
+// the legal-cell draws of one ply: kind 0 = dirichlet([alpha] * k), kind 1 = gumbel(size = k) (az_set_gumbel)
+static inline void ply_draws(MT &mt, int kind, double alpha, int k, double *out)
+{
+    if (kind == 1) {
+        for (int j = 0; j < k; j++) out[j] = mt.gumbel();
+    } else {
+        mt.dirichlet(alpha, k, out);
+    }
+}
+
+// One game's self-play tape: per ply m, the draws over nn-m cells then one uniform.
+void selfplay_tape(uint64_t seed, int nn, double alpha, int max_plies, double *noise, double *u, int kind)
 {
     MT mt((uint32_t)(seed & 0xffffffffu));
     size_t off = 0;
     int plies = max_plies > 0 && max_plies < nn ? max_plies : nn;
     for (int m = 0; m < plies; m++) {
-        mt.dirichlet(alpha, nn - m, noise + off);
+        ply_draws(mt, kind, alpha, nn - m, noise + off);
         off += (size_t)(nn - m);
         u[m] = mt.next_double();
     }
@@ -159,12 +171,12 @@ Streams *streams_new(uint64_t seed0, int count)
 void streams_free(Streams *s) { delete s; }
 
 // plies [m0, m1) of game i: noise_row receives sum_{m} (nn - m) doubles back to back, u_row one double per ply
-void streams_plies(Streams *s, int i, int nn, double alpha, int m0, int m1, double *noise_row, double *u_row)
+void streams_plies(Streams *s, int i, int nn, double alpha, int m0, int m1, double *noise_row, double *u_row, int kind)
 {
     MT &mt = s->mt[(size_t)i];
     size_t off = 0;
     for (int m = m0; m < m1; m++) {
-        mt.dirichlet(alpha, nn - m, noise_row + off);
+        ply_draws(mt, kind, alpha, nn - m, noise_row + off);
         off += (size_t)(nn - m);
         u_row[m - m0] = mt.next_double();
     }
@@ -178,7 +190,7 @@ void uniforms(uint64_t seed, int count, double *u)
 
 // Tapes for games [g0, g0+count) written with a fixed stride, generated by a small thread pool.
 void selfplay_tapes_parallel(uint64_t seed0, int g0, int count, int nn, double alpha, int max_plies, double *noise,
-                             int64_t noise_stride, double *u, int threads)
+                             int64_t noise_stride, double *u, int threads, int kind)
 {
     if (threads < 1) threads = 1;
     if (threads > count) threads = count > 0 ? count : 1;
@@ -187,7 +199,7 @@ void selfplay_tapes_parallel(uint64_t seed0, int g0, int count, int nn, double a
         pool.emplace_back([=]() {
             for (int i = t; i < count; i += threads)
                 selfplay_tape(seed0 + (uint64_t)(g0 + i), nn, alpha, max_plies, noise + (int64_t)i * noise_stride,
-                              u + (int64_t)i * nn);
+                              u + (int64_t)i * nn, kind);
         });
     }
     for (auto &th : pool) th.join();
@@ -198,7 +210,15 @@ void selfplay_tapes_parallel(uint64_t seed0, int g0, int count, int nn, double a
 extern "C" int az_rng_selfplay_tape(uint64_t seed, int board_size, double alpha, int max_plies, double *noise, double *u)
 {
     if (board_size < 1 || board_size > 15 || !noise || !u || alpha <= 0.0) return AZ_ERR_INVALID;
-    azrng::selfplay_tape(seed, board_size * board_size, alpha, max_plies, noise, u);
+    azrng::selfplay_tape(seed, board_size * board_size, alpha, max_plies, noise, u, 0);
+    return AZ_OK;
+}
+
+// az_set_gumbel's tape: per ply m, nn - m draws of RandomState(seed).gumbel() then one uniform, in az_rng_selfplay_tape's layout
+extern "C" int az_rng_selfplay_tape_gumbel(uint64_t seed, int board_size, int max_plies, double *noise, double *u)
+{
+    if (board_size < 1 || board_size > 15 || !noise || !u) return AZ_ERR_INVALID;
+    azrng::selfplay_tape(seed, board_size * board_size, 0.0, max_plies, noise, u, 1);
     return AZ_OK;
 }
 

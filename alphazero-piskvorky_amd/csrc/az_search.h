@@ -65,7 +65,7 @@ template <int N, class PG, bool SYNTH>
 __device__ __forceinline__ void step_lds(const DevState &d, int b, int lane, Edge *rows, unsigned *path, GameLds &gs,
                                          const float *lg, const float *hid, const double *sq_lds, int rootN, int do_select,
                                          int pl, int slast, int netid, int game, int ply, const Plane &bX, const Plane &bO,
-                                         unsigned long long (&cnt)[4], const float *w2, float b2, int carried KS_PARAM)
+                                         unsigned long long (&cnt)[4], const float *w2, float b2, int carried, double &gum_h KS_PARAM)
 {
 #ifdef AZ_STAMPS
     unsigned long long st_t = __builtin_amdgcn_s_memtime();
@@ -80,6 +80,7 @@ __device__ __forceinline__ void step_lds(const DevState &d, int b, int lane, Edg
     Plane lme, lopp;
 #pragma unroll
     for (int q = 0; q < 4; q++) { lme.w[q] = gs.leaf[q]; lopp.w[q] = gs.leaf[4 + q]; }
+    const bool gumbel = !SYNTH && d.gumbel_m > 0 && d.add_noise;      // Gumbel root search (kernel-argument test, uniform): the noised root only
     // ---------------- stage 1: evaluation -> expand -> backup ----------------
     if (kind == LEAF_REUSE) {
         // subtree reuse: the root kept from the previous ply (its rows were loaded by k_search) is not evaluated again; only the
@@ -138,8 +139,19 @@ __device__ __forceinline__ void step_lds(const DevState &d, int b, int lane, Edg
                 const float acc = value_fc2_chain_lds(hid, w2);    // w2, b2: value_fc2 of the game's net, put into LDS / a register once per ply
                 v = az_tanhf(acc + b2);
                 ST_STAMP(11);        // value tail
+                if (kind == LEAF_ROOT && gumbel) {
+                    // az_set_gumbel: the edges keep the plain softmax priors; g + logit of the lane's cell stays in a register of the
+                    // game's wave for the selections of this ply, the logits row and the value go to the slot for k_move
+                    Plane occ;
+#pragma unroll
+                    for (int q = 0; q < 4; q++) occ.w[q] = lme.w[q] | lopp.w[q];
+                    const double *nz = d.noise + (size_t)game * d.noise_stride + d.noise_off[ply];
+                    gum_h = (lane < G::nn && !pl_get(occ, lane)) ? nz[lane - pl_rank(occ, lane)] + (double)x : 0.0;
+                    d.root_logits[(size_t)b * G::RW + lane] = lane < G::nn ? x : 0.0f;
+                    if (lane == 0) d.root_v[b] = v;
+                }
             }
-            if (kind == LEAF_ROOT && d.add_noise) {
+            if (kind == LEAF_ROOT && d.add_noise && !gumbel) {
                 // mcts.py:113-116; float32 multiply, float64 add, float32 store
                 Plane occ;
 #pragma unroll
@@ -199,7 +211,23 @@ __device__ __forceinline__ void step_lds(const DevState &d, int b, int lane, Edg
         const double sq = sq_lds[npar];                       // np.sqrt(self.N + 1e-8), mcts.py:73
         double best = 0.0;
         int bi = -1, bN = 0, bC = 0;
-        if (lane < G::nn && !pl_get(occ, lane)) {
+        if (gumbel && row == 0) {
+            // az_set_gumbel: sequential halving at the root (k_step's branch, az_tree.h): the children whose visit count is the
+            // schedule's entry for this simulation compete with (g + logit) + sigma q
+            const bool own = lane < G::nn && !pl_get(occ, lane);
+            Edge e;
+            e.W = 0.0; e.P = 0.0f; e.N = 0; e.child = 0;
+            if (own) e = rows[lane];
+            const unsigned mxn = wave_max_u(own ? (unsigned)e.N : 0u);
+            const int kk = min_i(d.gumbel_m, G::nn - pl_count(occ));          // >= 1: an active slot has a legal cell
+            const int need = (int)d.gumbel_seq[(size_t)(kk > 0 ? kk - 1 : 0) * d.S + rootN];
+            const double sig = gumbel_sigma(d.gumbel_cv, d.gumbel_cs, (int)mxn);
+            if (own && (int)e.N == need) {
+                const double Q = e.N ? e.W / (double)e.N : 0.0;
+                best = gumbel_score(gum_h, sig, Q);
+                bi = lane; bN = e.N; bC = e.child;
+            }
+        } else if (lane < G::nn && !pl_get(occ, lane)) {
             Edge e = rows[row * PG::ROWE + lane];
             double Q = e.N ? e.W / (double)e.N : 0.0;         // mcts.py:80 Q = W/N (0.0 while unvisited)
             best = Q + ((d.c_puct * (double)e.P) * sq) / (double)(1 + (int)e.N);
@@ -435,6 +463,7 @@ __global__ __launch_bounds__(NetGeo<N>::NW * 64) __attribute__((amdgpu_waves_per
     const float b2 = (!SYNTH && mine) ? d.v2b[netid][0] : 0.0f;
     if (!SYNTH && mine) w2_lds[wave * 64 + lane] = d.v2w[netid][lane];        // read by the same wave only: no barrier needed beyond the loop's
     float *inA = lds, *inB = lds + 32 * PG::CS;
+    double gum_h = 0.0;                    // az_set_gumbel: g + logit of the lane's root cell, kept for the whole ply (step_lds)
 
     KS_STAMP(0);
     for (int idx = 0; idx <= S; idx++) {
@@ -617,7 +646,7 @@ __global__ __launch_bounds__(NetGeo<N>::NW * 64) __attribute__((amdgpu_waves_per
         if (mine && (!(AZ_SEARCH_SKIP & 2) || idx == S))
             step_lds<N, PG, SYNTH>(d, gb, lane, rows_all + (size_t)wave * d.R * PG::ROWE, path_l[wave], games[wave],
                                    logits_l + wave * PG::RW, vhid_l + wave * 64, sq_lds, idx, idx < S ? 1 : 0, pl, slast, netid,
-                                   game, ply, bX, bO, cnt, w2_lds + wave * 64, b2, carried KS_ARG);
+                                   game, ply, bX, bO, cnt, w2_lds + wave * 64, b2, carried, gum_h KS_ARG);
         KS_STAMP(8);                 // the tree step of this wave's game (waves 0 .. GP - 1)
         __syncthreads();
         KS_STAMP(9);                 // ... and the wait for the other game's

@@ -117,6 +117,12 @@ struct DevState {
     // --- opt-in forced playouts and policy target pruning (az_set_forced_playouts): noised roots only, 0.0 on every other path ---
     double forced_k;       // root child c is forced while n_c^2 < forced_k * P[c] * (parent count); 0.0 = off: nothing new is executed
     int forced_prune;      // k_move makes pi and the move from the pruned counts N' (the record's visits stay the raw ones)
+    // --- opt-in Gumbel root search (az_set_gumbel): noised roots only, gumbel_m = 0 on every other path ---
+    int gumbel_m;          // candidates sampled without replacement; 0 = off: nothing below is read or written
+    double gumbel_cv, gumbel_cs;       // sigma(q) = (c_visit + max N) * c_scale * q
+    const unsigned short *gumbel_seq;  // [gumbel_m][S] sequential-halving schedules: row k - 1 serves a root with k candidates
+    float *root_logits;    // [B][RW] the root's logits by board cell, written when the root evaluation is consumed, read by k_move
+    float *root_v;         // [B] ... and the root's value
 };
 __device__ __forceinline__ int game_key(const DevState &d, int game) { return (int)(d.game_key0 + d.key_stride * (unsigned)game); }
 // az_set_playout_cap's rule, a function of the game's global name and the absolute ply only (the host's az_playout_cap_full)
@@ -157,6 +163,23 @@ __host__ __device__ inline int forced_pruned(double k, double c_puct, double Q, 
         if (forced_score(Q, c_puct, P, sq, mid) < target) hi = mid; else lo = mid + 1;
     }
     return (lo == 1 && lo < n) ? 0 : lo;
+}
+
+// az_set_gumbel (Danihelka et al., ICLR 2022): the scalar pieces of the root rule, shared by the tree kernels, k_move and the host's
+// az_gumbel_target.  Every operation is a separate float64 one (the build keeps -ffp-contract=off).
+__host__ __device__ __forceinline__ double gumbel_sigma(double c_visit, double c_scale, int max_n)
+{
+    return (c_visit + (double)max_n) * c_scale;
+}
+// score = h + sig q (selection and move: h = g + logit; policy target: h = logit, q completed with v_mix)
+__host__ __device__ __forceinline__ double gumbel_score(double h, double sig, double q)
+{
+    const double t = sig * q;
+    return h + t;
+}
+__host__ __device__ __forceinline__ double gumbel_vmix(float v0, double sum_n, double pv, double pq)
+{
+    return ((double)v0 + (sum_n / pv) * pq) / (1.0 + sum_n);
 }
 
 template <int N>
@@ -448,6 +471,7 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
     Edge *rows = d.edges + (size_t)b * d.R * G::RW;
     const int budget = budget_raw < 0 ? -budget_raw : budget_raw;     // simulations of this slot's ply: S unless the cap says less
     const bool root_noise = d.add_noise && budget_raw > 0;            // a FAST ply uses the priors as they are
+    const bool gumbel = !SYNTH && d.gumbel_m > 0 && root_noise;       // Gumbel root search (kernel-argument test, uniform): the noised root only
 
     // ---------------- stage 1: evaluation -> expand -> backup ----------------
     if (kind == LEAF_REUSE) {
@@ -536,7 +560,13 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
                 v = az_tanhf(acc + (netid ? b2b : b2a));
                 }
             }
-            if (kind == LEAF_ROOT && root_noise) {
+            if (kind == LEAF_ROOT && gumbel) {
+                // az_set_gumbel: the edges keep the plain softmax priors; the root's logits (by board cell) and value stay with
+                // the slot for the selections of this ply and for k_move
+#pragma unroll
+                for (int i = 0; i < G::CPL; i++) d.root_logits[(size_t)b * G::RW + lane + 64 * i] = lane + 64 * i < G::nn ? x[i] : 0.0f;
+                if (lane == 0) d.root_v[b] = v;
+            } else if (kind == LEAF_ROOT && root_noise) {
                 // mcts.py:113-116; float32 multiply, float64 add, float32 store
                 Plane occ;
 #pragma unroll
@@ -606,6 +636,36 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
         const double sq = DEEP ? sq_next : sq_lds[npar];      // np.sqrt(self.N + 1e-8), mcts.py:73
         double best = 0.0;
         int bi = -1, bN = 0, bC = 0;
+        if (gumbel && row == 0) {
+            // az_set_gumbel: sequential halving at the root.  Among the legal children whose visit count is the schedule's entry
+            // for this simulation, the first maximum of (g + logit) + sigma q; they all have equal N, so the choice is exact.
+            Edge er[G::CPL];
+            unsigned mxn = 0u;
+#pragma unroll
+            for (int i = 0; i < G::CPL; i++) {
+                const int j = lane + 64 * i;
+                if (j < G::nn && !pl_get(occ, j)) {
+                    er[i] = rows[j];
+                    mxn = (unsigned)er[i].N > mxn ? (unsigned)er[i].N : mxn;
+                }
+            }
+            mxn = wave_max_u(mxn);
+            const int kk = min_i(d.gumbel_m, G::nn - pl_count(occ));          // >= 1: an active slot has a legal cell
+            const int need = (int)d.gumbel_seq[(size_t)(kk > 0 ? kk - 1 : 0) * d.S + rootN];
+            const double sig = gumbel_sigma(d.gumbel_cv, d.gumbel_cs, (int)mxn);
+            const double *nz = d.noise + (size_t)game * d.noise_stride + d.noise_off[ply];
+            const float *rl = d.root_logits + (size_t)b * G::RW;
+#pragma unroll
+            for (int i = 0; i < G::CPL; i++) {
+                const int j = lane + 64 * i;
+                if (j < G::nn && !pl_get(occ, j) && (int)er[i].N == need) {
+                    const double h = nz[j - pl_rank(occ, j)] + (double)rl[j];
+                    const double Q = er[i].N ? er[i].W / (double)er[i].N : 0.0;
+                    const double sc = gumbel_score(h, sig, Q);
+                    if (bi < 0 || sc > best) { best = sc; bi = j; bN = er[i].N; bC = er[i].child; }
+                }
+            }
+        } else {
 #pragma unroll
         for (int i = 0; i < G::CPL; i++) {
             int j = lane + 64 * i;
@@ -616,6 +676,7 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
                 if (forced && row == 0 && forced_child((double)(int)e.N, d.forced_k, e.P, rootN)) sc = INFINITY;
                 if (bi < 0 || sc > best) { best = sc; bi = j; bN = e.N; bC = e.child; }
             }
+        }
         }
         wave_argmax(best, bi);
         const int a = __builtin_amdgcn_readfirstlane(bi);
@@ -988,7 +1049,7 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
 
 // numpy pairwise sum of a contiguous float64 block (n <= 128): np.add.reduce on a contiguous array accumulates in 8 lanes
 // over blocks of <= 128 and combines them pairwise; probs.sum() at mcts.py:163 goes through it
-__device__ inline double pw_block(const double *a, int n)
+__host__ __device__ inline double pw_block(const double *a, int n)
 {
     if (n < 8) {
         double r = 0.0;
@@ -1004,6 +1065,13 @@ __device__ inline double pw_block(const double *a, int n)
     double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
     for (; i < n; i++) res += a[i];
     return res;
+}
+// np.add.reduce of A <= 225 contiguous float64: one block up to 128 entries, else two halves (the first a multiple of 8)
+__host__ __device__ inline double pw_sum(const double *a, int A)
+{
+    int n2 = A / 2;
+    n2 -= n2 % 8;
+    return A <= 128 ? 0.0 + pw_block(a, A) : 0.0 + (pw_block(a, n2) + pw_block(a + n2, A - n2));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1075,9 +1143,60 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
             }
         }
     }
+    // ---- Gumbel root search (az_set_gumbel, noised roots only): the move is the best g + logit + sigma(q) among the most visited
+    // children, and pi the softmax of logit + sigma(completed q); the softmax itself is the temperature path's below ----
+    const bool gumbel = d.gumbel_m > 0 && d.add_noise && (d.cap_fast ? d.s_budget[b] : 1) > 0;
+    int ga = -1;
+    if (gumbel) {
+        const double *nz = d.noise + (size_t)g * d.noise_stride + d.noise_off[ply];
+        const float *rl = d.root_logits + (size_t)b * G::RW;
+        const int maxN = (int)(best >> 16);
+        const double sig = gumbel_sigma(d.gumbel_cv, d.gumbel_cs, maxN);
+        double q[G::CPL], Pd[G::CPL], lg[G::CPL];
+        double sc = 0.0;
+        int bi = -1, tot = 0;
+#pragma unroll
+        for (int i = 0; i < G::CPL; i++) {
+            const int j = lane + 64 * i;
+            q[i] = 0.0; Pd[i] = 0.0; lg[i] = 0.0;
+            if (legal[i]) {
+                const Edge ec = root[j];
+                lg[i] = (double)rl[j];
+                Pd[i] = Nj[i] ? (double)ec.P : 0.0;
+                q[i] = Nj[i] ? ec.W / (double)Nj[i] : 0.0;
+                tot += Nj[i];
+                if (Nj[i] == maxN) {
+                    const double sj = gumbel_score(nz[rank[i]] + lg[i], sig, q[i]);
+                    if (bi < 0 || sj > sc) { sc = sj; bi = j; }
+                }
+            }
+        }
+        wave_argmax(sc, bi);
+        ga = __builtin_amdgcn_readfirstlane(bi);
+        tot = wave_sum_i(tot);
+        // pv = sum of the visited children's priors, pq = sum of prior * q, both in np.add.reduce order over the legal cells
+        double pv = 0.0, pq = 0.0;
+#pragma unroll
+        for (int i = 0; i < G::CPL; i++)
+            if (legal[i]) ebuf[rank[i]] = Pd[i];
+        wave_mem_sync();
+        if (lane == 0) pv = pw_sum(ebuf, A);
+        wave_mem_sync();
+#pragma unroll
+        for (int i = 0; i < G::CPL; i++)
+            if (legal[i]) ebuf[rank[i]] = Pd[i] * q[i];
+        wave_mem_sync();
+        if (lane == 0) pq = pw_sum(ebuf, A);
+        wave_mem_sync();
+        pv = __shfl(pv, 0, 64);
+        pq = __shfl(pq, 0, 64);
+        const double vmix = gumbel_vmix(d.root_v[b], (double)tot, pv, pq);
+#pragma unroll
+        for (int i = 0; i < G::CPL; i++) e[i] = legal[i] ? gumbel_score(lg[i], sig, Nj[i] ? q[i] : vmix) : -INFINITY;
+    }
     bool uniform = false;
     double s = 1.0;
-    if (T <= 1e-7) {
+    if (!gumbel && T <= 1e-7) {
         // temperature clipped to the Python float 1e-7 -> float32 arithmetic, exp() is exactly 0 or 1
         float y[G::CPL], m = -INFINITY;
 #pragma unroll
@@ -1099,7 +1218,7 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
         double m = -INFINITY;
 #pragma unroll
         for (int i = 0; i < G::CPL; i++) {
-            e[i] = legal[i] ? (double)d.log_table[Np[i]] / T : -INFINITY;
+            if (!gumbel) e[i] = legal[i] ? (double)d.log_table[Np[i]] / T : -INFINITY;
             m = e[i] > m ? e[i] : m;
         }
         m = wave_max_d(m);
@@ -1143,7 +1262,7 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
         if (legal[i] && rank[i] == idx) mycell = lane + 64 * i;
     u64 bal = __ballot(mycell >= 0);
     int src = __ffsll((long long)bal) - 1;
-    const int a = __shfl(mycell, src, 64);
+    const int a = gumbel ? ga : __shfl(mycell, src, 64);      // a Gumbel ply uses neither the temperature nor u
 
     // ---- record (self_play.py:63): state before the move, pi, mover ----
     const size_t ri = (size_t)g * G::nn + ply;

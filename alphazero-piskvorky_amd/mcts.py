@@ -7,7 +7,7 @@ them to the engine, so np.random.seed(s) reproduces the reference's choices."""
 import numpy as np
 
 from . import constants as _c
-from ._capi import AZ_MAX_SIMULATIONS, FORCED_K_MAX, Engine
+from ._capi import AZ_MAX_SIMULATIONS, FORCED_K_MAX, GUMBEL_DEFAULTS, GUMBEL_M_MAX, Engine
 from .controller import BatchPolicyValueFn, PolicyValueFn, device_index, model_kind, weights_version
 
 
@@ -30,9 +30,35 @@ def check_forced_playouts(fp):
     return out
 
 
+def check_gumbel(gumbel, subtree_reuse=False, virtual_loss=1, forced_playouts=None, evaluator=None):
+    """None, or the dict a seam takes for the Gumbel root search (az_set_gumbel): m in 1..64 (default 16), c_visit >= 0 (50) and
+    c_scale > 0 (1).  Raises ValueError for the combinations the engine refuses: subtree reuse, virtual-loss batching, forced
+    playouts and an evaluator outside the engine (it returns priors, not logits)."""
+    if gumbel is None:
+        return None
+    extra = set(gumbel) - set(GUMBEL_DEFAULTS)
+    if extra:
+        raise ValueError(f"gumbel takes m, c_visit and c_scale, got {sorted(gumbel)}")
+    out = {"m": int(gumbel.get("m", GUMBEL_DEFAULTS["m"])), "c_visit": float(gumbel.get("c_visit", GUMBEL_DEFAULTS["c_visit"])),
+           "c_scale": float(gumbel.get("c_scale", GUMBEL_DEFAULTS["c_scale"]))}
+    if not 1 <= out["m"] <= GUMBEL_M_MAX:
+        raise ValueError(f"gumbel m must be in 1..{GUMBEL_M_MAX}, got {out['m']}")
+    if not (0.0 <= out["c_visit"] < float("inf")) or not (0.0 < out["c_scale"] < float("inf")):
+        raise ValueError(f"gumbel needs c_visit >= 0 and c_scale > 0, both finite, got {out['c_visit']} and {out['c_scale']}")
+    if subtree_reuse:
+        raise ValueError("the Gumbel root search does not combine with subtree_reuse")
+    if virtual_loss != 1:
+        raise ValueError("the Gumbel root search does not combine with virtual-loss batching")
+    if forced_playouts is not None:
+        raise ValueError("the Gumbel root search does not combine with forced playouts")
+    if evaluator is not None:
+        raise ValueError("the Gumbel root search needs the engine's own net: an outside evaluator returns priors, not logits")
+    return out
+
+
 class MCTS:
     def __init__(self, policy_value_fn, num_simulations, c_puct, dirichlet_alpha=0.3, dirichlet_weight=0.25, virtual_loss=1,
-                 forced_playouts=None):
+                 forced_playouts=None, gumbel=None):
         if not callable(policy_value_fn):
             raise TypeError("policy_value_fn must be callable: state -> (policy [n, n], value)")
         # make_policy_value_fn(controller): the leaves are evaluated inside the HIP engine.  Any other callable keeps the
@@ -51,6 +77,10 @@ class MCTS:
         # opt-in: dict(k, prune=True), forced playouts and policy target pruning in the searches with add_root_noise
         # (az_set_forced_playouts); the others are untouched
         self.forced_playouts = check_forced_playouts(forced_playouts)
+        # opt-in: dict(m=16, c_visit=50.0, c_scale=1.0), the Gumbel root search in the searches with add_root_noise (az_set_gumbel):
+        # they draw np.random.gumbel(size=legal) where the others draw the Dirichlet sample.  Controller-backed evaluators only.
+        self.gumbel = check_gumbel(gumbel, virtual_loss=virtual_loss, forced_playouts=self.forced_playouts,
+                                   evaluator=policy_value_fn if (self._external or self._batched) else None)
         self._engine = None
         self._version = None
         self._batch_engine = None             # run_many's own engine; run() and its one-slot engine are untouched by it
@@ -60,7 +90,15 @@ class MCTS:
         """a new engine takes the searches' forced-playout setting"""
         if self.forced_playouts is not None:
             eng.set_forced_playouts(self.forced_playouts["k"], self.forced_playouts["prune"])
+        if self.gumbel is not None:
+            eng.set_gumbel(min(self.gumbel["m"], eng.nn), self.gumbel["c_visit"], self.gumbel["c_scale"])     # a board has n * n cells
         return eng
+
+    def _root_noise(self, legal):
+        """the draws of one noised root from numpy's global RNG: the Dirichlet sample, or Gumbel(0, 1) under gumbel=..."""
+        if self.gumbel is not None:
+            return np.random.gumbel(size=legal)
+        return np.random.dirichlet([self.dirichlet_alpha] * legal)
 
     def _eng_external(self, n, k):
         if self._engine is None or (self._engine.n, self._engine.k) != (n, k):
@@ -105,7 +143,7 @@ class MCTS:
         legal = int((root_state.cells == 0).sum())
         if legal == 0:
             return np.zeros((n, n), dtype=np.float32), None            # mcts.py:152-153
-        noise = np.random.dirichlet([self.dirichlet_alpha] * legal) if add_root_noise else None
+        noise = self._root_noise(legal) if add_root_noise else None
         u = np.random.random_sample()
         if self._external:
             r = self._run_external(root_state, temperature, noise, u)
@@ -201,7 +239,7 @@ class MCTS:
             if legal == 0:
                 continue                                                # mcts.py:152-153: nothing is drawn
             if add_root_noise:
-                noise.append(np.random.dirichlet([self.dirichlet_alpha] * legal))
+                noise.append(self._root_noise(legal))
             us.append(np.random.random_sample())
             live.append(i)
         out = [(np.zeros((n, n), dtype=np.float32), None) for _ in range(count)]     # mcts.py:152-153 for the full boards

@@ -9,7 +9,7 @@ from . import constants as _c
 from . import parallel
 from ._capi import AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine, playout_cap_permille, resign_permille
 from .controller import BatchPolicyValueFn, device_index, model_kind
-from .mcts import check_forced_playouts, numpy_log_table
+from .mcts import check_forced_playouts, check_gumbel, numpy_log_table
 
 
 def default_temperature_schedule(move: int) -> float:
@@ -114,7 +114,7 @@ class SelfPlayManager:
                  engines_per_gpu: int = None, subtree_reuse: bool = False, gather_to: int = None,
                  eval_cache: int = 0, virtual_loss: int = 1, trunk: str = "f32", leaf_symmetry: bool = False,
                  start_positions=None, resign: dict = None, evaluator: BatchPolicyValueFn = None,
-                 playout_cap: dict = None, forced_playouts: dict = None):
+                 playout_cap: dict = None, forced_playouts: dict = None, gumbel: dict = None):
         self.controller = controller
         # opt-in: a controller.BatchPolicyValueFn evaluates every leaf instead of the engine's own net kernels (any torch
         # net on the same GPU; az_set_external_evaluator).  Not with subtree_reuse or leaf_symmetry; eval_cache and trunk
@@ -141,6 +141,11 @@ class SelfPlayManager:
         self.forced_playouts = check_forced_playouts(forced_playouts)
         if self.forced_playouts is not None and subtree_reuse:
             raise ValueError("forced playouts do not combine with subtree_reuse")
+        # opt-in Gumbel root search: dict(m=16, c_visit=50.0, c_scale=1.0); every noised root (with a playout cap: the full plies')
+        # samples m Gumbel-top candidates, searches them by sequential halving and records pi = softmax(logits + sigma(completed
+        # Q)) (az_set_gumbel); the engine fills the game tapes with Gumbel draws.  Not with subtree_reuse, virtual_loss > 1,
+        # forced_playouts or an external evaluator.
+        self.gumbel = check_gumbel(gumbel, subtree_reuse, virtual_loss, self.forced_playouts, evaluator)
         self.temperature_schedule = temperature_schedule
         self.concurrent_games = concurrent_games or _c.CONCURRENT_GAMES
         self.augmentation = augmentation      # 4 = the reference's rotations (self_play.py:94-108), 8 = full dihedral group, 1 = none
@@ -259,6 +264,11 @@ class SelfPlayManager:
             eng.set_forced_playouts(self.forced_playouts["k"], self.forced_playouts["prune"])
         elif eng.forced_playouts()["k"]:
             eng.set_forced_playouts(0.0)
+        self.gumbel = check_gumbel(self.gumbel, self.subtree_reuse, self.virtual_loss, self.forced_playouts, self.evaluator)
+        if self.gumbel is not None:
+            eng.set_gumbel(min(self.gumbel["m"], n * n), self.gumbel["c_visit"], self.gumbel["c_scale"])
+        elif eng.gumbel()["m"]:
+            eng.set_gumbel(0)
         if mine > 0:
             self.last_counters = eng.selfplay(mine, seed0=seed0 + lo, temperature_table=T)
             if self.resign is not None:

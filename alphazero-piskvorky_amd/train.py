@@ -28,7 +28,7 @@ PROMOTION_THRESHOLD = 0.55          # promoter.py:19, strict ">" with draws coun
 
 def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=None, log=print, device_replay=False,
         subtree_reuse=False, trunk="f32", eval_sims=None, start_positions=None, resign=None, torch_eval=False,
-        playout_cap=None, forced_playouts=None):
+        playout_cap=None, forced_playouts=None, gumbel=None):
     """eval_sims: simulations per move in the arena (evaluator.py:53-62 takes NUM_EVAL_SIMULATIONS = 200 whatever the
     self-play count is; main() passes that constant); None = as many as self-play, which keeps small test runs short.
     device_replay=True keeps the examples on the GPU from the episode-end gather to the optimizer step (packed records
@@ -44,6 +44,9 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
     forced_playouts: dict(k, prune) for the self-play games (Engine.set_forced_playouts): every noised root guarantees its
     children visits by the square root of their prior, and with prune the policy target leaves those visits out again.  The
     arena is untouched.
+    gumbel: dict(m, c_visit, c_scale) for the self-play games (Engine.set_gumbel): every noised root is searched by sequential
+    halving over m Gumbel-top candidates and the policy target is softmax(logits + sigma(completed Q)).  Not with
+    forced_playouts, subtree_reuse or torch_eval.  The arena is untouched.
     torch_eval=True: the searches of self-play and the arena are evaluated by the controllers' own torch modules on the GPU
     (controller.make_batch_policy_value_fn, az_set_external_evaluator) instead of the engine's net kernels -- the loop a
     changed net.py runs on before it has kernels of its own."""
@@ -58,7 +61,7 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
     manager = SelfPlayManager(candidate, device, mcts_params={"num_simulations": sims, "c_puct": C.SELF_PLAY_EXPLORATION_CONSTANT},
                               seed=seed, subtree_reuse=subtree_reuse, gather_to=0 if world > 1 else None, trunk=trunk,
                               start_positions=start_positions, resign=resign, playout_cap=playout_cap,
-                              forced_playouts=forced_playouts,
+                              forced_playouts=forced_playouts, gumbel=gumbel,
                               evaluator=make_batch_policy_value_fn(candidate.net, device) if torch_eval else None)
     evaluator = ModelEvaluator(game_class=Gomoku, print_games=False, device=device, seed=seed,
                                evaluators=True if torch_eval else None)
@@ -150,6 +153,11 @@ def main():
                          "are below K x prior x simulations so far (0 < K <= 16; KataGo uses 2), and the policy target is pruned")
     ap.add_argument("--no-target-pruning", action="store_true",
                     help="with --forced-playouts: keep the forced visits in the policy target")
+    ap.add_argument("--gumbel", type=int, default=None, metavar="M",
+                    help="Gumbel root search at the noised roots of self-play: M Gumbel-top candidates searched by sequential "
+                         "halving, policy target from the completed Q values (1 <= M <= 64; the paper uses 16)")
+    ap.add_argument("--gumbel-c-visit", type=float, default=None, metavar="X", help="with --gumbel: c_visit of sigma (default 50)")
+    ap.add_argument("--gumbel-c-scale", type=float, default=None, metavar="Y", help="with --gumbel: c_scale of sigma (default 1)")
     ap.add_argument("--torch-eval", action="store_true",
                     help="evaluate the searches with the controller's own torch module as a batched external evaluator "
                          "(any net; no HIP trunk needed) instead of the engine's net kernels")
@@ -170,6 +178,15 @@ def main():
         forced_playouts = {"k": a.forced_playouts, "prune": not a.no_target_pruning}
     elif a.no_target_pruning:
         ap.error("--no-target-pruning needs --forced-playouts")
+    gumbel = None
+    if a.gumbel is not None:
+        gumbel = {"m": a.gumbel}
+        if a.gumbel_c_visit is not None:
+            gumbel["c_visit"] = a.gumbel_c_visit
+        if a.gumbel_c_scale is not None:
+            gumbel["c_scale"] = a.gumbel_c_scale
+    elif a.gumbel_c_visit is not None or a.gumbel_c_scale is not None:
+        ap.error("--gumbel-c-visit and --gumbel-c-scale need --gumbel")
     start_positions = None
     if a.start_positions:
         with np.load(a.start_positions) as z:
@@ -185,7 +202,8 @@ def main():
         a.device = f"cuda:{local}"
     run(a.episodes, a.games, a.sims, a.eval_games, a.device, model_dir=a.model_dir, device_replay=a.device_replay,
         subtree_reuse=a.subtree_reuse, trunk=a.trunk, eval_sims=C.NUM_EVAL_SIMULATIONS, start_positions=start_positions,
-        resign=resign, torch_eval=a.torch_eval, playout_cap=playout_cap, forced_playouts=forced_playouts)
+        resign=resign, torch_eval=a.torch_eval, playout_cap=playout_cap, forced_playouts=forced_playouts,
+        gumbel=gumbel)
     if world > 1:
         td.barrier()
         td.destroy_process_group()

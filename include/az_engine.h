@@ -377,6 +377,9 @@ int az_rules_replay(az_engine *e, int games, int max_len, const int16_t *actions
 /* ---- host-side numpy-compatible RNG (legacy MT19937 RandomState; mcts.py:114,177) ---- */
 int az_rng_selfplay_tape(uint64_t seed, int board_size, double alpha, int max_plies, double *noise, double *u);
 int az_rng_uniforms(uint64_t seed, int count, double *u);
+/* az_set_gumbel's tape: per ply p, n * n - p draws of RandomState(seed).gumbel() (-log(-log(1 - U)), one random_sample each) and
+ * then one uniform, in az_rng_selfplay_tape's layout */
+int az_rng_selfplay_tape_gumbel(uint64_t seed, int board_size, int max_plies, double *noise, double *u);
 
 /* Opt-in search upgrade the reference lists as a TODO (mcts.py:17-22 "subtree reuse", mcts.py:106 builds a new root
  * every run): after a self-play move the chosen child's subtree becomes the next ply's tree.  The retained root keeps
@@ -583,6 +586,61 @@ int az_selfplay_export_count(az_engine *e, int64_t *records);
 int az_set_forced_playouts(az_engine *e, double k, int prune);
 int az_get_forced_playouts(const az_engine *e, double *k, int *prune);
 int64_t az_forced_prune(double k, double c_puct, int count, const int32_t *visits, const double *W, const float *prior, int32_t *out);
+
+/* Opt-in Gumbel root search ("Policy improvement by planning with Gumbel", Danihelka et al., ICLR 2022): instead of Dirichlet
+ * noise, PUCT at the root and the visit-count target, the root samples Gumbel-top-m candidates without replacement, spends a
+ * fixed sequential-halving schedule on them and trains on softmax(logits + sigma(completed Q)).  Made for 16 to 64 simulations
+ * per move.  Values are in [-1, 1] from the mover's side; there is no min-max rescaling.
+ *
+ * Rule.  az_set_gumbel(m, c_visit, c_scale).  m = 0 switches the option off, which is the default; otherwise
+ * 1 <= m <= min(n * n, 64), c_visit >= 0 and c_scale > 0, both finite (the paper: m = 16, c_visit = 50, c_scale = 1).  It
+ * applies in every search whose root would receive Dirichlet noise, and only at that root: the self-play plies that are not
+ * FAST plies of the playout cap, and az_search / az_search_batch with noise != NULL.  az_arena, FAST plies and searches without
+ * noise are untouched, byte for byte; below the root the search stays PUCT exactly as it is.
+ *   Noise.  At such a root the noise values are not mixed into the priors: the edge keeps the plain float32 softmax prior.  The
+ *   noise values are read as Gumbel(0, 1) draws g over the legal cells in row-major order -- same place, stride and offsets as
+ *   the Dirichlet sample.  An episode begun with the option on fills the tapes it generates itself with
+ *   RandomState(seed0 + game).gumbel() draws (az_rng_selfplay_tape_gumbel: per ply p, n * n - p draws, then one uniform); an
+ *   explicit noise_tape is taken as given.  The uniforms of a generated tape are therefore not those of the Dirichlet tape of
+ *   the same seed (a Gumbel draw takes one random_sample, a Dirichlet sample a varying number): the FAST plies of a capped
+ *   episode are searched as without the option, but on generated tapes they sample their moves with other uniforms.
+ *   Schedule, a pure function of (k, S) (az_gumbel_schedule).  For k <= 1 it is 0, 1, .., S - 1.  Otherwise L = ceil(log2 k),
+ *   visits[0 .. k) = 0, c = k; until S entries exist: extra = max(1, S / (L * c)) in integers; extra times: append
+ *   visits[0 .. c), then increment those c entries; then c = max(2, c / 2).  Truncated to S entries.  seq_k[t] is the visit
+ *   count a root child must have to be selectable at simulation t.  A root uses k = min(m, number of legal cells).
+ *   Root selection at simulation t (t = the simulations finished so far).  maxN = the largest visit count among the legal root
+ *   children before this simulation; sig = (c_visit + (double)maxN) * c_scale; h_c = (double)g[rank(c)] + (double)logit_c, one
+ *   float64 add, logit_c the float32 logit the softmax consumes (read through the leaf symmetry where that option is on);
+ *   q_c = W_c / N_c, or 0.0 when unvisited; score_c = h_c + sig * q_c with a separate multiply and add.  Among the legal cells
+ *   with N_c == seq_k[t] the first maximum in row-major order is taken.  The candidates of one simulation have equal N, so
+ *   every selection is exact in float64.
+ *   Move.  After the last simulation: among the legal cells with N_c == maxN, the first maximum of score_c.  Temperature and u
+ *   are not used on such a ply (the tape still carries u).
+ *   Policy target.  v0 = the root's float32 value, widened.  Over the legal cells in row-major order, with float64 pairwise
+ *   sums in np.add.reduce order: sumN = sum N_c; pv = sum (double)P_c over the visited cells (unvisited ones add 0.0);
+ *   pq = sum (double)P_c * q_c likewise; v_mix = (v0 + (sumN / pv) * pq) / (1 + sumN); qh_c = q_c if visited, else v_mix;
+ *   y_c = (double)logit_c + sig * qh_c with sig from the final maxN; pi_c = exp(y_c - max y) / sum, the exp and the pairwise
+ *   sum being those of the temperature path, stored as float32.  The record's pi and the pi output of the searches is this.
+ *   Everything else stays on the raw tree as without the option: visits, W, prior (the unmixed softmax), the search value
+ *   W[a*] / N[a*] of the most visited cell, resignation, the counters.
+ * az_gumbel_schedule(k, S, out) writes seq_k[0 .. S) (no GPU needed).  az_gumbel_target(count, logits, g, visits, W, prior,
+ * root_value, c_visit, c_scale, pi, action) restates move and policy target on the host for one root row of `count` legal
+ * children with the functions the kernel uses: pi[0 .. count) and the index of the chosen child.  Both return AZ_ERR_INVALID for
+ * a bad argument (a null pointer, count outside 1 .. 225, a count outside 0 .. 65535, no visit at all, constants out of range).
+ * Combines with the evaluation cache, leaf symmetry, both nets, the emulated trunks, deep engines, start positions,
+ * resignation, max_plies, the playout cap (FULL plies only get the rule), both step APIs and the persistent search kernel,
+ * which stays in use.  Refused with AZ_ERR_INVALID, whichever is set first: subtree reuse, virtual-loss batching (in-flight
+ * counts under the equal-N gate need a definition of their own), forced playouts (both rules own the root selection), the
+ * external evaluator (it returns priors, not logits) and engines created with AZ_EVAL_SYNTHETIC; az_search_callback with noise
+ * and the option set returns AZ_ERR_INVALID as well.
+ * AZ_ERR_INVALID for arguments out of range (the previous setting is kept), AZ_ERR_STATE while an episode is open. */
+int az_set_gumbel(az_engine *e, int m, double c_visit, double c_scale);
+int az_get_gumbel(const az_engine *e, int *m, double *c_visit, double *c_scale);
+int az_gumbel_schedule(int k, int S, int32_t *out);
+int az_gumbel_target(int count, const float *logits, const double *g, const int32_t *visits, const double *W, const float *prior,
+                     float root_value, double c_visit, double c_scale, float *pi, int32_t *action);
+/* v_mix alone, as az_gumbel_target forms it: NaN for a bad argument */
+double az_gumbel_vmix(int count, const int32_t *visits, const double *W, const float *prior, float root_value);
 
 /* Opt-in: fp32-emulating conv trunks.  AZ_TRUNK_F32 (default) computes the net's forward (net.py:55-72) on the float32
  * matrix instruction in the build's canonical fp order: bit-identical to the oracle.  The other two run every conv but the
