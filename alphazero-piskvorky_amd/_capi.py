@@ -39,6 +39,7 @@ EXPORTS = [
     "az_set_forced_playouts", "az_get_forced_playouts", "az_forced_prune",
     "az_set_gumbel", "az_get_gumbel", "az_gumbel_schedule", "az_gumbel_target", "az_gumbel_vmix", "az_rng_selfplay_tape_gumbel",
     "az_set_external_evaluator", "az_get_external_evaluator", "az_ext_capacity", "az_ext_stats",
+    "az_set_solver", "az_get_solver", "az_last_proof", "az_selfplay_proofs", "az_solver_counts", "az_solver_stops",
     "az_dist_unique_id", "az_dist_init", "az_dist_rank", "az_dist_world", "az_dist_counts", "az_dist_gather_records",
     "az_dist_allreduce_sum", "az_dist_broadcast",
 ]
@@ -177,6 +178,13 @@ def lib():
             L.az_get_external_evaluator.argtypes = [C.c_void_p]
             L.az_ext_capacity.argtypes = [C.c_void_p]
             L.az_ext_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        if hasattr(L, "az_set_solver"):
+            L.az_set_solver.argtypes = [C.c_void_p, C.c_int]
+            L.az_get_solver.argtypes = [C.c_void_p]
+            L.az_last_proof.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+            L.az_solver_stops.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+            L.az_selfplay_proofs.argtypes = [C.c_void_p, C.c_void_p]
+            L.az_solver_counts.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -267,6 +275,22 @@ def forced_prune(k, c_puct, visits, W, prior):
     if removed < 0:
         raise ValueError(f"az_forced_prune refused its arguments (k {k} in (0, {FORCED_K_MAX:g}], counts 0..65534 with at least one visit)")
     return out, removed
+
+
+PROOF_UNKNOWN, PROOF_WIN, PROOF_LOSS, PROOF_DRAW = 0, 1, 2, 3    # az_set_solver: AZ_PROOF_*
+
+
+def solver_counts(visits, status):
+    """The count vector N' the solver makes pi and the move from (az_solver_counts; needs no GPU): visits int[count] and
+    status int8[count] (PROOF_*) of the LEGAL children of one root in row-major order -> int32[count]."""
+    visits = np.ascontiguousarray(visits, np.int32)
+    status = np.ascontiguousarray(status, np.int8)
+    if not (visits.ndim == 1 and visits.shape == status.shape):
+        raise ValueError("solver_counts takes two one-dimensional arrays of one length")
+    out = np.zeros(len(visits), np.int32)
+    if lib().az_solver_counts(len(visits), _p(visits), _p(status), _p(out)):
+        raise ValueError("az_solver_counts refused its arguments (at least one child, counts >= 0, statuses 0..3)")
+    return out
 
 
 GUMBEL_M_MAX = 64                                              # az_set_gumbel: m <= min(n * n, 64)
@@ -420,6 +444,7 @@ class Engine:
         a = C.c_int32(-1)
         self._check(lib().az_search(self.h, int(slot), _p(board), int(player), int(last), C.c_double(temperature),
                                     _dp(nz), C.c_double(u), _p(pi), C.byref(a), _p(N), _p(W), _p(P)), "az_search")
+        self._last_search_batched = False
         return dict(action=int(a.value), pi=pi, N=N, W=W, P=P)
 
     # ---- many searches at once ----
@@ -464,6 +489,7 @@ class Engine:
         a = np.full(cnt, -1, np.int32)
         self._check(lib().az_search_batch(self.h, int(slot), cnt, _p(boards), _p(players), _p(lasts), _p(T), _p(nz), _p(uu),
                                           _p(pi), _p(a), _p(N), _p(W), _p(P)), "az_search_batch")
+        self._last_search_batched = True
         return dict(action=a, pi=pi, N=N, W=W, P=P)
 
     _EVAL_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float))
@@ -768,6 +794,41 @@ class Engine:
         k, p = C.c_double(0.0), C.c_int(0)
         self._check(lib().az_get_forced_playouts(self.h, C.byref(k), C.byref(p)), "az_get_forced_playouts")
         return dict(k=float(k.value), prune=bool(p.value))
+
+    # ---- MCTS-Solver ----
+    def set_solver(self, on=True):
+        """Opt-in (Winands et al. 2008): every search keeps proven wins, losses and draws in its tree, propagates them by minimax,
+        never samples a refuted move when a better one is known and reports an exact value for a proven root.  See
+        include/az_engine.h."""
+        self._check(lib().az_set_solver(self.h, 1 if on else 0), "az_set_solver")
+
+    def solver(self):
+        """True while the solver is on (az_get_solver)."""
+        return lib().az_get_solver(self.h) == 1
+
+    def proofs(self):
+        """int8 root status (PROOF_*) of every record of the last episode, in the order of records() (az_selfplay_proofs)."""
+        v = np.zeros(self.last_records, np.int8)
+        self._check(lib().az_selfplay_proofs(self.h, _p(v)), "az_selfplay_proofs")
+        return v
+
+    def last_proof(self):
+        """(edges, root) of the last search(): int8[n*n] statuses of the root's edges (0 on occupied cells) and the root's own;
+        after search_batch(): int8[count, n*n] and int8[count] (az_last_proof)."""
+        cnt = C.c_int32(0)
+        self._check(lib().az_last_proof(self.h, 0, None, None, C.byref(cnt)), "az_last_proof")
+        cnt = int(cnt.value)
+        edges = np.zeros((cnt, self.nn), np.int8); roots = np.zeros(cnt, np.int8)
+        self._check(lib().az_last_proof(self.h, cnt, _p(edges), _p(roots), None), "az_last_proof")
+        if not getattr(self, "_last_search_batched", False):
+            return edges[0], int(roots[0])
+        return edges, roots
+
+    def solver_stops(self):
+        """Simulations of the last episode / search call that ended on a proven edge (az_solver_stops)."""
+        v = C.c_int64(0)
+        self._check(lib().az_solver_stops(self.h, C.byref(v)), "az_solver_stops")
+        return int(v.value)
 
     # ---- Gumbel root search ----
     def set_gumbel(self, m, c_visit=50.0, c_scale=1.0):

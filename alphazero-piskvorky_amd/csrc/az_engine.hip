@@ -60,6 +60,7 @@ struct Lane {
     DevBuf inflight;               // per slot, deep engines with virtual-loss batching only: in-flight count of every edge
     DevBuf budget, cp_board, cp_state;     // per slot, playout cap: the ply's simulation budget, and the staging of k_refill's partition
     DevBuf root_logits, root_v;            // per slot, az_set_gumbel: the root's logits row and value of the running ply (allocated by the setter)
+    DevBuf proof, root_proof, proof_stops; // per slot, az_set_solver: the status of every edge and of the root, the stops on proven edges (allocated by the setter)
     // one ply (k_begin, (S+1) x {trunk, fc, step}, k_move) captured once as a hipGraph and replayed every ply:
     // 3(S+1)+2 launches (6(S+1)+2 with the split trunk) become one submission.  Indexed [split trunk][arena].
     struct PlyGraph {
@@ -140,6 +141,13 @@ struct az_engine {
     int gumbel_m = 0;
     double gumbel_cv = 50.0, gumbel_cs = 1.0;
     DevBuf gumbel_seq;
+    // az_set_solver: 0 = off; the root status of every record, and what az_last_proof hands out (the root rows and root
+    // statuses of the last az_search / az_search_batch, occupied cells 0)
+    int solver = 0;
+    int64_t solver_stops = 0;      // simulations of the last (or open) episode / search call that ended on a proven edge
+    int episode_solver = 0;        // ... and whether the last (or open) episode ran with it: az_selfplay_proofs speaks of that one
+    DevBuf rec_proof;
+    std::vector<int8_t> proof_edges, proof_roots;
     PackedNet net[2];
     az_counters last{};
     // running episode (az_selfplay_begin .. az_selfplay_end)
@@ -742,6 +750,7 @@ static int create_engine(const az_config *cfg, az_engine **out, bool deep)
         d.cap_fast = 0; d.cap_permille = 0;
         d.forced_k = 0.0; d.forced_prune = 0;
         d.gumbel_m = 0; d.gumbel_cv = 0.0; d.gumbel_cs = 0.0; d.gumbel_seq = nullptr; d.root_logits = nullptr; d.root_v = nullptr;
+        d.proof = nullptr; d.proof_buf = nullptr; d.root_proof = nullptr; d.rec_proof = nullptr; d.proof_stops = nullptr;
         d.s_budget = (int *)L.budget.p; d.cp_board = (u64 *)L.cp_board.p; d.cp_state = (int *)L.cp_state.p;
         if (!rc) rc = alloc_items(e, L, 1);
     }
@@ -813,7 +822,7 @@ extern "C" void az_destroy(az_engine *e)
         DevBuf *all[] = {&L.board, &L.s_game, &L.s_ply, &L.s_player, &L.s_last, &L.s_status, &L.s_net, &L.edges, &L.rows_used,
                          &L.path, &L.depth, &L.leaf_kind, &L.leaf, &L.leaf_last, &L.logits, &L.vhid, &L.pol_feat, &L.cnt,
                          &L.active_dev, &L.carried, &L.dbg, &L.scratch, &L.it_status, &L.it_net, &L.leaf_sym, &L.inflight,
-                         &L.budget, &L.cp_board, &L.cp_state, &L.root_logits, &L.root_v};
+                         &L.budget, &L.cp_board, &L.cp_state, &L.root_logits, &L.root_v, &L.proof, &L.root_proof, &L.proof_stops};
         for (DevBuf *b : all) dev_free(*b);
         for (hipEvent_t ev : L.ev) (void)hipEventDestroy(ev);
         for (int i = 0; i < 4; i++)
@@ -822,7 +831,7 @@ extern "C" void az_destroy(az_engine *e)
     DevBuf *shared[] = {&e->T_table, &e->log_table, &e->sqrt_table, &e->noise_off, &e->next_game, &e->noise, &e->u,
                         &e->rec_planes, &e->rec_last, &e->rec_action, &e->rec_mover, &e->rec_pi, &e->rec_visits, &e->g_nply,
                         &e->g_result, &e->src_index, &e->rec_value, &e->g_cross, &e->cache, &e->start_tab, &e->bt_cells, &e->bt_players, &e->bt_lasts, &e->bt_T,
-                        &e->bt_zero_off, &e->bt_visits, &e->bt_W, &e->bt_prior, &e->bt_pi, &e->bt_action, &e->ext.map, &e->ext.count, &e->gumbel_seq};
+                        &e->bt_zero_off, &e->bt_visits, &e->bt_W, &e->bt_prior, &e->bt_pi, &e->bt_action, &e->ext.map, &e->ext.count, &e->gumbel_seq, &e->rec_proof};
     for (DevBuf *b : shared) dev_free(*b);
     for (int s = 0; s < 2; s++) {
         PackedNet &p = e->net[s];
@@ -978,6 +987,7 @@ static int ensure_episode_buffers(az_engine *e, int games, bool need_noise)
     ALLOC(rec_pi, G * nn * nn * 4, false); ALLOC(rec_visits, G * nn * nn * 2, false);
     ALLOC(g_nply, G * 4, true); ALLOC(g_result, G * 4, true);
     ALLOC(rec_value, G * nn * 4, false); ALLOC(g_cross, G * 4, false);
+    if (e->solver) ALLOC(rec_proof, G * nn, false);
     if (!rc) HIPCHECK(e, hipMemsetAsync(e->g_cross.p, 0xFF, G * 4, e->stream));      // -1: no game has crossed
     ALLOC(u, G * nn * sizeof(double), false);
     if (need_noise) ALLOC(noise, G * (size_t)e->tape_len * sizeof(double), false);
@@ -1071,15 +1081,21 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
         d.gumbel_m = sp.add_noise && !sp.arena ? e->gumbel_m : 0;
         d.gumbel_cv = d.gumbel_m ? e->gumbel_cv : 0.0;
         d.gumbel_cs = d.gumbel_m ? e->gumbel_cs : 0.0;
+        // the solver is for every search; the slot's status arrays were put into the state by az_set_solver
+        d.proof = e->solver ? d.proof_buf : nullptr;
+        d.rec_proof = e->solver ? (signed char *)e->rec_proof.p : nullptr;
     });
+    e->episode_solver = e->solver;
+    e->solver_stops = 0;
+    if (!sp.preset) { e->proof_edges.clear(); e->proof_roots.clear(); }     // az_last_proof speaks of the last preset search only
     const bool capped = !sp.preset && !sp.arena && e->cap_fast > 0;
     // persistent search kernel: plain net or synthetic evaluator, the reference's sequential search, trees that fit into LDS
     e->persist_gp = 0;
     if (e->persist_allowed && !ext && !e->vl_kernel && !capped && e->trunk_mode == AZ_TRUNK_F32) {
         const int synth = e->cfg.eval_kind == AZ_EVAL_SYNTHETIC ? 1 : 0;
         const int S = e->cfg.num_simulations;
-        if (!sp.arena && (!sp.preset || sp.batch) && e->ops->search_prepare(S, 2, synth, e->cfg.model)) e->persist_gp = 2;
-        else if (e->ops->search_prepare(S, 1, synth, e->cfg.model)) e->persist_gp = 1;     // arena: a workgroup's games must share one net
+        if (!sp.arena && (!sp.preset || sp.batch) && e->ops->search_prepare(S, 2, synth, e->cfg.model, e->solver)) e->persist_gp = 2;
+        else if (e->ops->search_prepare(S, 1, synth, e->cfg.model, e->solver)) e->persist_gp = 1;     // arena: a workgroup's games must share one net
     }
     az_engine::Run &r = e->run;
     r = az_engine::Run();
@@ -1105,6 +1121,7 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
         L.active = 0; L.n_full = 0; L.refill_out[0] = L.refill_out[1] = 0; L.cur = L.d.B; L.plies_played = 0; L.steps = L.trunk_launches = L.plies = 0;
         L.trunk_ms = L.nn_ms = L.step_ms = 0.0; L.tape_wait_s = 0.0; L.rc = AZ_OK; L.err.clear();
         HIPCHECK(e, hipMemsetAsync(L.cnt.p, 0, L.cnt.bytes, L.stream));
+        if (e->solver) HIPCHECK(e, hipMemsetAsync(L.proof_stops.p, 0, L.proof_stops.bytes, L.stream));
         HIPCHECK(e, hipMemsetAsync(L.carried.p, 0xFF, L.carried.bytes, L.stream));      // -1: every slot starts from a fresh root
         if (!sp.preset) {
             HIPCHECK(e, hipMemsetAsync(L.s_status.p, 0, L.s_status.bytes, L.stream));
@@ -1481,7 +1498,7 @@ static int read_counters(az_engine *e, az_counters &c)
     c.expansions = c.simulations = c.terminal_hits = c.depth_sum = 0;
     c.steps = c.trunk_launches = c.plies = 0;
     c.duplicate_leaves = c.cache_lookups = c.cache_hits = 0;
-    int64_t reused = 0;
+    int64_t reused = 0, stops = 0;
     double trunk_ms = 0.0, nn_ms = 0.0, step_ms = 0.0, tape_wait = 0.0;
     for (Lane &L : e->lanes) {
         std::vector<unsigned long long> hc((size_t)L.d.B * CNT_STRIDE);
@@ -1496,10 +1513,16 @@ static int read_counters(az_engine *e, az_counters &c)
             c.cache_lookups += (int64_t)hc[(size_t)b * CNT_STRIDE + 6];
             c.cache_hits += (int64_t)hc[(size_t)b * CNT_STRIDE + 7];
         }
+        if (e->episode_solver && L.proof_stops.p) {
+            std::vector<unsigned long long> hs((size_t)L.d.B);
+            HIPCHECK(e, az_memcpy(L.stream, hs.data(), L.proof_stops.p, hs.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            for (unsigned long long x : hs) stops += (int64_t)x;
+        }
         c.steps += L.steps; c.trunk_launches += L.trunk_launches; c.plies += L.plies;
         trunk_ms += L.trunk_ms; nn_ms += L.nn_ms; step_ms += L.step_ms;
         if (L.tape_wait_s > tape_wait) tape_wait = L.tape_wait_s;
     }
+    e->solver_stops = stops;
     c.tape_wait_seconds = tape_wait;
     c.tape_threads = e->tapes || e->stream_tapes ? e->tape_threads : 0;
     c.host_cpus = e->host_cpus;
@@ -1873,6 +1896,7 @@ extern "C" int az_set_forced_playouts(az_engine *e, double k, int prune)
         return fail(e, AZ_ERR_INVALID, "az_set_forced_playouts: k %g (0 = off, else in (0, 16]), prune %d (0 / 1)", k, prune);
     if (e->reuse) return fail(e, AZ_ERR_INVALID, "forced playouts and subtree reuse cannot be combined");
     if (e->gumbel_m > 0) return fail(e, AZ_ERR_INVALID, "forced playouts and the Gumbel root search cannot be combined");
+    if (e->solver) return fail(e, AZ_ERR_INVALID, "the solver and forced playouts cannot be combined");
     e->forced_k = k; e->forced_prune = prune;
     return AZ_OK;
 }
@@ -1950,6 +1974,7 @@ extern "C" int az_set_gumbel(az_engine *e, int m, double c_visit, double c_scale
     if (e->forced_k > 0.0) return fail(e, AZ_ERR_INVALID, "forced playouts and the Gumbel root search cannot be combined");
     if (e->ext.on) return fail(e, AZ_ERR_INVALID, "the Gumbel root search and the external evaluator cannot be combined (it returns priors, not logits)");
     if (e->cfg.eval_kind == AZ_EVAL_SYNTHETIC) return fail(e, AZ_ERR_INVALID, "the Gumbel root search needs a net: the synthetic evaluator has no logits");
+    if (e->solver) return fail(e, AZ_ERR_INVALID, "the solver and the Gumbel root search cannot be combined");
     DEVICE_GUARD(e);
     // the schedules of k = 1 .. m candidates (a root has min(m, legal cells) of them), one row of S entries each
     const int S = e->cfg.num_simulations;
@@ -2153,6 +2178,114 @@ extern "C" int az_net_eval(az_engine *e, int slot, int count, const uint8_t *boa
     return rc;
 }
 
+// ---- MCTS-Solver: proven wins, losses and draws in the search tree ----
+// the root rows and root statuses of the first m slots of a lane, after a preset search, into e->proof_edges / proof_roots
+// from position `at` on; boards = those positions' cells (an occupied cell reports 0)
+static int fetch_proofs(az_engine *e, Lane &L, int m, const uint8_t *boards, size_t at)
+{
+    const size_t nn = (size_t)e->nn, pitch = (size_t)e->R * e->RW;
+    if (e->proof_edges.size() < (at + m) * nn) { e->proof_edges.resize((at + m) * nn); e->proof_roots.resize(at + m); }
+    HIPCHECK(e, az_memcpy2d(e->stream, e->proof_edges.data() + at * nn, nn, L.proof.p, pitch, nn, (size_t)m, hipMemcpyDeviceToHost));
+    HIPCHECK(e, az_memcpy(e->stream, e->proof_roots.data() + at, L.root_proof.p, (size_t)m, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < (size_t)m * nn; i++)
+        if (boards[i]) e->proof_edges[at * nn + i] = 0;
+    return AZ_OK;
+}
+
+extern "C" int az_set_solver(az_engine *e, int on)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_solver: an episode is open (az_selfplay_end first)");
+    if (on != 0 && on != 1) return fail(e, AZ_ERR_INVALID, "az_set_solver: on %d (0 / 1)", on);
+    if (!on) {
+        e->solver = 0;
+        e->proof_edges.clear(); e->proof_roots.clear();
+        return AZ_OK;
+    }
+    if (e->reuse) return fail(e, AZ_ERR_INVALID, "the solver and subtree reuse cannot be combined");
+    if (e->vl > 1 || e->vl_kernel) return fail(e, AZ_ERR_INVALID, "the solver and virtual-loss batching cannot be combined");
+    if (e->forced_k > 0.0) return fail(e, AZ_ERR_INVALID, "the solver and forced playouts cannot be combined");
+    if (e->gumbel_m > 0) return fail(e, AZ_ERR_INVALID, "the solver and the Gumbel root search cannot be combined");
+    if (e->ext.on) return fail(e, AZ_ERR_INVALID, "the solver and the external evaluator cannot be combined");
+    if (e->cfg.eval_kind == AZ_EVAL_SYNTHETIC) return fail(e, AZ_ERR_INVALID, "the solver and the synthetic evaluator cannot be combined");
+    DEVICE_GUARD(e);
+    // one status byte per edge beside every slot's tree
+    size_t need = 0;
+    for (Lane &L : e->lanes)
+        if (!L.proof.p) need += (size_t)L.d.B * (size_t)e->R * (size_t)e->RW;
+    if (need && e->deep) {
+        int rc = deep_memory_guard("the edge statuses of the solver", need, e);
+        if (rc) return rc;
+    }
+    int rc = AZ_OK;
+    for (Lane &L : e->lanes) {
+        if (!rc && !L.proof.p) rc = dev_alloc(e, L.proof, (size_t)L.d.B * (size_t)e->R * (size_t)e->RW);
+        if (!rc && !L.root_proof.p) rc = dev_alloc(e, L.root_proof, (size_t)L.d.B);
+        if (!rc && !L.proof_stops.p) rc = dev_alloc(e, L.proof_stops, (size_t)L.d.B * sizeof(unsigned long long));
+    }
+    if (rc) return rc;
+    HIPCHECK(e, hipStreamSynchronize(e->stream));
+    for (Lane &L : e->lanes) {
+        L.d.proof_buf = (unsigned char *)L.proof.p;
+        L.d.root_proof = (signed char *)L.root_proof.p;
+        L.d.proof_stops = (unsigned long long *)L.proof_stops.p;
+    }
+    each_state(e, [&](DevState &d) { (void)d; });        // refresh the item views
+    e->solver = 1;
+    return AZ_OK;
+}
+
+extern "C" int az_get_solver(const az_engine *e) { return e ? e->solver : AZ_ERR_INVALID; }
+
+extern "C" int az_last_proof(az_engine *e, int capacity, int8_t *edges, int8_t *roots, int32_t *count)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (!e->solver || e->proof_roots.empty()) return fail(e, AZ_ERR_STATE, "az_last_proof: no az_search / az_search_batch has run with the solver on");
+    const int have = (int)e->proof_roots.size();
+    if (count) *count = have;
+    if ((edges || roots) && capacity < have)
+        return fail(e, AZ_ERR_INVALID, "az_last_proof: the buffers hold %d positions, the last search had %d", capacity, have);
+    if (edges) memcpy(edges, e->proof_edges.data(), (size_t)have * e->nn);
+    if (roots) memcpy(roots, e->proof_roots.data(), (size_t)have);
+    return AZ_OK;
+}
+
+extern "C" int az_solver_stops(const az_engine *e, int64_t *stops)
+{
+    if (!e || !stops) return AZ_ERR_INVALID;
+    *stops = e->solver_stops;
+    return AZ_OK;
+}
+
+extern "C" int az_selfplay_proofs(az_engine *e, int8_t *roots)
+{
+    if (!e || !e->have_episode) return fail(e, AZ_ERR_STATE, "no episode has been run");
+    if (!roots) return fail(e, AZ_ERR_INVALID, "az_selfplay_proofs: null buffer");
+    if (!e->episode_solver || !e->rec_proof.p) return fail(e, AZ_ERR_STATE, "az_selfplay_proofs: the episode ran without the solver");
+    DEVICE_GUARD(e);
+    const int nn = e->nn, G = e->episode_games;
+    std::vector<int8_t> val((size_t)G * nn);
+    HIPCHECK(e, az_memcpy(e->stream, val.data(), e->rec_proof.p, val.size(), hipMemcpyDeviceToHost));
+    size_t r = 0;
+    for (int g = 0; g < G; g++)
+        for (int m = 0; m < e->h_nply[g]; m++) roots[r++] = val[(size_t)g * nn + e->h_start[g] + m];
+    return AZ_OK;
+}
+
+// k_move's count vector N' of one root row of `count` legal children, with the function the kernel uses (az_tree.h)
+extern "C" int az_solver_counts(int count, const int32_t *visits, const int8_t *status, int32_t *out)
+{
+    if (count < 1 || !visits || !status || !out) return AZ_ERR_INVALID;
+    bool any_win = false, survivor = false;
+    for (int c = 0; c < count; c++) {
+        if (visits[c] < 0 || status[c] < 0 || status[c] > 3) return AZ_ERR_INVALID;
+        any_win = any_win || status[c] == PROOF_WIN;
+        survivor = survivor || (status[c] != PROOF_LOSS && visits[c] > 0);
+    }
+    for (int c = 0; c < count; c++) out[c] = solver_keeps(status[c], any_win, survivor) ? visits[c] : 0;
+    return AZ_OK;
+}
+
 extern "C" int az_search(az_engine *e, int slot, const uint8_t *board, int player, int last, double temperature,
                          const double *noise, double u, float *pi, int32_t *action, int32_t *visits, double *W,
                          float *prior)
@@ -2168,6 +2301,7 @@ extern "C" int az_search(az_engine *e, int slot, const uint8_t *board, int playe
     }
     if (stones >= nn) return fail(e, AZ_ERR_INVALID, "az_search: no legal action");
     if (last >= nn || (last >= 0 && board[last] == 0)) return fail(e, AZ_ERR_INVALID, "az_search: bad last action");
+    e->proof_edges.clear(); e->proof_roots.clear();
     int rc = ensure_episode_buffers(e, 1, true);
     if (rc) return rc;
     std::vector<double> T(nn + 1, temperature);
@@ -2221,6 +2355,7 @@ extern "C" int az_search(az_engine *e, int slot, const uint8_t *board, int playe
             if (prior) prior[j] = legal ? row[j].P : 0.0f;
         }
     }
+    if (e->solver && (rc = fetch_proofs(e, L0, 1, board, 0))) return rc;
     e->have_episode = false;
     return AZ_OK;
 }
@@ -2263,6 +2398,7 @@ extern "C" int az_search_batch(az_engine *e, int slot, int count, const uint8_t 
     if (!e->ext.on && e->cfg.eval_kind == AZ_EVAL_NET && !e->net[slot].loaded) return fail(e, AZ_ERR_NO_WEIGHTS, "weights slot %d not loaded", slot);
     if (K > BATCH_MAX_LANES) return fail(e, AZ_ERR_INVALID, "az_search_batch: more than %d lanes", BATCH_MAX_LANES);
     DEVICE_GUARD(e);
+    e->proof_edges.clear(); e->proof_roots.clear();
     const int Wv = std::min(count, e->cfg.slots);           // positions per wave: everything below is sized by it, not by count
     int rc = ensure_episode_buffers(e, Wv, false);
     const size_t wn = (size_t)Wv * nn;
@@ -2307,6 +2443,7 @@ extern "C" int az_search_batch(az_engine *e, int slot, int count, const uint8_t 
     sp.ext_net = slot;
     az_counters total{};
     int64_t ext_requests = 0, ext_items = 0;       // az_ext_stats reports the whole call, like the counters
+    int64_t batch_stops = 0;                       // ... and so does az_solver_stops
     std::vector<double> hu(wn);
     for (int w0 = 0; w0 < count; w0 += Wv) {
         const int m = std::min(Wv, count - w0);
@@ -2355,11 +2492,19 @@ extern "C" int az_search_batch(az_engine *e, int slot, int count, const uint8_t 
         az_counters c{};
         if ((rc = run_episode(e, sp, &c))) return rc;
         add_counters(total, c);
+        batch_stops += e->solver_stops;
         ext_requests += e->ext.requests; ext_items += e->ext.items;
         // the lanes' streams are drained: every slot's root row and record into the compact staging, one copy per output
         e->ops->gather_roots(e->stream, bl, e->lanes[0].d, (const unsigned char *)e->bt_cells.p, visits ? (int *)e->bt_visits.p : nullptr, W ? (double *)e->bt_W.p : nullptr,
                              prior ? (float *)e->bt_prior.p : nullptr, pi ? (float *)e->bt_pi.p : nullptr,
                              actions ? (int *)e->bt_action.p : nullptr);
+        if (e->solver) {
+            int first = 0;
+            for (Lane &L : e->lanes) {
+                if (L.preset_m > 0 && (rc = fetch_proofs(e, L, L.preset_m, boards + (size_t)(w0 + first) * nn, (size_t)(w0 + first)))) return rc;
+                first += L.preset_m;
+            }
+        }
         const size_t o = (size_t)w0 * nn, mn = (size_t)m * nn;
         if (visits) HIPCHECK(e, hipMemcpyAsync(visits + o, e->bt_visits.p, mn * 4, hipMemcpyDeviceToHost, e->stream));
         if (W) HIPCHECK(e, hipMemcpyAsync(W + o, e->bt_W.p, mn * 8, hipMemcpyDeviceToHost, e->stream));
@@ -2370,6 +2515,7 @@ extern "C" int az_search_batch(az_engine *e, int slot, int count, const uint8_t 
         HIPCHECK(e, hipGetLastError());
     }
     e->last = total;
+    e->solver_stops = batch_stops;
     if (e->ext.on) { e->ext.requests = ext_requests; e->ext.items = ext_items; }
     return AZ_OK;
 }
@@ -2565,6 +2711,7 @@ extern "C" int az_set_subtree_reuse(az_engine *e, int on)
     if (on && e->cap_fast) return fail(e, AZ_ERR_INVALID, "the playout cap and subtree reuse cannot be combined");
     if (on && e->forced_k > 0.0) return fail(e, AZ_ERR_INVALID, "forced playouts and subtree reuse cannot be combined");
     if (on && e->gumbel_m > 0) return fail(e, AZ_ERR_INVALID, "the Gumbel root search and subtree reuse cannot be combined");
+    if (on && e->solver) return fail(e, AZ_ERR_INVALID, "the solver and subtree reuse cannot be combined");
     if (on && e->R > REUSE_MAX_ROWS)
         return fail(e, AZ_ERR_INVALID, "subtree reuse supports at most %d simulations per move", REUSE_MAX_ROWS - 1);
     e->reuse = on ? 1 : 0;
@@ -2597,6 +2744,8 @@ extern "C" int az_set_virtual_loss(az_engine *e, int leaves)
         const char *f = getenv("AZ_VL_FORCE");
         if (e->gumbel_m > 0 && (leaves > 1 || (f && f[0] == '1')))
             return fail(e, AZ_ERR_INVALID, "the Gumbel root search and virtual-loss batching cannot be combined");
+        if (e->solver && (leaves > 1 || (f && f[0] == '1')))
+            return fail(e, AZ_ERR_INVALID, "the solver and virtual-loss batching cannot be combined");
     }
     DEVICE_GUARD(e);
     // deep search (S > DEFAULT_MAX_S) with batches: the in-flight counts live beside the tree, one byte per edge
@@ -2723,6 +2872,7 @@ extern "C" int az_set_external_evaluator(az_engine *e, const az_ext_evaluator *e
     if (e->cap_fast) return fail(e, AZ_ERR_INVALID, "the playout cap and the external evaluator cannot be combined");
     if (e->leaf_symmetry) return fail(e, AZ_ERR_INVALID, "random-symmetry leaf evaluation and the external evaluator cannot be combined");
     if (e->gumbel_m > 0) return fail(e, AZ_ERR_INVALID, "the Gumbel root search and the external evaluator cannot be combined (it returns priors, not logits)");
+    if (e->solver) return fail(e, AZ_ERR_INVALID, "the solver and the external evaluator cannot be combined");
     if (ev->capacity < e->cfg.slots * e->vl)
         return fail(e, AZ_ERR_INVALID, "az_set_external_evaluator: capacity %d is below az_ext_capacity = %d slots x %d leaves per batch",
                     ev->capacity, e->cfg.slots, e->vl);
@@ -2751,6 +2901,7 @@ extern "C" int az_search_callback(az_engine *e, const uint8_t *board, int player
     if (e->run.open) return fail(e, AZ_ERR_STATE, "az_search_callback: a self-play episode is open on this engine");
     if (e->vl > 1 || e->reuse || e->leaf_symmetry)
         return fail(e, AZ_ERR_INVALID, "az_search_callback: not combinable with virtual-loss batching, subtree reuse or random-symmetry leaf evaluation");
+    if (e->solver) return fail(e, AZ_ERR_INVALID, "az_search_callback: not combinable with the solver");
     if (noise && e->gumbel_m > 0)
         return fail(e, AZ_ERR_INVALID, "az_search_callback: a noised search under the Gumbel root search needs logits, the callback returns priors");
     DEVICE_GUARD(e);

@@ -82,6 +82,11 @@ void fc(const LaunchCtx &c, int net_id)
 void step(const LaunchCtx &c, int rootN, int do_select)
 {
     dim3 g((c.d.B + STEP_WAVES - 1) / STEP_WAVES), b(STEP_WAVES * 64);
+    if (c.d.proof) {                                           // az_set_solver (never with the synthetic evaluator): the SOLVER kernels
+        if (c.d.S > DEFAULT_MAX_S) hipLaunchKernelGGL((k_step<N, false, true, true>), g, b, 0, c.stream, c.d, rootN, do_select);
+        else hipLaunchKernelGGL((k_step<N, false, false, true>), g, b, (size_t)(c.d.S + 2) * sizeof(double), c.stream, c.d, rootN, do_select);
+        return;
+    }
     if (c.d.S > DEFAULT_MAX_S) {
         if (c.synthetic) hipLaunchKernelGGL((k_step<N, true, true>), g, b, 0, c.stream, c.d, rootN, do_select);
         else hipLaunchKernelGGL((k_step<N, false, true>), g, b, 0, c.stream, c.d, rootN, do_select);
@@ -118,13 +123,14 @@ void root_cache(const LaunchCtx &c)
 constexpr bool HAS_SEARCH = N <= 7;      // the LDS-resident tree needs (S + 1) * n*n * 16 B per game
 constexpr bool HAS_SEARCH2 = N <= 5;     // two games per workgroup: beyond 5x5 the rows of two games never fit beside the image
 
-template <int GP, bool SY, bool RES>
+// SOLVER (az_set_solver): one status byte per edge behind the edges, and the SOLVER kernel (no tile-subset variant of it)
+template <int GP, bool SY, bool RES, bool SOLVER = false>
 int search_prepare_t(int S)
 {
     if constexpr (HAS_SEARCH) {
-        const size_t dyn = (size_t)GP * (S + 1) * N * N * sizeof(Edge);
-        const void *fns[2] = {reinterpret_cast<const void *>(&k_search<N, GP, SY, false, RES>),
-                              reinterpret_cast<const void *>(&k_search<N, GP, SY, GP == 2 && !SY, RES>)};     // [1]: the tile-subset variant (search_t)
+        const size_t dyn = (size_t)GP * (S + 1) * N * N * (sizeof(Edge) + (SOLVER ? 1 : 0));
+        const void *fns[2] = {reinterpret_cast<const void *>(&k_search<N, GP, SY, false, RES, SOLVER>),
+                              reinterpret_cast<const void *>(&k_search<N, GP, SY, GP == 2 && !SY && !SOLVER, RES, SOLVER>)};     // [1]: the tile-subset variant (search_t)
         for (const void *fn : fns) {
             hipFuncAttributes at;
             if (hipFuncGetAttributes(&at, fn) != hipSuccess) return 0;
@@ -137,10 +143,19 @@ int search_prepare_t(int S)
     }
 }
 
-int search_prepare(int S, int games, int synthetic, int model)
+int search_prepare(int S, int games, int synthetic, int model, int solver)
 {
     if (S > DEFAULT_MAX_S) return 0;                   // k_search's static sqrt table holds S + 2 <= 1026 entries
     const bool res = model == 1 && !synthetic;         // the synthetic evaluator has no net: the plain kernels serve it
+    if (solver) {                                      // never with the synthetic evaluator
+        if (synthetic) return 0;
+        if (games == 2) {
+            if constexpr (HAS_SEARCH2) return res ? search_prepare_t<2, false, true, true>(S) : search_prepare_t<2, false, false, true>(S);
+            return 0;
+        }
+        if (games == 1) return res ? search_prepare_t<1, false, true, true>(S) : search_prepare_t<1, false, false, true>(S);
+        return 0;
+    }
     if (games == 2) {
         if constexpr (HAS_SEARCH2)
             return synthetic ? search_prepare_t<2, true, false>(S) : (res ? search_prepare_t<2, false, true>(S) : search_prepare_t<2, false, false>(S));
@@ -157,6 +172,12 @@ void search_t(const LaunchCtx &c)
         dim3 g((c.d.B + GP - 1) / GP), b(NetGeo<N>::NW * 64);
         const size_t dyn = (size_t)GP * c.d.R * N * N * sizeof(Edge);
         const bool ts = GP == 2 && (c.d.cache || c.d.reuse);      // many iterations with one game waiting for the net: compute its tiles only
+        if (c.d.proof) {                                          // az_set_solver: the status bytes behind the edges
+            const size_t dyns = dyn + (size_t)GP * c.d.R * N * N;
+            if (c.model == 1) hipLaunchKernelGGL((k_search<N, GP, false, false, true, true>), g, b, dyns, c.stream, c.d, c.w[0], c.w[1], c.dbg, c.rw[0], c.rw[1]);
+            else hipLaunchKernelGGL((k_search<N, GP, false, false, false, true>), g, b, dyns, c.stream, c.d, c.w[0], c.w[1], c.dbg, NoWeights{}, NoWeights{});
+            return;
+        }
         if (c.synthetic)
             hipLaunchKernelGGL((k_search<N, GP, true, false, false>), g, b, dyn, c.stream, c.d, c.w[0], c.w[1], c.dbg, NoWeights{}, NoWeights{});
         else if (c.model == 1) {

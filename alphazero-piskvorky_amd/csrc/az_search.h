@@ -61,11 +61,14 @@ struct GameLds {
 // the tree step of one game on LDS rows: k_step's two stages (az_tree.h) with the node array, the path and the evaluator
 // outputs in LDS.  One wavefront.  Subtree reuse: k_search loads the retained rows and writes the whole tree back; an evaluation-cache hit (LEAF_*_HIT, set by k_search before the
 // net phase) is consumed exactly like the evaluation it stands for.
-template <int N, class PG, bool SYNTH>
+// SOLVER (az_set_solver): k_step's SOLVER rule (az_tree.h) on LDS rows: prf = the game's status bytes, one per edge, ROWE per row;
+// root_st = the root's status, stops = the simulations that ended on a proven edge, both in registers of the game's wave.
+template <int N, class PG, bool SYNTH, bool SOLVER = false>
 __device__ __forceinline__ void step_lds(const DevState &d, int b, int lane, Edge *rows, unsigned *path, GameLds &gs,
                                          const float *lg, const float *hid, const double *sq_lds, int rootN, int do_select,
                                          int pl, int slast, int netid, int game, int ply, const Plane &bX, const Plane &bO,
-                                         unsigned long long (&cnt)[4], const float *w2, float b2, int carried, double &gum_h KS_PARAM)
+                                         unsigned long long (&cnt)[4], const float *w2, float b2, int carried, double &gum_h KS_PARAM,
+                                         unsigned char *prf = nullptr, int *root_st = nullptr, unsigned long long *stops = nullptr)
 {
 #ifdef AZ_STAMPS
     unsigned long long st_t = __builtin_amdgcn_s_memtime();
@@ -169,6 +172,10 @@ __device__ __forceinline__ void step_lds(const DevState &d, int b, int lane, Edg
                 Edge e;
                 e.W = 0.0; e.P = P; e.N = 0; e.child = 0;
                 rows[row * PG::ROWE + lane] = e;
+                if constexpr (SOLVER) prf[row * PG::ROWE + lane] = PROOF_UNKNOWN;      // a new row starts all UNKNOWN
+            }
+            if constexpr (SOLVER) {
+                if (kind == LEAF_ROOT) *root_st = PROOF_UNKNOWN;
             }
             if (lane == 0) gs.rows_used = row + 1;
             if (kind == LEAF_EXPAND) {
@@ -179,13 +186,24 @@ __device__ __forceinline__ void step_lds(const DevState &d, int b, int lane, Edg
         }
         if (kind != LEAF_ROOT) {
             // mcts.py:132-134,141,76-82: value w.r.t. the side to move at the leaf, backed up with alternating sign
-            const double value = kind == LEAF_EXPAND ? (double)v : (kind == LEAF_TERM_LOSS ? -1.0 : 0.0);
+            double value = kind == LEAF_EXPAND ? (double)v : (kind == LEAF_TERM_LOSS ? -1.0 : 0.0);
+            if constexpr (SOLVER) value = kind == LEAF_TERM_WIN ? 1.0 : value;
             for (int dd = lane; dd < depth0; dd += 64) {
                 const unsigned pe = path[dd];
                 Edge *e = rows + (pe >> 16) * PG::ROWE + (pe & 0xFFFFu);
                 const double val = ((depth0 - 1 - dd) & 1) ? value : -value;
                 e->N = (unsigned short)(e->N + 1);
                 e->W = e->W + val;
+            }
+            if constexpr (SOLVER) {
+                // marking: a real terminal whose edge is still UNKNOWN proves that edge (proof_mark, az_tree.h)
+                if (kind == LEAF_TERM_LOSS || kind == LEAF_TERM_DRAW) {
+                    Plane occ0;
+#pragma unroll
+                    for (int q = 0; q < 4; q++) occ0.w[q] = bX.w[q] | bO.w[q];
+                    const int rs = proof_mark<N, PG::ROWE>(prf, path, depth0, occ0, kind == LEAF_TERM_LOSS ? PROOF_WIN : PROOF_DRAW, lane);
+                    if (rs != PROOF_UNKNOWN) *root_st = rs;
+                }
             }
             cnt[0] += kind == LEAF_EXPAND ? 1ull : 0ull;
             cnt[1] += 1ull;
@@ -210,7 +228,14 @@ __device__ __forceinline__ void step_lds(const DevState &d, int b, int lane, Edg
         for (int q = 0; q < 4; q++) occ.w[q] = me.w[q] | opp.w[q];
         const double sq = sq_lds[npar];                       // np.sqrt(self.N + 1e-8), mcts.py:73
         double best = 0.0;
-        int bi = -1, bN = 0, bC = 0;
+        int bi = -1, bN = 0, bC = 0, bS = PROOF_UNKNOWN;
+        bool masked = false;
+        if constexpr (SOLVER) {
+            // the lane's status and the vote "some legal edge is not LOSS" (every legal edge LOSS, the root only: the plain scores decide)
+            const bool own = lane < G::nn && !pl_get(occ, lane);
+            bS = own ? (int)prf[row * PG::ROWE + lane] : PROOF_UNKNOWN;
+            masked = __ballot(own && bS != PROOF_LOSS) != 0ull;
+        }
         if (gumbel && row == 0) {
             // az_set_gumbel: sequential halving at the root (k_step's branch, az_tree.h): the children whose visit count is the
             // schedule's entry for this simulation compete with (g + logit) + sigma q
@@ -232,6 +257,10 @@ __device__ __forceinline__ void step_lds(const DevState &d, int b, int lane, Edg
             double Q = e.N ? e.W / (double)e.N : 0.0;         // mcts.py:80 Q = W/N (0.0 while unvisited)
             best = Q + ((d.c_puct * (double)e.P) * sq) / (double)(1 + (int)e.N);
             if (forced && row == 0 && forced_child((double)(int)e.N, d.forced_k, e.P, rootN)) best = INFINITY;
+            if constexpr (SOLVER) {
+                if (bS == PROOF_WIN) best = INFINITY;
+                else if (bS == PROOF_LOSS && masked) best = -INFINITY;
+            }
             bi = lane; bN = e.N; bC = e.child;
         }
         ST_STAMP(16);                // one level: row read, PUCT scores
@@ -248,6 +277,15 @@ __device__ __forceinline__ void step_lds(const DevState &d, int b, int lane, Edg
         last = a;
         if (wins_through_wave(opp, a, N, d.k, lane)) { out_kind = LEAF_TERM_LOSS; break; }  // the side to move has lost
         if (pl_count(me) + pl_count(opp) == G::nn) { out_kind = LEAF_TERM_DRAW; break; }
+        if constexpr (SOLVER) {
+            // a proven edge ends the simulation like a terminal: the value of the side to move below it, no evaluation, no row
+            const int ast = __builtin_amdgcn_readlane(bS, a);
+            if (ast != PROOF_UNKNOWN) {
+                out_kind = ast == PROOF_WIN ? LEAF_TERM_LOSS : (ast == PROOF_LOSS ? LEAF_TERM_WIN : LEAF_TERM_DRAW);
+                *stops += 1ull;
+                break;
+            }
+        }
         if (child == 0) { out_kind = LEAF_EXPAND; break; }    // mcts.py:127 node.is_leaf()
         npar = an;
         row = child;
@@ -351,7 +389,9 @@ __device__ __forceinline__ void fc_mfma(const FcPre<NG> &pre, const float *featl
 // RES: the ResidualBlock net (stem + 3 blocks on two 64-channel images, 2 + 1 head channels; k_trunk_res): r0 / r1 hold its conv
 // weights, w0 / w1 only the FC layers'.  The reference's trained ResidualBlock checkpoints are 5x5 nets.
 struct NoWeights { };
-template <int N, int GP, bool SYNTH, bool TS = false, bool RES = false>
+// SOLVER (az_set_solver): instantiations of their own.  The status bytes follow the edges in the dynamic LDS, GP x R x ROWE
+// bytes (1/16 of the edges); the root row's statuses and the root's status go to d.proof / d.root_proof for k_move at the end.
+template <int N, int GP, bool SYNTH, bool TS = false, bool RES = false, bool SOLVER = false>
 __global__ __launch_bounds__(NetGeo<N>::NW * 64) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_search(DevState d, NetWeights w0, NetWeights w1, unsigned long long *dbg,
                                                                                                   std::conditional_t<RES, ResWeights, NoWeights> r0,
                                                                                                   std::conditional_t<RES, ResWeights, NoWeights> r1)
@@ -390,6 +430,9 @@ __global__ __launch_bounds__(NetGeo<N>::NW * 64) __attribute__((amdgpu_waves_per
     __shared__ int wg_net;
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];     // GP x R x ROWE edges
     Edge *rows_all = reinterpret_cast<Edge *>(dyn_lds);
+    unsigned char *prf_all = dyn_lds + (size_t)GP * d.R * PG::ROWE * sizeof(Edge);       // SOLVER only: GP x R x ROWE status bytes
+    int root_st = PROOF_UNKNOWN;
+    unsigned long long stops = 0ull;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -643,10 +686,17 @@ __global__ __launch_bounds__(NetGeo<N>::NW * 64) __attribute__((amdgpu_waves_per
             }
         }
         // ---- tree step: wave g works on game g ----
-        if (mine && (!(AZ_SEARCH_SKIP & 2) || idx == S))
-            step_lds<N, PG, SYNTH>(d, gb, lane, rows_all + (size_t)wave * d.R * PG::ROWE, path_l[wave], games[wave],
-                                   logits_l + wave * PG::RW, vhid_l + wave * 64, sq_lds, idx, idx < S ? 1 : 0, pl, slast, netid,
-                                   game, ply, bX, bO, cnt, w2_lds + wave * 64, b2, carried, gum_h KS_ARG);
+        if (mine && (!(AZ_SEARCH_SKIP & 2) || idx == S)) {
+            if constexpr (SOLVER)
+                step_lds<N, PG, SYNTH, true>(d, gb, lane, rows_all + (size_t)wave * d.R * PG::ROWE, path_l[wave], games[wave],
+                                             logits_l + wave * PG::RW, vhid_l + wave * 64, sq_lds, idx, idx < S ? 1 : 0, pl, slast, netid,
+                                             game, ply, bX, bO, cnt, w2_lds + wave * 64, b2, carried, gum_h KS_ARG,
+                                             prf_all + (size_t)wave * d.R * PG::ROWE, &root_st, &stops);
+            else
+                step_lds<N, PG, SYNTH>(d, gb, lane, rows_all + (size_t)wave * d.R * PG::ROWE, path_l[wave], games[wave],
+                                       logits_l + wave * PG::RW, vhid_l + wave * 64, sq_lds, idx, idx < S ? 1 : 0, pl, slast, netid,
+                                       game, ply, bX, bO, cnt, w2_lds + wave * 64, b2, carried, gum_h KS_ARG);
+        }
         KS_STAMP(8);                 // the tree step of this wave's game (waves 0 .. GP - 1)
         __syncthreads();
         KS_STAMP(9);                 // ... and the wait for the other game's
@@ -665,6 +715,12 @@ __global__ __launch_bounds__(NetGeo<N>::NW * 64) __attribute__((amdgpu_waves_per
             c[0] += cnt[0]; c[1] += cnt[1]; c[2] += cnt[2]; c[3] += cnt[3];
             c[4] += kind0 == LEAF_REUSE ? 1ull : 0ull;
             c[6] += cache_lookups; c[7] += cache_hits;
+        }
+        if constexpr (SOLVER) {
+            // the root row's statuses (RW = 64 bytes per row in HBM) and the root's own, for k_move and az_last_proof
+            const unsigned char *prf = prf_all + (size_t)wave * d.R * PG::ROWE;
+            d.proof[(size_t)gb * d.R * TG::RW + lane] = lane < PG::ROWE ? prf[lane] : (unsigned char)PROOF_UNKNOWN;
+            if (lane == 0) { d.root_proof[gb] = (signed char)root_st; d.proof_stops[gb] += stops; }
         }
     }
 #ifdef AZ_STAMPS

@@ -12,6 +12,7 @@
 enum { LEAF_NONE = 0, LEAF_EXPAND = 1, LEAF_TERM_LOSS = 2, LEAF_TERM_DRAW = 3, LEAF_ROOT = 4,
        LEAF_REUSE = 5,        // root retained from the previous ply's search (subtree reuse): no evaluation, noise mix only
        LEAF_EXPAND_HIT = 6, LEAF_ROOT_HIT = 7,   // evaluation cache hit: logits / hidden row already in place, the net kernels skip the slot
+       LEAF_TERM_WIN = 8,     // az_set_solver: the descent stopped on an edge proven LOSS for its mover, the side to move below it has won (+1)
        LEAF_DUP_BASE = 16 };  // virtual-loss batching: LEAF_DUP_BASE + i = same leaf as item i of this batch (no second evaluation)
 __host__ __device__ constexpr bool leaf_needs_net(int kind) { return kind == LEAF_ROOT || kind == LEAF_EXPAND; }
 constexpr int VL_MAX = 32;             // leaves per batch in virtual-loss mode (5 spare bits of the edge's visit field)
@@ -25,6 +26,9 @@ constexpr int DEFAULT_MAX_S = 1024;
 constexpr int CNT_STRIDE = 8;  // per-slot counters: expansions, simulations, terminal hits, depth sum, reused roots, duplicate leaves,
                                // cache lookups, cache hits
 enum { SLOT_IDLE = 0, SLOT_ACTIVE = 1, SLOT_FINISHED = 2 };
+// az_set_solver: the status of an edge, seen from the side that makes the move (AZ_PROOF_* of include/az_engine.h)
+enum { PROOF_UNKNOWN = 0, PROOF_WIN = 1, PROOF_LOSS = 2, PROOF_DRAW = 3 };
+__host__ __device__ constexpr int proof_negate(int s) { return s == PROOF_WIN ? PROOF_LOSS : (s == PROOF_LOSS ? PROOF_WIN : s); }
 
 struct __attribute__((aligned(16))) Edge {
     double W;              // mcts.py:38 total value (float64 like the reference)
@@ -123,6 +127,12 @@ struct DevState {
     const unsigned short *gumbel_seq;  // [gumbel_m][S] sequential-halving schedules: row k - 1 serves a root with k candidates
     float *root_logits;    // [B][RW] the root's logits by board cell, written when the root evaluation is consumed, read by k_move
     float *root_v;         // [B] ... and the root's value
+    // --- opt-in MCTS-Solver (az_set_solver): proof = nullptr on every other path, nothing below is read or written then ---
+    unsigned char *proof;  // [B][R][RW] status of every edge, beside the tree like the DEEP in-flight counts; a new row starts all UNKNOWN
+    unsigned char *proof_buf;  // the slot's array, as az_set_solver allocated it: proof = proof_buf while the option is on (host side only)
+    signed char *root_proof;   // [B] status of the root of the running ply, seen from its side to move
+    signed char *rec_proof;    // [G*nn] ... and of every record's root, written by k_move
+    unsigned long long *proof_stops;   // [B] simulations that ended on a proven edge (a terminal hit in cnt as well)
 };
 __device__ __forceinline__ int game_key(const DevState &d, int game) { return (int)(d.game_key0 + d.key_stride * (unsigned)game); }
 // az_set_playout_cap's rule, a function of the game's global name and the absolute ply only (the host's az_playout_cap_full)
@@ -414,8 +424,72 @@ __global__ void k_begin(DevState d)
 // the global table (L2-resident) right after the chosen edge is known, so it is in flight with that level's win test
 // and the next level's edge loads (same values: results are bit-identical).
 // ------------------------------------------------------------------------------------------------
+// SOLVER (az_set_solver): instantiations of their own, so that the default ones keep their code.  One status byte per edge
+// beside the tree (d.proof).  Selection masks the scores with the row's statuses (a WIN edge +inf, a LOSS edge -inf while
+// the row has a legal edge that is not LOSS: one more wave vote per level); a descent that lands on a proven edge ends there
+// like a terminal; and the launch that backs a real terminal up whose edge was still UNKNOWN marks that edge and walks the
+// path upwards, replaying the occupancy of each level from the root planes and the path (proof_mark).  A simulation that
+// ends in an expansion only pays for the status loads.
 constexpr int STEP_WAVES = 4;      // games (wavefronts) per k_step workgroup
-template <int N, bool SYNTH, bool DEEP = false>
+
+// the status of a node, seen from its side to move, from this lane's CPL statuses of its row: WIN if any legal edge is WIN,
+// else DRAW / LOSS once every legal edge is proven
+template <int N>
+__device__ __forceinline__ int proof_node(const int (&st)[TreeGeo<N>::CPL], const Plane &occ, int lane)
+{
+    typedef TreeGeo<N> G;
+    bool anyw = false, anyd = false, anyu = false;
+#pragma unroll
+    for (int i = 0; i < G::CPL; i++) {
+        const int j = lane + 64 * i;
+        if (j < G::nn && !pl_get(occ, j)) {
+            anyw = anyw || st[i] == PROOF_WIN;
+            anyd = anyd || st[i] == PROOF_DRAW;
+            anyu = anyu || st[i] == PROOF_UNKNOWN;
+        }
+    }
+    if (__ballot(anyw)) return PROOF_WIN;
+    if (__ballot(anyu)) return PROOF_UNKNOWN;
+    return __ballot(anyd) ? PROOF_DRAW : PROOF_LOSS;
+}
+
+// The marking walk (wave-uniform).  The simulation whose path[0 .. depth) is given ended on a real terminal: `status` (WIN:
+// the move made the line, DRAW: it filled the board) goes to its last edge when that edge is still UNKNOWN, and upwards as
+// long as the owning node's status is known.  occ0 = the root's occupancy.  prf = this slot's statuses, RS bytes per row (the
+// HBM array pads a row to RW, k_search's LDS copy does not).  Returns the root's status when the walk reaches it, else UNKNOWN.
+template <int N, int RS = TreeGeo<N>::RW>
+__device__ __forceinline__ int proof_mark(unsigned char *prf, const unsigned *path, int depth, Plane occ0, int status, int lane)
+{
+    typedef TreeGeo<N> G;
+    if (depth < 1 || depth > G::nn) return PROOF_UNKNOWN;
+    const unsigned last = path[depth - 1];
+    if (prf[(size_t)(last >> 16) * RS + (last & 0xFFFFu)] != PROOF_UNKNOWN) return PROOF_UNKNOWN;
+    Plane occ = occ0;                                         // the occupancy of level depth - 1: the root's and the moves above it
+    for (int dd = 0; dd < depth - 1; dd++) pl_set(occ, (int)(path[dd] & 0xFFFFu));
+    for (int lvl = depth - 1; lvl >= 0; lvl--) {
+        const unsigned pe = path[lvl];
+        const int cell = (int)(pe & 0xFFFFu);
+        unsigned char *row = prf + (size_t)(pe >> 16) * RS;
+        int st[G::CPL];
+#pragma unroll
+        for (int i = 0; i < G::CPL; i++) {
+            const int j = lane + 64 * i;
+            st[i] = j == cell ? status : (j < G::nn ? (int)row[j] : PROOF_UNKNOWN);
+        }
+        if (lane == 0) row[cell] = (unsigned char)status;
+        const int ns = proof_node<N>(st, occ, lane);
+        if (ns == PROOF_UNKNOWN) return PROOF_UNKNOWN;
+        if (lvl == 0) return ns;
+        status = proof_negate(ns);
+        const int up = (int)(path[lvl - 1] & 0xFFFFu);        // the level above had this cell still empty
+        const u64 bit = 1ull << (up & 63);
+#pragma unroll
+        for (int q = 0; q < 4; q++) occ.w[q] &= (up >> 6) == q ? ~bit : ~0ull;
+    }
+    return PROOF_UNKNOWN;
+}
+
+template <int N, bool SYNTH, bool DEEP = false, bool SOLVER = false>
 __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN, int do_select)
 {
     typedef TreeGeo<N> G;
@@ -591,6 +665,13 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
                 e.W = 0.0; e.P = P[i]; e.N = 0; e.child = 0;
                 rows[(size_t)row * G::RW + j] = e;
             }
+            if constexpr (SOLVER) {
+                // a new row starts with every edge UNKNOWN, and a new root with its own status UNKNOWN
+                unsigned char *prow = d.proof + ((size_t)b * d.R + row) * G::RW;
+#pragma unroll
+                for (int i = 0; i < G::CPL; i++) prow[lane + 64 * i] = PROOF_UNKNOWN;
+                if (kind == LEAF_ROOT && lane == 0) d.root_proof[b] = PROOF_UNKNOWN;
+            }
             if (lane == 0) d.rows_used[b] = row + 1;
             if (kind == LEAF_EXPAND) {
                 const unsigned pe = depth0 - 1 < 64 ? (unsigned)__shfl((int)path_l, depth0 - 1, 64) : path[depth0 - 1];
@@ -599,13 +680,25 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
         }
         if (kind != LEAF_ROOT) {
             // mcts.py:132-134,141,76-82: value w.r.t. the side to move at the leaf, backed up with alternating sign
-            const double value = kind == LEAF_EXPAND ? (double)v : (kind == LEAF_TERM_LOSS ? -1.0 : 0.0);
+            double value = kind == LEAF_EXPAND ? (double)v : (kind == LEAF_TERM_LOSS ? -1.0 : 0.0);
+            if constexpr (SOLVER) value = kind == LEAF_TERM_WIN ? 1.0 : value;
             for (int dd = lane; dd < depth0; dd += 64) {
                 const unsigned pe = dd < 64 ? path_l : path[dd];
                 Edge *e = rows + (size_t)(pe >> 16) * G::RW + (pe & 0xFFFFu);
                 const double val = ((depth0 - 1 - dd) & 1) ? value : -value;
                 e->N = (unsigned short)(e->N + 1);
                 e->W = e->W + val;
+            }
+            if constexpr (SOLVER) {
+                // marking: a real terminal whose edge is still UNKNOWN (a stop on a proven edge never is) proves that edge
+                if (kind == LEAF_TERM_LOSS || kind == LEAF_TERM_DRAW) {
+                    Plane occ0;
+#pragma unroll
+                    for (int q = 0; q < 4; q++) occ0.w[q] = bX.w[q] | bO.w[q];
+                    const int rs = proof_mark<N>(d.proof + (size_t)b * d.R * G::RW, path, depth0, occ0,
+                                                 kind == LEAF_TERM_LOSS ? PROOF_WIN : PROOF_DRAW, lane);
+                    if (rs != PROOF_UNKNOWN && lane == 0) d.root_proof[b] = (signed char)rs;
+                }
             }
             if (lane == 0) {
                 unsigned long long *c = d.cnt + (size_t)b * CNT_STRIDE;
@@ -635,7 +728,7 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
         for (int q = 0; q < 4; q++) occ.w[q] = me.w[q] | opp.w[q];
         const double sq = DEEP ? sq_next : sq_lds[npar];      // np.sqrt(self.N + 1e-8), mcts.py:73
         double best = 0.0;
-        int bi = -1, bN = 0, bC = 0;
+        int bi = -1, bN = 0, bC = 0, bS = 0;
         if (gumbel && row == 0) {
             // az_set_gumbel: sequential halving at the root.  Among the legal children whose visit count is the schedule's entry
             // for this simulation, the first maximum of (g + logit) + sigma q; they all have equal N, so the choice is exact.
@@ -666,6 +759,19 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
                 }
             }
         } else {
+        int pst[G::CPL];                                      // SOLVER: the row's statuses; the vote: some legal edge is not LOSS
+        bool masked = false;
+        if constexpr (SOLVER) {
+            const unsigned char *prow = d.proof + ((size_t)b * d.R + row) * G::RW;
+            bool alive = false;
+#pragma unroll
+            for (int i = 0; i < G::CPL; i++) {
+                const int j = lane + 64 * i;
+                pst[i] = prow[j];
+                alive = alive || (j < G::nn && !pl_get(occ, j) && pst[i] != PROOF_LOSS);
+            }
+            masked = __ballot(alive) != 0ull;                 // every legal edge LOSS (the root only): the plain scores decide
+        }
 #pragma unroll
         for (int i = 0; i < G::CPL; i++) {
             int j = lane + 64 * i;
@@ -674,7 +780,13 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
                 double Q = e.N ? e.W / (double)e.N : 0.0;     // mcts.py:80 Q = W/N (0.0 while unvisited)
                 double sc = Q + ((d.c_puct * (double)e.P) * sq) / (double)(1 + (int)e.N);
                 if (forced && row == 0 && forced_child((double)(int)e.N, d.forced_k, e.P, rootN)) sc = INFINITY;
-                if (bi < 0 || sc > best) { best = sc; bi = j; bN = e.N; bC = e.child; }
+                int key = 0;
+                if constexpr (SOLVER) {
+                    if (pst[i] == PROOF_WIN) sc = INFINITY;
+                    else if (pst[i] == PROOF_LOSS && masked) sc = -INFINITY;
+                    key = pst[i];
+                }
+                if (bi < 0 || sc > best) { best = sc; bi = j; bN = e.N; bC = e.child; bS = key; }
             }
         }
         }
@@ -684,6 +796,7 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
         // the lane that owns cell a (a & 63) holds its edge: the global best is also that lane's best
         const int child = __builtin_amdgcn_readlane(bC, a & 63);
         const int an = __builtin_amdgcn_readlane(bN, a & 63);
+        const int ast = SOLVER ? __builtin_amdgcn_readlane(bS, a & 63) : PROOF_UNKNOWN;
         if (DEEP) sq_next = d.sqrt_table[an];                 // the next level's parent visits: issued before the win test
         if (lane == 0) path[depth] = ((unsigned)row << 16) | (unsigned)a;
         depth++;
@@ -692,6 +805,14 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
         last = a;
         if (wins_through_wave(opp, a, N, d.k, lane)) { out_kind = LEAF_TERM_LOSS; break; }  // the side to move has lost
         if (pl_count(me) + pl_count(opp) == G::nn) { out_kind = LEAF_TERM_DRAW; break; }
+        if constexpr (SOLVER) {
+            // a proven edge ends the simulation like a terminal: no evaluation, no row; the value of the side to move below it
+            if (ast != PROOF_UNKNOWN) {
+                out_kind = ast == PROOF_WIN ? LEAF_TERM_LOSS : (ast == PROOF_LOSS ? LEAF_TERM_WIN : LEAF_TERM_DRAW);
+                if (lane == 0) d.proof_stops[b] += 1ull;
+                break;
+            }
+        }
         if (child == 0) { out_kind = LEAF_EXPAND; break; }    // mcts.py:127 node.is_leaf()
         npar = an;
         row = child;
@@ -1074,6 +1195,26 @@ __host__ __device__ inline double pw_sum(const double *a, int A)
     return A <= 128 ? 0.0 + pw_block(a, A) : 0.0 + (pw_block(a, n2) + pw_block(a + n2, A - n2));
 }
 
+// az_set_solver: N' of a root row, shared by k_move and the host's az_solver_counts.  any_win: some legal edge is WIN;
+// survivor: some legal edge that is not LOSS has a visit.  A child keeps its count unless the rule empties it.
+__host__ __device__ __forceinline__ bool solver_keeps(int st, bool any_win, bool survivor)
+{
+    return any_win ? st == PROOF_WIN : !(survivor && st == PROOF_LOSS);
+}
+template <int CPL>
+__device__ __forceinline__ void solver_counts_wave(const int (&Nj)[CPL], const int (&st)[CPL], const bool (&legal)[CPL], int (&Np)[CPL])
+{
+    bool w = false, sv = false;
+#pragma unroll
+    for (int i = 0; i < CPL; i++) {
+        w = w || (legal[i] && st[i] == PROOF_WIN);
+        sv = sv || (legal[i] && st[i] != PROOF_LOSS && Nj[i] > 0);
+    }
+    const bool any_win = __ballot(w) != 0ull, survivor = __ballot(sv) != 0ull;
+#pragma unroll
+    for (int i = 0; i < CPL; i++) Np[i] = solver_keeps(st[i], any_win, survivor) ? Nj[i] : 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // k_move: visit counts -> pi -> sampled action (mcts.py:144-177), record (self_play.py:63),
 //         apply (games.py:64-82), terminal check (games.py:133-166).
@@ -1142,6 +1283,17 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
                 Np[i] = forced_pruned(d.forced_k, d.c_puct, ec.W / (double)Nj[i], ec.P, Nj[i], tot, sq, target);
             }
         }
+    }
+    // ---- MCTS-Solver (az_set_solver, every root): pi and the move are made from Np = the counts of the WIN edges when there is
+    // one, else the counts without the LOSS edges when a visited edge survives that, else the raw counts (solver_counts) ----
+    int rproof = PROOF_UNKNOWN;
+    if (d.proof) {
+        const unsigned char *prow = d.proof + (size_t)b * d.R * G::RW;
+        int st[G::CPL];
+#pragma unroll
+        for (int i = 0; i < G::CPL; i++) st[i] = legal[i] ? (int)prow[lane + 64 * i] : PROOF_UNKNOWN;
+        solver_counts_wave<G::CPL>(Nj, st, legal, Np);
+        rproof = d.root_proof[b];
     }
     // ---- Gumbel root search (az_set_gumbel, noised roots only): the move is the best g + logit + sigma(q) among the most visited
     // children, and pi the softmax of logit + sigma(completed q); the softmax itself is the temperature path's below ----
@@ -1275,7 +1427,9 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
         }
     }
     // ---- search value of the ply: v = W[a*] / N[a*] of the raw counts (a* found above) ----
-    const double v = root[astar].W / (double)(int)(best >> 16);
+    // (az_set_solver: exactly +1, -1 or 0 when the root is proven)
+    const double v = rproof == PROOF_UNKNOWN ? root[astar].W / (double)(int)(best >> 16)
+                                             : (rproof == PROOF_WIN ? 1.0 : (rproof == PROOF_LOSS ? -1.0 : 0.0));
     // resignation (az_set_resign): the ply crosses below -threshold; an exempt game only notes it and plays on
     const bool crossed = d.resign_thr > 0.0 && ply >= d.resign_min_ply && v < -d.resign_thr;
     const bool exempt = !d.arena && az_fmix32((unsigned)game_key(d, g)) % 1000u < (unsigned)d.resign_permille;
@@ -1301,6 +1455,7 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
         d.s_last[b] = a;
         d.s_ply[b] = ply + 1;
         d.rec_value[ri] = (float)v;
+        if (d.proof) d.rec_proof[ri] = (signed char)rproof;
         if (crossed && d.g_cross[g] < 0) d.g_cross[g] = ply;
         int res = win ? pl : (full ? 3 : 0);
         if (resign) res = 3 - pl;           // the mover resigns: on a crossing ply this is the result, max_plies or not

@@ -9,7 +9,7 @@ from . import constants as _c
 from . import parallel
 from ._capi import AZ_MAX_SIMULATIONS, Engine
 from .controller import device_index, make_batch_policy_value_fn, merge_batch_evaluators, model_kind
-from .mcts import numpy_log_table
+from .mcts import check_solver, numpy_log_table
 from .self_play import check_resign
 
 
@@ -19,7 +19,7 @@ def temperature_schedule(move: int) -> float:
 
 class ModelEvaluator:
     def __init__(self, game_class=None, print_games=False, device=None, seed=None, virtual_loss=1, eval_cache=0,
-                 start_positions=None, resign: dict = None, evaluators=None):
+                 start_positions=None, resign: dict = None, evaluators=None, solver: bool = False):
         self.game_class = game_class
         # opt-in: the arena's evaluations leave the engine (az_set_external_evaluator).  A (candidate, baseline) pair of
         # controller.BatchPolicyValueFn, one BatchPolicyValueFn that serves both nets by its `net` argument, or True = the
@@ -36,6 +36,8 @@ class ModelEvaluator:
         # opt-in: dict(threshold, min_ply=0); an arena game ends as a loss of the mover once the search value of a ply falls
         # below -threshold.  No arena game is exempt: a `playout` share is accepted and has no effect here.
         self.resign = check_resign(resign)
+        # opt-in MCTS-Solver in both sides' searches (az_set_solver).  Not with virtual_loss > 1 or outside evaluators.
+        self.solver = check_solver(solver, virtual_loss=virtual_loss, evaluator=self.evaluators)
         self._engine = None
 
     def evaluate(self, candidate_controller, baseline_controller, num_games=20, debug=False):
@@ -80,6 +82,9 @@ class ModelEvaluator:
             eng.set_resign(**self.resign)
         elif eng.resign()["threshold"]:
             eng.set_resign(0.0)
+        self.solver = check_solver(self.solver, virtual_loss=self.virtual_loss, evaluator=self.evaluators)
+        if self.solver != eng.solver():
+            eng.set_solver(self.solver)
         r = eng.arena(mine, seed0=seed0 + lo, temperature_table=T) if mine > 0 else {"wins": 0, "losses": 0, "draws": 0, "total": 0, "win_rate": 0.0}
         if world > 1:
             w, l, d = parallel.all_reduce_tally(r["wins"], r["losses"], r["draws"], dev, engine=eng)

@@ -30,6 +30,24 @@ def check_forced_playouts(fp):
     return out
 
 
+def check_solver(solver, subtree_reuse=False, virtual_loss=1, forced_playouts=None, gumbel=None, evaluator=None):
+    """bool(solver), the MCTS-Solver option of a seam (az_set_solver).  Raises ValueError for the combinations the engine refuses:
+    subtree reuse, virtual-loss batching, forced playouts, the Gumbel root search and evaluators outside the engine."""
+    if not solver:
+        return False
+    if subtree_reuse:
+        raise ValueError("the solver does not combine with subtree_reuse")
+    if virtual_loss != 1:
+        raise ValueError("the solver does not combine with virtual-loss batching")
+    if forced_playouts is not None:
+        raise ValueError("the solver does not combine with forced playouts")
+    if gumbel is not None:
+        raise ValueError("the solver does not combine with the Gumbel root search")
+    if evaluator is not None:
+        raise ValueError("the solver needs the engine's own net: it does not combine with an outside evaluator")
+    return True
+
+
 def check_gumbel(gumbel, subtree_reuse=False, virtual_loss=1, forced_playouts=None, evaluator=None):
     """None, or the dict a seam takes for the Gumbel root search (az_set_gumbel): m in 1..64 (default 16), c_visit >= 0 (50) and
     c_scale > 0 (1).  Raises ValueError for the combinations the engine refuses: subtree reuse, virtual-loss batching, forced
@@ -58,7 +76,7 @@ def check_gumbel(gumbel, subtree_reuse=False, virtual_loss=1, forced_playouts=No
 
 class MCTS:
     def __init__(self, policy_value_fn, num_simulations, c_puct, dirichlet_alpha=0.3, dirichlet_weight=0.25, virtual_loss=1,
-                 forced_playouts=None, gumbel=None):
+                 forced_playouts=None, gumbel=None, solver=False):
         if not callable(policy_value_fn):
             raise TypeError("policy_value_fn must be callable: state -> (policy [n, n], value)")
         # make_policy_value_fn(controller): the leaves are evaluated inside the HIP engine.  Any other callable keeps the
@@ -81,6 +99,11 @@ class MCTS:
         # they draw np.random.gumbel(size=legal) where the others draw the Dirichlet sample.  Controller-backed evaluators only.
         self.gumbel = check_gumbel(gumbel, virtual_loss=virtual_loss, forced_playouts=self.forced_playouts,
                                    evaluator=policy_value_fn if (self._external or self._batched) else None)
+        # opt-in: MCTS-Solver in every search (az_set_solver): proven wins, losses and draws; last_proof then holds the last
+        # run()'s (edge statuses [n, n], root status), after run_many() one pair per state.  Controller-backed evaluators only.
+        self.solver = check_solver(solver, virtual_loss=virtual_loss, forced_playouts=self.forced_playouts, gumbel=self.gumbel,
+                                   evaluator=policy_value_fn if (self._external or self._batched) else None)
+        self.last_proof = None
         self._engine = None
         self._version = None
         self._batch_engine = None             # run_many's own engine; run() and its one-slot engine are untouched by it
@@ -92,6 +115,8 @@ class MCTS:
             eng.set_forced_playouts(self.forced_playouts["k"], self.forced_playouts["prune"])
         if self.gumbel is not None:
             eng.set_gumbel(min(self.gumbel["m"], eng.nn), self.gumbel["c_visit"], self.gumbel["c_scale"])     # a board has n * n cells
+        if self.solver:
+            eng.set_solver(True)
         return eng
 
     def _root_noise(self, legal):
@@ -155,6 +180,9 @@ class MCTS:
         else:
             eng = self._eng(n, root_state.win_length)
             r = eng.search(root_state.cells, root_state.player_code(), root_state.last_index(), float(temperature), noise, u)
+            if self.solver:
+                edges, root = eng.last_proof()
+                self.last_proof = (edges.reshape(n, n), root)
         a = int(r["action"])
         self.last_visits = r["N"].reshape(n, n)
         return r["pi"].reshape(n, n), (a // n, a % n)
@@ -253,5 +281,11 @@ class MCTS:
                 a = int(r["action"][j])
                 out[i] = (r["pi"][j].reshape(n, n), (a // n, a % n))
                 visits[i] = r["N"][j].reshape(n, n)
+            if self.solver:
+                edges, roots = eng.last_proof()
+                proof = [None] * count
+                for j, i in enumerate(live):
+                    proof[i] = (edges[j].reshape(n, n), int(roots[j]))
+                self.last_proof = proof
         self.last_visits = visits
         return out

@@ -9,7 +9,7 @@ from . import constants as _c
 from . import parallel
 from ._capi import AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine, playout_cap_permille, resign_permille
 from .controller import BatchPolicyValueFn, device_index, model_kind
-from .mcts import check_forced_playouts, check_gumbel, numpy_log_table
+from .mcts import check_forced_playouts, check_gumbel, check_solver, numpy_log_table
 
 
 def default_temperature_schedule(move: int) -> float:
@@ -114,7 +114,7 @@ class SelfPlayManager:
                  engines_per_gpu: int = None, subtree_reuse: bool = False, gather_to: int = None,
                  eval_cache: int = 0, virtual_loss: int = 1, trunk: str = "f32", leaf_symmetry: bool = False,
                  start_positions=None, resign: dict = None, evaluator: BatchPolicyValueFn = None,
-                 playout_cap: dict = None, forced_playouts: dict = None, gumbel: dict = None):
+                 playout_cap: dict = None, forced_playouts: dict = None, gumbel: dict = None, solver: bool = False):
         self.controller = controller
         # opt-in: a controller.BatchPolicyValueFn evaluates every leaf instead of the engine's own net kernels (any torch
         # net on the same GPU; az_set_external_evaluator).  Not with subtree_reuse or leaf_symmetry; eval_cache and trunk
@@ -146,6 +146,11 @@ class SelfPlayManager:
         # Q)) (az_set_gumbel); the engine fills the game tapes with Gumbel draws.  Not with subtree_reuse, virtual_loss > 1,
         # forced_playouts or an external evaluator.
         self.gumbel = check_gumbel(gumbel, subtree_reuse, virtual_loss, self.forced_playouts, evaluator)
+        # opt-in MCTS-Solver: every search keeps proven wins, losses and draws in its tree; pi never spreads mass over refuted
+        # moves while a better one is known, a proven root records an exact value (az_set_solver).  Not with subtree_reuse,
+        # virtual_loss > 1, forced_playouts, gumbel or an external evaluator.  Whether it trains a stronger net per GPU hour
+        # has not been measured.
+        self.solver = check_solver(solver, subtree_reuse, virtual_loss, self.forced_playouts, self.gumbel, evaluator)
         self.temperature_schedule = temperature_schedule
         self.concurrent_games = concurrent_games or _c.CONCURRENT_GAMES
         self.augmentation = augmentation      # 4 = the reference's rotations (self_play.py:94-108), 8 = full dihedral group, 1 = none
@@ -269,6 +274,9 @@ class SelfPlayManager:
             eng.set_gumbel(min(self.gumbel["m"], n * n), self.gumbel["c_visit"], self.gumbel["c_scale"])
         elif eng.gumbel()["m"]:
             eng.set_gumbel(0)
+        self.solver = check_solver(self.solver, self.subtree_reuse, self.virtual_loss, self.forced_playouts, self.gumbel, self.evaluator)
+        if self.solver != eng.solver():
+            eng.set_solver(self.solver)
         if mine > 0:
             self.last_counters = eng.selfplay(mine, seed0=seed0 + lo, temperature_table=T)
             if self.resign is not None:

@@ -28,7 +28,7 @@ PROMOTION_THRESHOLD = 0.55          # promoter.py:19, strict ">" with draws coun
 
 def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=None, log=print, device_replay=False,
         subtree_reuse=False, trunk="f32", eval_sims=None, start_positions=None, resign=None, torch_eval=False,
-        playout_cap=None, forced_playouts=None, gumbel=None):
+        playout_cap=None, forced_playouts=None, gumbel=None, solver=False):
     """eval_sims: simulations per move in the arena (evaluator.py:53-62 takes NUM_EVAL_SIMULATIONS = 200 whatever the
     self-play count is; main() passes that constant); None = as many as self-play, which keeps small test runs short.
     device_replay=True keeps the examples on the GPU from the episode-end gather to the optimizer step (packed records
@@ -47,6 +47,9 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
     gumbel: dict(m, c_visit, c_scale) for the self-play games (Engine.set_gumbel): every noised root is searched by sequential
     halving over m Gumbel-top candidates and the policy target is softmax(logits + sigma(completed Q)).  Not with
     forced_playouts, subtree_reuse or torch_eval.  The arena is untouched.
+    solver=True: MCTS-Solver in the self-play searches (Engine.set_solver): proven wins, losses and draws are kept in the tree,
+    the policy target leaves refuted moves out and a proven root records an exact value.  Not with forced_playouts, gumbel,
+    subtree_reuse or torch_eval.  The arena is untouched.  Whether it trains a stronger net per GPU hour is not measured.
     torch_eval=True: the searches of self-play and the arena are evaluated by the controllers' own torch modules on the GPU
     (controller.make_batch_policy_value_fn, az_set_external_evaluator) instead of the engine's net kernels -- the loop a
     changed net.py runs on before it has kernels of its own."""
@@ -61,7 +64,7 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
     manager = SelfPlayManager(candidate, device, mcts_params={"num_simulations": sims, "c_puct": C.SELF_PLAY_EXPLORATION_CONSTANT},
                               seed=seed, subtree_reuse=subtree_reuse, gather_to=0 if world > 1 else None, trunk=trunk,
                               start_positions=start_positions, resign=resign, playout_cap=playout_cap,
-                              forced_playouts=forced_playouts, gumbel=gumbel,
+                              forced_playouts=forced_playouts, gumbel=gumbel, solver=solver,
                               evaluator=make_batch_policy_value_fn(candidate.net, device) if torch_eval else None)
     evaluator = ModelEvaluator(game_class=Gomoku, print_games=False, device=device, seed=seed,
                                evaluators=True if torch_eval else None)
@@ -158,6 +161,9 @@ def main():
                          "halving, policy target from the completed Q values (1 <= M <= 64; the paper uses 16)")
     ap.add_argument("--gumbel-c-visit", type=float, default=None, metavar="X", help="with --gumbel: c_visit of sigma (default 50)")
     ap.add_argument("--gumbel-c-scale", type=float, default=None, metavar="Y", help="with --gumbel: c_scale of sigma (default 1)")
+    ap.add_argument("--solver", action="store_true",
+                    help="MCTS-Solver in the self-play searches: proven wins, losses and draws are kept in the tree, the policy "
+                         "target leaves refuted moves out and a proven root records an exact value")
     ap.add_argument("--torch-eval", action="store_true",
                     help="evaluate the searches with the controller's own torch module as a batched external evaluator "
                          "(any net; no HIP trunk needed) instead of the engine's net kernels")
@@ -203,7 +209,7 @@ def main():
     run(a.episodes, a.games, a.sims, a.eval_games, a.device, model_dir=a.model_dir, device_replay=a.device_replay,
         subtree_reuse=a.subtree_reuse, trunk=a.trunk, eval_sims=C.NUM_EVAL_SIMULATIONS, start_positions=start_positions,
         resign=resign, torch_eval=a.torch_eval, playout_cap=playout_cap, forced_playouts=forced_playouts,
-        gumbel=gumbel)
+        gumbel=gumbel, solver=a.solver)
     if world > 1:
         td.barrier()
         td.destroy_process_group()

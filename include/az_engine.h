@@ -642,6 +642,63 @@ int az_gumbel_target(int count, const float *logits, const double *g, const int3
 /* v_mix alone, as az_gumbel_target forms it: NaN for a bad argument */
 double az_gumbel_vmix(int count, const int32_t *visits, const double *W, const float *prior, float root_value);
 
+/* Opt-in MCTS-Solver (Winands, Bjornsson, Saito 2008): proven wins, losses and draws in the search tree.  The reference's
+ * mcts.py has nothing of the kind; off by default, and with the option off nothing below is read, written or executed.
+ *
+ * Rule.  Every edge has a status, seen from the side that makes the move: */
+enum { AZ_PROOF_UNKNOWN = 0, AZ_PROOF_WIN = 1, AZ_PROOF_LOSS = 2, AZ_PROOF_DRAW = 3 };
+/* A node's status, seen from its side to move, is computed over its legal cells (the empty cells at that node): WIN if any
+ * edge is WIN; otherwise, if every legal edge is proven, DRAW if any edge is DRAW, else LOSS; otherwise UNKNOWN.
+ * With az_set_solver(e, 1) every search applies the rule -- self-play, arena, az_search and az_search_batch, with or without
+ * root noise, the FULL and the FAST plies of the playout cap alike.  In one simulation:
+ *   Selection, at every level and at the root.  The scores are the PUCT scores.  A WIN edge then scores +infinity, and a LOSS
+ *   edge -infinity provided the row has at least one legal edge that is not LOSS; if every legal edge is LOSS (the root only)
+ *   the plain scores decide.  The first maximum in row-major order is taken, as without the option.
+ *   After the move the real terminal tests come first (a line through the stone, a full board).  If neither holds and the
+ *   edge's status is not UNKNOWN the simulation ends on that edge: no evaluation is made, no row is allocated, and it backs
+ *   up -1 for a WIN edge, +1 for a LOSS edge and 0 for a DRAW edge as the value of the side to move below the edge; it counts
+ *   as a terminal hit (az_counters.terminal_hits).  Otherwise the simulation expands or descends.
+ *   Backup is unchanged.
+ *   Marking, only when the simulation ended on a real terminal whose edge was UNKNOWN: that edge becomes WIN for the mover
+ *   if the move made the line, DRAW if it filled the board.  Then, walking the path upwards: the status of the node that
+ *   owns the edge is computed; if it is UNKNOWN the walk stops; otherwise the edge above it gets the negated status (WIN
+ *   and LOSS swap, DRAW stays), and at the top the root's own status is kept.  A proven edge is never descended through,
+ *   so the walk never meets an edge that is already proven.
+ * At the end of the search, with st the root row's statuses, pi and the sampled move are made from the count vector N': if
+ * any root edge is WIN, the counts of the WIN edges and 0 elsewhere (a WIN edge has at least one visit); otherwise, if some
+ * legal edge that is not LOSS has a visit, 0 on the LOSS edges; otherwise the raw counts.  The temperature / cumsum /
+ * searchsorted path is unchanged, and the record's visits stay the raw ones.  The record's value (az_selfplay_values) is
+ * exactly +1, -1 or 0 when the root is proven WIN, LOSS or DRAW, else W[a*] / N[a*] as always; resignation reads it
+ * unchanged, so a proven loss resigns by itself.  The number of simulations stays num_simulations (no early out), games are
+ * played to their real end, z is unchanged.
+ *
+ * az_last_proof(e, capacity, edges, roots, count): after az_search, edges[n*n] and roots[1]; after az_search_batch,
+ * edges[positions][n*n] and roots[positions] -- the root row's statuses (0 on occupied cells) and the root's status.  *count
+ * receives the number of positions the engine holds (1 after az_search); capacity is the number of positions the caller's
+ * buffers hold, and a call with a buffer and capacity < *count writes nothing but *count and returns AZ_ERR_INVALID.  Any
+ * pointer may be NULL (edges = roots = NULL asks for the count).  AZ_ERR_STATE when the last search or episode on the engine
+ * was not such a search with the solver on.
+ * az_solver_stops(e, stops): the simulations of the last (or open) episode, az_search or az_search_batch call that ended on
+ * a proven edge (they are terminal hits in az_counters as well); 0 with the option off.  az_selfplay_proofs(e, roots): the root status of every record of the last episode, indexed like
+ * az_selfplay_values; AZ_ERR_STATE without an episode or when it ran without the solver.
+ * az_solver_counts(count, visits, status, out) restates N' on the host for one root row of `count` legal children with the
+ * function the kernel uses (no GPU needed); AZ_ERR_INVALID for a null pointer, count < 1, a negative visit count or a
+ * status outside 0 .. 3.
+ * Combines with both nets, the evaluation cache, leaf symmetry, the emulated trunks, deep engines, start positions,
+ * resignation, max_plies, the playout cap, the arena, az_search_batch and the step API (az_selfplay_begin / _step / _end).  Refused with AZ_ERR_INVALID,
+ * whichever is set first: subtree reuse, virtual-loss batching, forced playouts, the Gumbel root search, the batched external
+ * evaluator (az_set_external_evaluator: refused, not supported) and engines created with AZ_EVAL_SYNTHETIC;
+ * az_search_callback with the option set returns AZ_ERR_INVALID as well.  The persistent search kernel serves the solver
+ * with one status byte per edge behind the edges in LDS; where the rows and the bytes of a configuration do not fit together
+ * the searches run on the lock-step pipeline (az_get_persistent says which).
+ * AZ_ERR_INVALID for on outside 0 / 1, AZ_ERR_STATE while an episode is open. */
+int az_set_solver(az_engine *e, int on);
+int az_get_solver(const az_engine *e);
+int az_last_proof(az_engine *e, int capacity, int8_t *edges, int8_t *roots, int32_t *count);
+int az_solver_stops(const az_engine *e, int64_t *stops);
+int az_selfplay_proofs(az_engine *e, int8_t *roots);
+int az_solver_counts(int count, const int32_t *visits, const int8_t *status, int32_t *out);
+
 /* Opt-in: fp32-emulating conv trunks.  AZ_TRUNK_F32 (default) computes the net's forward (net.py:55-72) on the float32
  * matrix instruction in the build's canonical fp order: bit-identical to the oracle.  The other two run every conv but the
  * first (99 % of the net's arithmetic) and the 1x1 head convs on the 16 x faster 16-bit matrix instructions with split
