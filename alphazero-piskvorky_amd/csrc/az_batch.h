@@ -1,8 +1,10 @@
-// az_batch.h -- az_search_batch: many given positions into the slots, and every slot's root statistics back out.
+// az_batch.h -- az_search, az_search_batch, az_search_callback: given positions into the slots, and every slot's root
+// statistics back out.
 //
-// A wave of the batch is one ply of every lane of the engine: position i of the wave sits in slot b of lane l with
-// i = lane.first + b, b < lane.m, and is game i of a one-ply episode (its noise row, u, temperature and record are indexed
-// by i).  Both kernels run one 64-lane wavefront per slot over ALL lanes of the engine in one launch; the lanes' buffers
+// A wave of the batch is one ply of the lanes it is spread over (all of them, or lane 0 alone for one position): position i
+// of the wave sits in slot b of lane l with i = lane.first + b, b < lane.m, and is game i of a one-ply episode (its noise
+// row, u, temperature and record are indexed by i).  Both kernels run one 64-lane wavefront per slot over all those lanes in
+// one launch; the lanes' buffers
 // are separate allocations, so their pointers travel by value in a BatchLanes table.  Neither kernel is compute-bound:
 // what matters is one launch per wave and coalesced traffic.
 #pragma once
@@ -55,8 +57,8 @@ __device__ __forceinline__ u64 cells_to_planes(const unsigned char *__restrict__
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_set_positions: cells[wave][n*n] -> the slots' bit-planes and game state, as k_set_position and k_refill do for one
-// slot.  Slots beyond the lane's share go idle.
+// k_set_positions: cells[wave][n*n] -> the slots' bit-planes and game state, as k_refill does for a claimed game.  Slots
+// beyond the lane's share go idle.
 // ------------------------------------------------------------------------------------------------
 template <int N>
 __global__ __launch_bounds__(256) void k_set_positions(BatchLanes bl, const unsigned char *__restrict__ cells,

@@ -78,7 +78,7 @@ struct Lane {
     double trunk_ms = 0.0, nn_ms = 0.0, step_ms = 0.0;
     double tape_wait_s = 0.0;      // host time this lane's thread was blocked on a tape wave (production or its upload)
     int rc = AZ_OK;                // result of the last threaded call on this lane
-    int preset_m = 0;              // preset episodes (az_search, az_search_batch): the first preset_m slots hold given positions
+    int preset_m = 0;              // preset episodes (preset_search): the first preset_m slots hold given positions
     std::string err;
 };
 
@@ -114,9 +114,12 @@ struct az_engine {
         DevBuf map, count;
         int64_t requests = 0, items = 0;
     } ext;
-    // az_search_batch, all sized by the slots: the wave's positions, temperatures and compact root statistics, and the all-zero
-    // noise_off table that makes row g of the [wave][n*n] noise upload the tape of game g
+    // preset searches (az_search*), all sized by the slots: the wave's positions, temperatures and compact root statistics, and
+    // the all-zero noise_off table that makes row g of the [wave][n*n] noise upload the tape of game g
     DevBuf bt_cells, bt_players, bt_lasts, bt_T, bt_zero_off, bt_visits, bt_W, bt_prior, bt_pi, bt_action;
+    // az_search_callback: the buffers of the engine's own external evaluator, slots x leaves per batch entries as episode_begin
+    // asks of any (allocated by the first callback search)
+    DevBuf cb_planes, cb_policy, cb_value;
     unsigned cache_mask = 0, cache_gen = 1;
     // az_set_start_positions: the device table k_refill loads claimed games from, and each position's stone count on the host
     DevBuf start_tab;
@@ -278,7 +281,56 @@ static int upload(az_engine *e, DevBuf &b, const void *src, size_t bytes)
 }
 
 // ------------------------------------------------------------------------------------------------
-// weight packing: B-operand fragments of v_mfma_f32_16x16x4_f32.  Lane l supplies B[k = l>>4][j = l&15]
+// Settings that cannot be combined: every pair once, with the text both setters refuse it with.  A setter that switches
+// its setting ON calls refuse_conflicts; the first row with an active partner names the error.
+// ------------------------------------------------------------------------------------------------
+enum Setting {
+    SET_REUSE, SET_VL, SET_VL_KERNEL, SET_SYMMETRY, SET_EXT, SET_CAP, SET_FORCED, SET_GUMBEL, SET_SOLVER,
+    SET_SYNTHETIC, SET_NO_NET          // facts of az_config: the synthetic evaluator; any evaluator but the net
+};
+static const struct { Setting a, b; const char *message; } g_conflicts[] = {
+    {SET_REUSE, SET_VL, "subtree reuse and virtual-loss batching cannot be combined"},
+    {SET_REUSE, SET_EXT, "subtree reuse and the external evaluator cannot be combined"},
+    {SET_CAP, SET_REUSE, "the playout cap and subtree reuse cannot be combined"},
+    {SET_FORCED, SET_REUSE, "forced playouts and subtree reuse cannot be combined"},
+    {SET_GUMBEL, SET_REUSE, "the Gumbel root search and subtree reuse cannot be combined"},
+    {SET_SOLVER, SET_REUSE, "the solver and subtree reuse cannot be combined"},
+    {SET_CAP, SET_EXT, "the playout cap and the external evaluator cannot be combined"},
+    {SET_SYMMETRY, SET_NO_NET, "random-symmetry leaf evaluation needs the net evaluator"},
+    {SET_SYMMETRY, SET_EXT, "random-symmetry leaf evaluation and the external evaluator cannot be combined"},
+    {SET_GUMBEL, SET_VL_KERNEL, "the Gumbel root search and virtual-loss batching cannot be combined"},
+    {SET_FORCED, SET_GUMBEL, "forced playouts and the Gumbel root search cannot be combined"},
+    {SET_GUMBEL, SET_EXT, "the Gumbel root search and the external evaluator cannot be combined (it returns priors, not logits)"},
+    {SET_GUMBEL, SET_SYNTHETIC, "the Gumbel root search needs a net: the synthetic evaluator has no logits"},
+    {SET_SOLVER, SET_VL_KERNEL, "the solver and virtual-loss batching cannot be combined"},
+    {SET_SOLVER, SET_FORCED, "the solver and forced playouts cannot be combined"},
+    {SET_SOLVER, SET_GUMBEL, "the solver and the Gumbel root search cannot be combined"},
+    {SET_SOLVER, SET_EXT, "the solver and the external evaluator cannot be combined"},
+    {SET_SOLVER, SET_SYNTHETIC, "the solver and the synthetic evaluator cannot be combined"},
+};
+
+// bit s = setting s is on.  Virtual-loss batching has two: more than one leaf per batch, and the batched tree kernel being in
+// use at all (AZ_VL_FORCE=1 runs it with batches of one), which is what the Gumbel root search and the solver go by.
+static unsigned active_settings(const az_engine *e)
+{
+    const bool on[] = {e->reuse != 0, e->vl > 1, e->vl > 1 || e->vl_kernel, e->leaf_symmetry != 0, e->ext.on, e->cap_fast != 0,
+                       e->forced_k > 0.0, e->gumbel_m > 0, e->solver != 0,
+                       e->cfg.eval_kind == AZ_EVAL_SYNTHETIC, e->cfg.eval_kind != AZ_EVAL_NET};
+    unsigned m = 0;
+    for (int s = 0; s <= SET_NO_NET; s++) m |= on[s] ? 1u << s : 0u;
+    return m;
+}
+
+static int refuse_conflicts(az_engine *e, Setting s)
+{
+    const unsigned active = active_settings(e);
+    for (const auto &c : g_conflicts)
+        if ((c.a == s && (active >> c.b & 1u)) || (c.b == s && (active >> c.a & 1u))) return fail(e, AZ_ERR_INVALID, "%s", c.message);
+    return AZ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// weight packing:B-operand fragments of v_mfma_f32_16x16x4_f32.  Lane l supplies B[k = l>>4][j = l&15]
 // of k-step s; four consecutive k-steps are stored together so one dwordx4 load feeds four MFMAs:
 //   packed[((ntile*KS4 + s/4)*64 + lane)*4 + s%4]
 // ------------------------------------------------------------------------------------------------
@@ -831,7 +883,8 @@ extern "C" void az_destroy(az_engine *e)
     DevBuf *shared[] = {&e->T_table, &e->log_table, &e->sqrt_table, &e->noise_off, &e->next_game, &e->noise, &e->u,
                         &e->rec_planes, &e->rec_last, &e->rec_action, &e->rec_mover, &e->rec_pi, &e->rec_visits, &e->g_nply,
                         &e->g_result, &e->src_index, &e->rec_value, &e->g_cross, &e->cache, &e->start_tab, &e->bt_cells, &e->bt_players, &e->bt_lasts, &e->bt_T,
-                        &e->bt_zero_off, &e->bt_visits, &e->bt_W, &e->bt_prior, &e->bt_pi, &e->bt_action, &e->ext.map, &e->ext.count, &e->gumbel_seq, &e->rec_proof};
+                        &e->bt_zero_off, &e->bt_visits, &e->bt_W, &e->bt_prior, &e->bt_pi, &e->bt_action, &e->ext.map, &e->ext.count, &e->gumbel_seq, &e->rec_proof,
+                        &e->cb_planes, &e->cb_policy, &e->cb_value};
     for (DevBuf *b : shared) dev_free(*b);
     for (int s = 0; s < 2; s++) {
         PackedNet &p = e->net[s];
@@ -1006,8 +1059,8 @@ static int ensure_episode_buffers(az_engine *e, int games, bool need_noise)
 struct EpisodeSpec {
     int num_games = 0, max_plies = 0;
     bool add_noise = true, arena = false;
-    bool preset = false;      // the first Lane::preset_m slots of every lane already hold positions (az_search: slot 0 of lane 0); skip the initial refill
-    bool batch = false;       // preset by az_search_batch: the ply runs over the preset slots only, throughput kernel choices as in self-play
+    bool preset = false;      // the first Lane::preset_m slots of every lane already hold positions (preset_search); skip the initial refill
+    bool batch = false;       // ... of az_search_batch: the ply runs over the preset slots only, throughput kernel choices as in self-play
     bool profile = true;      // this episode may be timed with HIP events (only when az_set_profiling is on)
     unsigned game_key0 = 0;   // low 32 bits of seed0: the leaf-symmetry hash names game g by its seed, seed0 + g
     int ext_net = -1;         // external evaluator: the net id of the requests (az_search*: the slot argument), -1 = the items' own
@@ -1868,8 +1921,7 @@ extern "C" int az_set_playout_cap(az_engine *e, int fast_sims, int full_permille
         (export_full_only != 0 && export_full_only != 1))
         return fail(e, AZ_ERR_INVALID, "az_set_playout_cap: fast_sims %d (0 = off, else 1..%d), full_permille %d (0..1000), export_full_only %d (0 / 1)",
                     fast_sims, e->cfg.num_simulations, full_permille, export_full_only);
-    if (e->reuse) return fail(e, AZ_ERR_INVALID, "the playout cap and subtree reuse cannot be combined");
-    if (e->ext.on) return fail(e, AZ_ERR_INVALID, "the playout cap and the external evaluator cannot be combined");
+    if (refuse_conflicts(e, SET_CAP)) return AZ_ERR_INVALID;
     e->cap_fast = fast_sims; e->cap_permille = full_permille; e->cap_export_full = export_full_only;
     return AZ_OK;
 }
@@ -1894,9 +1946,7 @@ extern "C" int az_set_forced_playouts(az_engine *e, double k, int prune)
     }
     if (!(k > 0.0 && k <= 16.0) || (prune != 0 && prune != 1))
         return fail(e, AZ_ERR_INVALID, "az_set_forced_playouts: k %g (0 = off, else in (0, 16]), prune %d (0 / 1)", k, prune);
-    if (e->reuse) return fail(e, AZ_ERR_INVALID, "forced playouts and subtree reuse cannot be combined");
-    if (e->gumbel_m > 0) return fail(e, AZ_ERR_INVALID, "forced playouts and the Gumbel root search cannot be combined");
-    if (e->solver) return fail(e, AZ_ERR_INVALID, "the solver and forced playouts cannot be combined");
+    if (refuse_conflicts(e, SET_FORCED)) return AZ_ERR_INVALID;
     e->forced_k = k; e->forced_prune = prune;
     return AZ_OK;
 }
@@ -1969,12 +2019,7 @@ extern "C" int az_set_gumbel(az_engine *e, int m, double c_visit, double c_scale
     if (m < 0 || m > std::min(e->nn, 64) || !(c_visit >= 0.0) || !std::isfinite(c_visit) || !(c_scale > 0.0) || !std::isfinite(c_scale))
         return fail(e, AZ_ERR_INVALID, "az_set_gumbel: m %d (0 = off, else 1..%d), c_visit %g (>= 0), c_scale %g (> 0)", m,
                     std::min(e->nn, 64), c_visit, c_scale);
-    if (e->reuse) return fail(e, AZ_ERR_INVALID, "the Gumbel root search and subtree reuse cannot be combined");
-    if (e->vl > 1 || e->vl_kernel) return fail(e, AZ_ERR_INVALID, "the Gumbel root search and virtual-loss batching cannot be combined");
-    if (e->forced_k > 0.0) return fail(e, AZ_ERR_INVALID, "forced playouts and the Gumbel root search cannot be combined");
-    if (e->ext.on) return fail(e, AZ_ERR_INVALID, "the Gumbel root search and the external evaluator cannot be combined (it returns priors, not logits)");
-    if (e->cfg.eval_kind == AZ_EVAL_SYNTHETIC) return fail(e, AZ_ERR_INVALID, "the Gumbel root search needs a net: the synthetic evaluator has no logits");
-    if (e->solver) return fail(e, AZ_ERR_INVALID, "the solver and the Gumbel root search cannot be combined");
+    if (refuse_conflicts(e, SET_GUMBEL)) return AZ_ERR_INVALID;
     DEVICE_GUARD(e);
     // the schedules of k = 1 .. m candidates (a root has min(m, legal cells) of them), one row of S entries each
     const int S = e->cfg.num_simulations;
@@ -2202,12 +2247,7 @@ extern "C" int az_set_solver(az_engine *e, int on)
         e->proof_edges.clear(); e->proof_roots.clear();
         return AZ_OK;
     }
-    if (e->reuse) return fail(e, AZ_ERR_INVALID, "the solver and subtree reuse cannot be combined");
-    if (e->vl > 1 || e->vl_kernel) return fail(e, AZ_ERR_INVALID, "the solver and virtual-loss batching cannot be combined");
-    if (e->forced_k > 0.0) return fail(e, AZ_ERR_INVALID, "the solver and forced playouts cannot be combined");
-    if (e->gumbel_m > 0) return fail(e, AZ_ERR_INVALID, "the solver and the Gumbel root search cannot be combined");
-    if (e->ext.on) return fail(e, AZ_ERR_INVALID, "the solver and the external evaluator cannot be combined");
-    if (e->cfg.eval_kind == AZ_EVAL_SYNTHETIC) return fail(e, AZ_ERR_INVALID, "the solver and the synthetic evaluator cannot be combined");
+    if (refuse_conflicts(e, SET_SOLVER)) return AZ_ERR_INVALID;
     DEVICE_GUARD(e);
     // one status byte per edge beside every slot's tree
     size_t need = 0;
@@ -2286,81 +2326,23 @@ extern "C" int az_solver_counts(int count, const int32_t *visits, const int8_t *
     return AZ_OK;
 }
 
-extern "C" int az_search(az_engine *e, int slot, const uint8_t *board, int player, int last, double temperature,
-                         const double *noise, double u, float *pi, int32_t *action, int32_t *visits, double *W,
-                         float *prior)
+// ---- searches of given positions: MCTS.run for one position (az_search, az_search_callback) or every position of a list ----
+// one given position, checked on the host; `who` names the entry point (and the position) in the error text
+static int check_position(az_engine *e, const char *who, const uint8_t *bd, int player, int last, int *stones)
 {
-    if (!e || !board || (player != 1 && player != 2) || slot < 0 || slot > 1) return fail(e, AZ_ERR_INVALID, "az_search: bad argument");
-    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_search: a self-play episode is open on this engine");
-    DEVICE_GUARD(e);
     const int nn = e->nn;
-    int stones = 0;
+    if (player != 1 && player != 2) return fail(e, AZ_ERR_INVALID, "%s: player %d", who, player);
+    int st = 0;
     for (int j = 0; j < nn; j++) {
-        if (board[j] > 2) return fail(e, AZ_ERR_INVALID, "az_search: cell value %d", board[j]);
-        stones += board[j] != 0;
+        if (bd[j] > 2) return fail(e, AZ_ERR_INVALID, "%s: cell value %d", who, bd[j]);
+        st += bd[j] != 0;
     }
-    if (stones >= nn) return fail(e, AZ_ERR_INVALID, "az_search: no legal action");
-    if (last >= nn || (last >= 0 && board[last] == 0)) return fail(e, AZ_ERR_INVALID, "az_search: bad last action");
-    e->proof_edges.clear(); e->proof_roots.clear();
-    int rc = ensure_episode_buffers(e, 1, true);
-    if (rc) return rc;
-    std::vector<double> T(nn + 1, temperature);
-    if ((rc = upload_T(e, T.data(), false))) return rc;
-    // tape: the single ply `stones`
-    std::vector<double> hn((size_t)e->tape_len, 0.0), hu(nn, u);
-    int off = 0;
-    for (int m = 0; m < stones; m++) off += nn - m;
-    if (noise) memcpy(hn.data() + off, noise, (size_t)(nn - stones) * 8);
-    HIPCHECK(e, az_memcpy(e->stream, e->noise.p, hn.data(), hn.size() * 8, hipMemcpyHostToDevice));
-    HIPCHECK(e, az_memcpy(e->stream, e->u.p, hu.data(), hu.size() * 8, hipMemcpyHostToDevice));
-    u64 bd[8];
-    planes_from_cells(board, nn, bd, bd + 4);
-    Lane &L0 = e->lanes[0];
-    HIPCHECK(e, hipMemsetAsync(L0.s_status.p, 0, L0.s_status.bytes, e->stream));
-    HIPCHECK(e, hipMemcpyAsync(L0.board.p, bd, sizeof bd, hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(k_set_position, dim3(1), dim3(64), 0, e->stream, L0.d, 0, 0, player, last, stones);
-    HIPCHECK(e, hipStreamSynchronize(e->stream));
-    EpisodeSpec sp;
-    sp.num_games = 1; sp.max_plies = 0; sp.add_noise = noise != nullptr; sp.arena = false; sp.preset = true; sp.profile = false;
-    sp.ext_net = slot;
-    // the arena flag only selects the net through s_player; a search with the baseline net uses slot 1 weights as slot 0
-    PackedNet saved0 = e->net[0];
-    const float *sv2w = L0.d.v2w[0], *sv2b = L0.d.v2b[0];
-    // (the evaluation cache keys its entries by net id: the swapped search runs under its own cache generation)
-    if (slot == 1) { e->net[0] = e->net[1]; L0.d.v2w[0] = L0.d.v2w[1]; L0.d.v2b[0] = L0.d.v2b[1]; e->cache_gen ^= 0x80000000u; }
-    for (Lane &L : e->lanes) L.preset_m = L.index == 0 ? 1 : 0;
-    rc = run_episode(e, sp, nullptr);
-    if (slot == 1) {
-        e->net[0] = saved0; e->cache_gen ^= 0x80000000u;
-        // put back in the states AND their item views (Lane::dv, refreshed by each_state): episode_begin copied the swapped
-        // pointers there, and az_net_eval's tail reads them through the item view without an episode_begin of its own
-        each_state(e, [&](DevState &d) { d.v2w[0] = sv2w; d.v2b[0] = sv2b; d.cache_gen = e->cache_gen; });
-    }
-    if (rc) return rc;
-    // outputs: record 0*nn + stones
-    const size_t ri = (size_t)stones;
-    if (pi) HIPCHECK(e, az_memcpy(e->stream, pi, (float *)e->rec_pi.p + ri * nn, (size_t)nn * 4, hipMemcpyDeviceToHost));
-    if (action) {
-        short a = -1;
-        HIPCHECK(e, az_memcpy(e->stream, &a, (short *)e->rec_action.p + ri, 2, hipMemcpyDeviceToHost));
-        *action = a;
-    }
-    if (visits || W || prior) {
-        std::vector<Edge> row(e->RW);
-        HIPCHECK(e, az_memcpy(e->stream, row.data(), L0.edges.p, row.size() * sizeof(Edge), hipMemcpyDeviceToHost));
-        for (int j = 0; j < nn; j++) {
-            const bool legal = board[j] == 0;
-            if (visits) visits[j] = legal ? row[j].N : 0;
-            if (W) W[j] = legal ? row[j].W : 0.0;
-            if (prior) prior[j] = legal ? row[j].P : 0.0f;
-        }
-    }
-    if (e->solver && (rc = fetch_proofs(e, L0, 1, board, 0))) return rc;
-    e->have_episode = false;
+    if (st >= nn) return fail(e, AZ_ERR_INVALID, "%s: no legal action", who);
+    if (last >= nn || (last >= 0 && bd[last] == 0)) return fail(e, AZ_ERR_INVALID, "%s: bad last action", who);
+    if (stones) *stones = st;
     return AZ_OK;
 }
 
-// ---- many positions at once: MCTS.run for every position of a list ----
 // Waves of at most `slots` positions; a wave is ONE ply of every lane (a one-ply episode whose game i is position i of the
 // wave), so the searches of a wave share every evaluation batch.  Position i of the wave sits in slot i - first(l) of lane l.
 static void add_counters(az_counters &t, const az_counters &c)
@@ -2374,32 +2356,19 @@ static void add_counters(az_counters &t, const az_counters &c)
     t.tape_threads = c.tape_threads; t.host_cpus = c.host_cpus;
 }
 
-extern "C" int az_search_batch(az_engine *e, int slot, int count, const uint8_t *boards, const uint8_t *players,
-                               const int16_t *lasts, const double *temperatures, const double *noise, const double *u,
-                               float *pi, int32_t *actions, int32_t *visits, double *W, float *prior)
+// The search of `count` checked positions, arguments as az_search_batch.  batch: the positions go over every lane, the ply
+// runs over the slots that hold one and the kernels are chosen for throughput, as in self-play (EpisodeSpec::batch); else
+// they sit in the first slots of lane 0, whose ply runs over its whole grid (the captured graph) on the latency choices.
+static int preset_search(az_engine *e, bool batch, int slot, int count, const uint8_t *boards, const uint8_t *players,
+                         const int16_t *lasts, const double *temperatures, const double *noise, const double *u,
+                         float *pi, int32_t *actions, int32_t *visits, double *W, float *prior)
 {
-    if (!e || slot < 0 || slot > 1 || count < 0) return fail(e, AZ_ERR_INVALID, "az_search_batch: bad argument");
-    if (count == 0) return AZ_OK;
-    if (!boards || !players || !lasts || !temperatures || !u) return fail(e, AZ_ERR_INVALID, "az_search_batch: null argument");
-    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_search_batch: a self-play episode is open on this engine");
-    const int nn = e->nn, K = (int)e->lanes.size();
-    // every position is checked on the host before any GPU work: an error leaves every output untouched
-    for (int i = 0; i < count; i++) {
-        const uint8_t *bd = boards + (size_t)i * nn;
-        if (players[i] != 1 && players[i] != 2) return fail(e, AZ_ERR_INVALID, "az_search_batch: position %d: player %d", i, players[i]);
-        int st = 0;
-        for (int j = 0; j < nn; j++) {
-            if (bd[j] > 2) return fail(e, AZ_ERR_INVALID, "az_search_batch: position %d: cell value %d", i, bd[j]);
-            st += bd[j] != 0;
-        }
-        if (st >= nn) return fail(e, AZ_ERR_INVALID, "az_search_batch: position %d: no legal action", i);
-        if (lasts[i] >= nn || (lasts[i] >= 0 && bd[lasts[i]] == 0)) return fail(e, AZ_ERR_INVALID, "az_search_batch: position %d: bad last action", i);
-    }
+    const int nn = e->nn, K = batch ? (int)e->lanes.size() : 1;
     if (!e->ext.on && e->cfg.eval_kind == AZ_EVAL_NET && !e->net[slot].loaded) return fail(e, AZ_ERR_NO_WEIGHTS, "weights slot %d not loaded", slot);
     if (K > BATCH_MAX_LANES) return fail(e, AZ_ERR_INVALID, "az_search_batch: more than %d lanes", BATCH_MAX_LANES);
     DEVICE_GUARD(e);
     e->proof_edges.clear(); e->proof_roots.clear();
-    const int Wv = std::min(count, e->cfg.slots);           // positions per wave: everything below is sized by it, not by count
+    const int Wv = std::min(count, batch ? e->cfg.slots : e->lanes[0].d.B);     // positions per wave: everything below is sized by it, not by count
     int rc = ensure_episode_buffers(e, Wv, false);
     const size_t wn = (size_t)Wv * nn;
     if (!rc && noise) rc = dev_alloc(e, e->noise, wn * 8, false);
@@ -2415,8 +2384,9 @@ extern "C" int az_search_batch(az_engine *e, int slot, int count, const uint8_t 
     if (!rc && actions) rc = dev_alloc(e, e->bt_action, (size_t)Wv * 4, false);
     if (rc) return rc;
     // The lanes' states for this call: per-position temperatures, key 0 for every position, and the compact noise rows.  The
-    // baseline net (slot 1) searches as net 0 under its own cache generation, like az_search.  Everything is put back on
-    // every way out, so that no other entry point ever sees these values.
+    // baseline net (slot 1) searches as net 0 (the arena flag only selects the net through s_player) under its own cache
+    // generation (the evaluation cache keys its entries by net id).  Everything is put back on every way out -- in the states
+    // AND their item views, which az_net_eval's tail reads -- so that no other entry point ever sees these values.
     const PackedNet saved0 = e->net[0];
     const float *sv2w = e->lanes[0].d.v2w[0], *sv2b = e->lanes[0].d.v2b[0];
     struct Restore {
@@ -2439,7 +2409,7 @@ extern "C" int az_search_batch(az_engine *e, int slot, int count, const uint8_t 
         if (slot == 1) { d.v2w[0] = d.v2w[1]; d.v2b[0] = d.v2b[1]; }
     });
     EpisodeSpec sp;
-    sp.max_plies = 0; sp.add_noise = noise != nullptr; sp.arena = false; sp.preset = true; sp.batch = true; sp.profile = false;
+    sp.max_plies = 0; sp.add_noise = noise != nullptr; sp.arena = false; sp.preset = true; sp.batch = batch; sp.profile = false;
     sp.ext_net = slot;
     az_counters total{};
     int64_t ext_requests = 0, ext_items = 0;       // az_ext_stats reports the whole call, like the counters
@@ -2518,6 +2488,46 @@ extern "C" int az_search_batch(az_engine *e, int slot, int count, const uint8_t 
     e->solver_stops = batch_stops;
     if (e->ext.on) { e->ext.requests = ext_requests; e->ext.items = ext_items; }
     return AZ_OK;
+}
+
+extern "C" int az_search_batch(az_engine *e, int slot, int count, const uint8_t *boards, const uint8_t *players,
+                               const int16_t *lasts, const double *temperatures, const double *noise, const double *u,
+                               float *pi, int32_t *actions, int32_t *visits, double *W, float *prior)
+{
+    if (!e || slot < 0 || slot > 1 || count < 0) return fail(e, AZ_ERR_INVALID, "az_search_batch: bad argument");
+    if (count == 0) return AZ_OK;
+    if (!boards || !players || !lasts || !temperatures || !u) return fail(e, AZ_ERR_INVALID, "az_search_batch: null argument");
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_search_batch: a self-play episode is open on this engine");
+    // every position is checked on the host before any GPU work: an error leaves every output untouched
+    for (int i = 0; i < count; i++) {
+        char who[48];
+        snprintf(who, sizeof who, "az_search_batch: position %d", i);
+        if (check_position(e, who, boards + (size_t)i * e->nn, players[i], lasts[i], nullptr)) return AZ_ERR_INVALID;
+    }
+    return preset_search(e, true, slot, count, boards, players, lasts, temperatures, noise, u, pi, actions, visits, W, prior);
+}
+
+// one position: a batch of one on lane 0.  The single noise row, temperature and u address the same values as the tapes of a
+// one-game episode would, so the search is the one az_search_batch makes of the position, bit for bit.
+static int search_one(az_engine *e, int slot, const uint8_t *board, int player, int last, int stones, double temperature,
+                      const double *noise, double u, float *pi, int32_t *action, int32_t *visits, double *W, float *prior)
+{
+    const uint8_t pl = (uint8_t)player;
+    const int16_t la = (int16_t)std::max(last, (int)INT16_MIN);     // the kernels tell negative values apart (the symmetry hash)
+    std::vector<double> row;                                        // one entry per legal cell -> the [n*n] row of the batch
+    if (noise) { row.assign(e->nn, 0.0); memcpy(row.data(), noise, (size_t)(e->nn - stones) * 8); }
+    return preset_search(e, false, slot, 1, board, &pl, &la, &temperature, noise ? row.data() : nullptr, &u, pi, action, visits, W, prior);
+}
+
+extern "C" int az_search(az_engine *e, int slot, const uint8_t *board, int player, int last, double temperature,
+                         const double *noise, double u, float *pi, int32_t *action, int32_t *visits, double *W,
+                         float *prior)
+{
+    if (!e || !board || (player != 1 && player != 2) || slot < 0 || slot > 1) return fail(e, AZ_ERR_INVALID, "az_search: bad argument");
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_search: a self-play episode is open on this engine");
+    int stones = 0;
+    if (check_position(e, "az_search", board, player, last, &stones)) return AZ_ERR_INVALID;
+    return search_one(e, slot, board, player, last, stones, temperature, noise, u, pi, action, visits, W, prior);
 }
 
 // ---- start positions: later self-play and arena games continue these instead of beginning on the empty board ----
@@ -2706,12 +2716,7 @@ extern "C" int az_set_subtree_reuse(az_engine *e, int on)
 {
     if (!e) return AZ_ERR_INVALID;
     if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_subtree_reuse: an episode is open");
-    if (on && e->vl > 1) return fail(e, AZ_ERR_INVALID, "subtree reuse and virtual-loss batching cannot be combined");
-    if (on && e->ext.on) return fail(e, AZ_ERR_INVALID, "subtree reuse and the external evaluator cannot be combined");
-    if (on && e->cap_fast) return fail(e, AZ_ERR_INVALID, "the playout cap and subtree reuse cannot be combined");
-    if (on && e->forced_k > 0.0) return fail(e, AZ_ERR_INVALID, "forced playouts and subtree reuse cannot be combined");
-    if (on && e->gumbel_m > 0) return fail(e, AZ_ERR_INVALID, "the Gumbel root search and subtree reuse cannot be combined");
-    if (on && e->solver) return fail(e, AZ_ERR_INVALID, "the solver and subtree reuse cannot be combined");
+    if (on && refuse_conflicts(e, SET_REUSE)) return AZ_ERR_INVALID;
     if (on && e->R > REUSE_MAX_ROWS)
         return fail(e, AZ_ERR_INVALID, "subtree reuse supports at most %d simulations per move", REUSE_MAX_ROWS - 1);
     e->reuse = on ? 1 : 0;
@@ -2739,14 +2744,10 @@ extern "C" int az_set_virtual_loss(az_engine *e, int leaves)
     if (!e) return AZ_ERR_INVALID;
     if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_virtual_loss: an episode is open");
     if (leaves < 1 || leaves > VL_MAX) return fail(e, AZ_ERR_INVALID, "virtual-loss batching supports 1..%d leaves per batch", VL_MAX);
-    if (leaves > 1 && e->reuse) return fail(e, AZ_ERR_INVALID, "subtree reuse and virtual-loss batching cannot be combined");
-    {
-        const char *f = getenv("AZ_VL_FORCE");
-        if (e->gumbel_m > 0 && (leaves > 1 || (f && f[0] == '1')))
-            return fail(e, AZ_ERR_INVALID, "the Gumbel root search and virtual-loss batching cannot be combined");
-        if (e->solver && (leaves > 1 || (f && f[0] == '1')))
-            return fail(e, AZ_ERR_INVALID, "the solver and virtual-loss batching cannot be combined");
-    }
+    const char *f = getenv("AZ_VL_FORCE");       // AZ_VL_FORCE=1: the batched kernel also for batches of one (must equal k_step)
+    const bool vl_kernel = leaves > 1 || (f && f[0] == '1');
+    if (leaves > 1 && refuse_conflicts(e, SET_VL)) return AZ_ERR_INVALID;
+    if (vl_kernel && refuse_conflicts(e, SET_VL_KERNEL)) return AZ_ERR_INVALID;
     DEVICE_GUARD(e);
     // deep search (S > DEFAULT_MAX_S) with batches: the in-flight counts live beside the tree, one byte per edge
     const bool need_inflight = e->deep && e->cfg.num_simulations > DEFAULT_MAX_S && leaves > 1;
@@ -2775,8 +2776,7 @@ extern "C" int az_set_virtual_loss(az_engine *e, int leaves)
         HIPCHECK(e, hipStreamSynchronize(e->stream));
     }
     e->vl = leaves;
-    const char *f = getenv("AZ_VL_FORCE");       // AZ_VL_FORCE=1: the batched kernel also for batches of one (must equal k_step)
-    e->vl_kernel = leaves > 1 || (f && f[0] == '1');
+    e->vl_kernel = vl_kernel;
     each_state(e, [&](DevState &d) { (void)d; });        // refresh the item views
     return AZ_OK;
 }
@@ -2809,8 +2809,7 @@ extern "C" int az_set_leaf_symmetry(az_engine *e, int on)
 {
     if (!e) return AZ_ERR_INVALID;
     if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_leaf_symmetry: an episode is open");
-    if (on && e->cfg.eval_kind != AZ_EVAL_NET) return fail(e, AZ_ERR_INVALID, "random-symmetry leaf evaluation needs the net evaluator");
-    if (on && e->ext.on) return fail(e, AZ_ERR_INVALID, "random-symmetry leaf evaluation and the external evaluator cannot be combined");
+    if (on && refuse_conflicts(e, SET_SYMMETRY)) return AZ_ERR_INVALID;
     e->leaf_symmetry = on ? 1 : 0;
     for (Lane &L : e->lanes) L.d.leaf_sym = on ? (int *)L.leaf_sym.p : nullptr;
     each_state(e, [&](DevState &d) { (void)d; });        // refresh the item views
@@ -2868,11 +2867,7 @@ extern "C" int az_set_external_evaluator(az_engine *e, const az_ext_evaluator *e
     if (!ev->planes_dev || !ev->policy_dev || !ev->value_dev || !ev->fn)
         return fail(e, AZ_ERR_INVALID, "az_set_external_evaluator: null buffer or callback");
     if ((uintptr_t)ev->planes_dev & 15u) return fail(e, AZ_ERR_INVALID, "az_set_external_evaluator: planes_dev must be 16-byte aligned");
-    if (e->reuse) return fail(e, AZ_ERR_INVALID, "subtree reuse and the external evaluator cannot be combined");
-    if (e->cap_fast) return fail(e, AZ_ERR_INVALID, "the playout cap and the external evaluator cannot be combined");
-    if (e->leaf_symmetry) return fail(e, AZ_ERR_INVALID, "random-symmetry leaf evaluation and the external evaluator cannot be combined");
-    if (e->gumbel_m > 0) return fail(e, AZ_ERR_INVALID, "the Gumbel root search and the external evaluator cannot be combined (it returns priors, not logits)");
-    if (e->solver) return fail(e, AZ_ERR_INVALID, "the solver and the external evaluator cannot be combined");
+    if (refuse_conflicts(e, SET_EXT)) return AZ_ERR_INVALID;
     if (ev->capacity < e->cfg.slots * e->vl)
         return fail(e, AZ_ERR_INVALID, "az_set_external_evaluator: capacity %d is below az_ext_capacity = %d slots x %d leaves per batch",
                     ev->capacity, e->cfg.slots, e->vl);
@@ -2890,9 +2885,42 @@ extern "C" int az_ext_stats(const az_engine *e, int64_t *requests, int64_t *item
 }
 
 // MCTS.run with the evaluator outside the engine: the policy_value_fn seam of mcts.py:87-93 for evaluators that are not
-// this engine's net (any callable in the reference).  The tree kernels run on the GPU as always; each of the
-// num_simulations + 1 evaluations crosses to the host: the pending leaf is read back, the callback fills priors and
-// value, they are uploaded, and the tree step consumes them as they are (no softmax, no value head).
+// this engine's net (any callable in the reference).  The search is az_search's with an external evaluator of the engine's
+// own (ext_plies): each of the num_simulations + 1 evaluations is a request of one entry, whose planes callback_eval reads
+// back and decodes for the callback and whose priors and value it uploads, and the tree step consumes them as they are
+// (no softmax, no value head).
+struct CallbackEval {
+    az_engine *e; az_eval_callback fn; void *user;
+    int player, stones;            // of the searched position: the side to move at a leaf follows from the leaf's stone count
+    int status = 0;                // what the callback returned, if not 0
+    hipError_t hip = hipSuccess;   // ... or the copy that failed
+    std::vector<float> planes, policy;
+    std::vector<uint8_t> cells;
+};
+static int callback_eval(void *user, int /*net*/, int count)
+{
+    CallbackEval &c = *(CallbackEval *)user;
+    az_engine *e = c.e;
+    const int nn = e->nn;
+    if (count != 1) return -1;     // one position, one leaf per batch
+    std::vector<float> &planes = c.planes, &policy = c.policy;
+    std::vector<uint8_t> &cells = c.cells;
+    planes.resize((size_t)3 * nn); policy.assign((size_t)nn, 0.0f); cells.resize((size_t)nn);
+    if ((c.hip = az_memcpy(e->stream, planes.data(), e->cb_planes.p, planes.size() * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess) return -1;
+    int stones = 0, last = -1;
+    for (int j = 0; j < nn; j++) stones += planes[j] != 0.0f || planes[nn + j] != 0.0f;
+    const int mover = ((stones - c.stones) & 1) ? 3 - c.player : c.player;
+    for (int j = 0; j < nn; j++) {
+        cells[j] = (uint8_t)(planes[j] != 0.0f ? mover : (planes[nn + j] != 0.0f ? 3 - mover : 0));
+        if (planes[2 * nn + j] != 0.0f) last = j;
+    }
+    float value = 0.0f;
+    if ((c.status = c.fn(c.user, cells.data(), mover, last, policy.data(), &value))) return c.status;
+    c.hip = az_memcpy(e->stream, e->cb_policy.p, policy.data(), policy.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (c.hip == hipSuccess) c.hip = az_memcpy(e->stream, e->cb_value.p, &value, sizeof value, hipMemcpyHostToDevice);
+    return c.hip == hipSuccess ? 0 : -1;
+}
+
 extern "C" int az_search_callback(az_engine *e, const uint8_t *board, int player, int last, double temperature,
                                   const double *noise, double u, az_eval_callback fn, void *user, float *pi, int32_t *action,
                                   int32_t *visits, double *W, float *prior)
@@ -2904,112 +2932,32 @@ extern "C" int az_search_callback(az_engine *e, const uint8_t *board, int player
     if (e->solver) return fail(e, AZ_ERR_INVALID, "az_search_callback: not combinable with the solver");
     if (noise && e->gumbel_m > 0)
         return fail(e, AZ_ERR_INVALID, "az_search_callback: a noised search under the Gumbel root search needs logits, the callback returns priors");
-    DEVICE_GUARD(e);
-    const int nn = e->nn, S = e->cfg.num_simulations;
     int stones = 0;
-    for (int j = 0; j < nn; j++) {
-        if (board[j] > 2) return fail(e, AZ_ERR_INVALID, "az_search_callback: cell value %d", board[j]);
-        stones += board[j] != 0;
-    }
-    if (stones >= nn) return fail(e, AZ_ERR_INVALID, "az_search_callback: no legal action");
-    if (last >= nn || (last >= 0 && board[last] == 0)) return fail(e, AZ_ERR_INVALID, "az_search_callback: bad last action");
-    int rc = ensure_episode_buffers(e, 1, true);
+    if (check_position(e, "az_search_callback", board, player, last, &stones)) return AZ_ERR_INVALID;
+    DEVICE_GUARD(e);
+    const size_t cap = (size_t)e->cfg.slots * e->vl, nn = (size_t)e->nn;
+    int rc = dev_alloc(e, e->cb_planes, cap * 4 * nn * sizeof(float), false);
+    if (!rc) rc = dev_alloc(e, e->cb_policy, cap * nn * sizeof(float), false);
+    if (!rc) rc = dev_alloc(e, e->cb_value, cap * sizeof(float), false);
     if (rc) return rc;
-    std::vector<double> T(nn + 1, temperature);
-    if ((rc = upload_T(e, T.data(), false))) return rc;
-    std::vector<double> hn((size_t)e->tape_len, 0.0), hu(nn, u);
-    int off = 0;
-    for (int m = 0; m < stones; m++) off += nn - m;
-    if (noise) memcpy(hn.data() + off, noise, (size_t)(nn - stones) * 8);
-    HIPCHECK(e, az_memcpy(e->stream, e->noise.p, hn.data(), hn.size() * 8, hipMemcpyHostToDevice));
-    HIPCHECK(e, az_memcpy(e->stream, e->u.p, hu.data(), hu.size() * 8, hipMemcpyHostToDevice));
-    u64 bd[8];
-    planes_from_cells(board, nn, bd, bd + 4);
-    Lane &L = e->lanes[0];
-    HIPCHECK(e, hipMemsetAsync(L.s_status.p, 0, L.s_status.bytes, e->stream));
-    HIPCHECK(e, hipMemcpyAsync(L.board.p, bd, sizeof bd, hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(k_set_position, dim3(1), dim3(64), 0, e->stream, L.d, 0, 0, player, last, stones);
-    HIPCHECK(e, hipStreamSynchronize(e->stream));
-    // the episode machinery is bypassed: this loop is the episode (one game, one ply), driven step by step from the host
-    const bool had_cache = e->cache.p != nullptr;
-    HIPCHECK(e, hipMemsetAsync(L.cnt.p, 0, L.cnt.bytes, e->stream));
-    HIPCHECK(e, hipMemsetAsync(L.carried.p, 0xFF, L.carried.bytes, e->stream));
-    // from here on the lane states say "priors come from outside": put them back on EVERY way out (the guard below),
-    // or a later az_selfplay / az_arena would feed raw logits to the tree step as priors
-    each_state(e, [&](DevState &d) {
-        d.max_plies = 0; d.add_noise = noise ? 1 : 0; d.arena = 0; d.total_games = 1; d.reuse = 0; d.game_key0 = 0;
-        d.cache = nullptr; d.ext_eval = 1; d.cap_fast = 0; d.cap_permille = 0;
-        d.forced_k = noise ? e->forced_k : 0.0; d.forced_prune = d.forced_k > 0.0 ? e->forced_prune : 0;
-        d.gumbel_m = 0; d.gumbel_cv = 0.0; d.gumbel_cs = 0.0;       // refused above with noise; without noise there is no Gumbel root
-    });
+    // The engine's own evaluator stands in for the public one (written directly: az_set_external_evaluator's refusals are
+    // about the public setting) while the position is searched like any other.  What a search call reports afterwards --
+    // the public evaluator and its statistics, the counters, the solver's stops -- goes back as found on every way out.
     struct Restore {
-        az_engine *e; bool had_cache;
-        ~Restore() { each_state(e, [&](DevState &d) { d.ext_eval = 0; d.cache = had_cache ? (float *)e->cache.p : nullptr; }); }
-    } restore{e, had_cache};
-    e->persist_gp = 0;
-    LaunchCtx lc = ctx_of_impl(e, L);
-    lc.synthetic = 0;
-    hipLaunchKernelGGL(k_begin, dim3((L.d.B + 255) / 256), dim3(256), 0, e->stream, L.d);
-    std::vector<float> pol(e->RW, 0.0f), hid(64, 0.0f);
-    std::vector<uint8_t> cells(nn);
-    int cbrc = 0;
-    for (int idx = 0; idx <= S && !rc; idx++) {
-        int kind = LEAF_NONE, depth = 0, llast = -1;
-        u64 lf[8];
-        hipError_t hr = az_memcpy(e->stream, &kind, L.leaf_kind.p, 4, hipMemcpyDeviceToHost);
-        if (hr == hipSuccess && leaf_needs_net(kind)) {
-            hr = az_memcpy(e->stream, lf, L.leaf.p, sizeof lf, hipMemcpyDeviceToHost);
-            if (hr == hipSuccess) hr = az_memcpy(e->stream, &depth, L.depth.p, 4, hipMemcpyDeviceToHost);
-            if (hr == hipSuccess) hr = az_memcpy(e->stream, &llast, L.leaf_last.p, 4, hipMemcpyDeviceToHost);
-            if (hr == hipSuccess) {
-                const int mover = (depth & 1) ? 3 - player : player;     // side to move at the leaf
-                for (int j = 0; j < nn; j++) {
-                    const bool me = (lf[j >> 6] >> (j & 63)) & 1ull, op = (lf[4 + (j >> 6)] >> (j & 63)) & 1ull;
-                    cells[j] = (uint8_t)(me ? mover : (op ? 3 - mover : 0));
-                }
-                float value = 0.0f;
-                std::fill(pol.begin(), pol.end(), 0.0f);
-                cbrc = fn(user, cells.data(), mover, llast, pol.data(), &value);
-                if (cbrc) { rc = fail(e, AZ_ERR_INVALID, "az_search_callback: the evaluator returned %d", cbrc); break; }
-                hid[0] = value;
-                hr = az_memcpy(e->stream, L.logits.p, pol.data(), (size_t)e->RW * 4, hipMemcpyHostToDevice);
-                if (hr == hipSuccess) hr = az_memcpy(e->stream, L.vhid.p, hid.data(), 64 * 4, hipMemcpyHostToDevice);
-            }
+        az_engine *e; bool on; az_ext_evaluator ev; int64_t requests, items, stops; az_counters last;
+        ~Restore()
+        {
+            e->ext.on = on; e->ext.ev = ev; e->ext.requests = requests; e->ext.items = items;
+            e->solver_stops = stops; e->last = last; e->have_episode = false;
         }
-        if (hr != hipSuccess) { rc = fail(e, AZ_ERR_HIP, "az_search_callback: %s", hipGetErrorString(hr)); break; }
-        e->ops->step(lc, idx, idx < S ? 1 : 0);
-    }
-    if (!rc) {
-        e->ops->move(lc);
-        hipError_t hr = hipStreamSynchronize(e->stream);
-        if (hr == hipSuccess) hr = hipGetLastError();
-        if (hr != hipSuccess) rc = fail(e, AZ_ERR_HIP, "az_search_callback: %s", hipGetErrorString(hr));
-    } else {
-        (void)hipStreamSynchronize(e->stream);
-    }
-    (void)hipMemsetAsync(L.s_status.p, 0, L.s_status.bytes, e->stream);
-    (void)hipMemsetAsync(L.leaf_kind.p, 0, L.leaf_kind.bytes, e->stream);
-    (void)hipStreamSynchronize(e->stream);
-    e->have_episode = false;
-    if (rc) return rc;
-    const size_t ri = (size_t)stones;
-    if (pi) HIPCHECK(e, az_memcpy(e->stream, pi, (float *)e->rec_pi.p + ri * nn, (size_t)nn * 4, hipMemcpyDeviceToHost));
-    if (action) {
-        short a = -1;
-        HIPCHECK(e, az_memcpy(e->stream, &a, (short *)e->rec_action.p + ri, 2, hipMemcpyDeviceToHost));
-        *action = a;
-    }
-    if (visits || W || prior) {
-        std::vector<Edge> row(e->RW);
-        HIPCHECK(e, az_memcpy(e->stream, row.data(), L.edges.p, row.size() * sizeof(Edge), hipMemcpyDeviceToHost));
-        for (int j = 0; j < nn; j++) {
-            const bool legal = board[j] == 0;
-            if (visits) visits[j] = legal ? row[j].N : 0;
-            if (W) W[j] = legal ? row[j].W : 0.0;
-            if (prior) prior[j] = legal ? row[j].P : 0.0f;
-        }
-    }
-    return AZ_OK;
+    } restore{e, e->ext.on, e->ext.ev, e->ext.requests, e->ext.items, e->solver_stops, e->last};
+    CallbackEval ce{e, fn, user, player, stones};
+    e->ext.ev = az_ext_evaluator{(float *)e->cb_planes.p, (float *)e->cb_policy.p, (float *)e->cb_value.p, (int32_t)cap, callback_eval, &ce};
+    e->ext.on = true;
+    rc = search_one(e, 0, board, player, last, stones, temperature, noise, u, pi, action, visits, W, prior);
+    if (ce.status) return fail(e, AZ_ERR_INVALID, "az_search_callback: the evaluator returned %d", ce.status);
+    if (ce.hip != hipSuccess) return fail(e, AZ_ERR_HIP, "az_search_callback: %s", hipGetErrorString(ce.hip));
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------------

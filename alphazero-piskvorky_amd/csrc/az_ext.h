@@ -1,7 +1,7 @@
-// az_ext.h -- the batched external evaluator (az_set_external_evaluator): the pending leaves of every game as one compact
-// batch of encoded positions for an evaluator outside the engine, and its priors and values back into the rows the tree
-// step reads.  Both kernels work over the net kernels' view of a lane (LaunchCtx.dv: B = evaluation items = slots x leaves
-// per batch, s_status / s_net per item).  The lanes of an engine are served one launch after another on one stream, each
+// az_ext.h -- the batched external evaluator (az_set_external_evaluator, and the one az_search_callback installs for its
+// own call): the pending leaves of every game as one compact batch of encoded positions for an evaluator outside the
+// engine, and its priors and values back into the rows the tree step reads.  Both kernels work over the net kernels' view of a lane
+// (LaunchCtx.dv: B = evaluation items = slots x leaves per batch, s_status / s_net per item).  The lanes of an engine are served one launch after another on one stream, each
 // appending to the same request, so a request lists its items in ascending (lane, slot, leaf-of-batch) order.
 #pragma once
 #include "az_tree.h"
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(EXT_GATHER_THREADS) void k_ext_gather(DevState dv, 
 
 // ------------------------------------------------------------------------------------------------
 // k_ext_scatter: one wavefront per request entry; entries of other lanes are skipped.  policy[j][0 .. n*n) becomes the
-// logits row of the entry's item (row stride RW, the tail up to RW zeroed, as az_search_callback uploads it) and value[j]
+// logits row of the entry's item (row stride RW, the tail up to RW zeroed) and value[j]
 // the first entry of its hidden row: where the tree step's ext_eval branch reads priors and value.
 // ------------------------------------------------------------------------------------------------
 template <int N>

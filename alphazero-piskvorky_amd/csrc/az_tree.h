@@ -94,7 +94,7 @@ struct DevState {
     int L;                 // 1 = the reference's sequential simulation loop (mcts.py:123-141)
     int *it_status, *it_net;   // [B*L] per evaluation item, what the net kernels read as s_status / s_net (alias them when L == 1)
     int *leaf_sym;         // [B] opt-in random-symmetry leaf evaluation (az_set_leaf_symmetry): symmetry 0..7 the net sees the pending leaf in; nullptr = off
-    int ext_eval;          // the pending rows were filled by an evaluator outside the engine (az_search_callback): priors and value as given
+    int ext_eval;          // the pending rows were filled by an evaluator outside the engine (az_ext.h): priors and value as given
     unsigned game_key0;    // leaf-symmetry hash key of game id 0 = low 32 bits of the episode's seed0: key(g) = game_key0 + g is the game's
                            // seed, a GLOBAL name of the game that does not depend on which rank / slot / lane plays it
     unsigned key_stride;   // key(g) = game_key0 + key_stride * g.  1 everywhere; 0 in az_search_batch, whose positions all carry
@@ -1722,18 +1722,5 @@ __global__ void k_rules_replay(int n, int k, int games, int max_len, const short
     players[g] = pl;
     results[g] = res;
     status[g] = bad;
-}
-
-// custom start position for az_search: slot 0 gets the given state
-__global__ void k_set_position(DevState d, int slot, int game, int player, int last, int ply)
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    d.s_game[slot] = game;
-    d.s_ply[slot] = ply;
-    d.s_player[slot] = player;
-    d.s_last[slot] = last;
-    d.s_status[slot] = SLOT_ACTIVE;
-    d.leaf_kind[(size_t)slot * d.L] = LEAF_NONE;
-    d.carried[slot] = -1;
 }
 #endif  // AZ_ENGINE_TU

@@ -463,3 +463,69 @@ def test_every_kernel_shape_gives_the_same_episode(n, k, S, cut, model):
         for key in ("actions", "visits", "pis"):
             assert np.array_equal(rec[key][off:off + L], r[key]), f"game {g}: {key}"
         off += L
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# settings that cannot be combined: every pair, whichever is switched on first
+# ---------------------------------------------------------------------------------------------------------------------
+# how each setting is switched on, and how it reads back as off where the API can say (subtree reuse and leaf symmetry have
+# no getter: for them, as for all, the episode after the refusal must be the one before it)
+def _ext_on(e):
+    from tests.test_external_eval_gpu import CpuEvaluator, net_eval
+    CpuEvaluator(e, net_eval(orc.Net(e.n, weights_from_fixture(e.n, "ckpt_saved"))))
+
+
+SETTINGS = {
+    "reuse": (lambda e: e.set_subtree_reuse(True), None),
+    "virtual loss": (lambda e: e.set_virtual_loss(2), lambda e: e.ext_capacity() == 4),
+    "leaf symmetry": (lambda e: e.set_leaf_symmetry(True), None),
+    "external evaluator": (_ext_on, lambda e: not e.external_evaluator()),
+    "playout cap": (lambda e: e.set_playout_cap(4), lambda e: e.playout_cap()["fast_sims"] == 0),
+    "forced playouts": (lambda e: e.set_forced_playouts(2.0), lambda e: e.forced_playouts()["k"] == 0.0),
+    "gumbel": (lambda e: e.set_gumbel(4), lambda e: e.gumbel()["m"] == 0),
+    "solver": (lambda e: e.set_solver(True), lambda e: not e.solver()),
+}
+CONFLICTS = [
+    ("reuse", "virtual loss", "subtree reuse and virtual-loss batching cannot be combined"),
+    ("reuse", "external evaluator", "subtree reuse and the external evaluator cannot be combined"),
+    ("playout cap", "reuse", "the playout cap and subtree reuse cannot be combined"),
+    ("forced playouts", "reuse", "forced playouts and subtree reuse cannot be combined"),
+    ("gumbel", "reuse", "the Gumbel root search and subtree reuse cannot be combined"),
+    ("solver", "reuse", "the solver and subtree reuse cannot be combined"),
+    ("playout cap", "external evaluator", "the playout cap and the external evaluator cannot be combined"),
+    ("leaf symmetry", "external evaluator", "random-symmetry leaf evaluation and the external evaluator cannot be combined"),
+    ("gumbel", "virtual loss", "the Gumbel root search and virtual-loss batching cannot be combined"),
+    ("forced playouts", "gumbel", "forced playouts and the Gumbel root search cannot be combined"),
+    ("gumbel", "external evaluator", "the Gumbel root search and the external evaluator cannot be combined (it returns priors, not logits)"),
+    ("solver", "virtual loss", "the solver and virtual-loss batching cannot be combined"),
+    ("solver", "forced playouts", "the solver and forced playouts cannot be combined"),
+    ("solver", "gumbel", "the solver and the Gumbel root search cannot be combined"),
+    ("solver", "external evaluator", "the solver and the external evaluator cannot be combined"),
+]
+
+
+@pytest.mark.parametrize("a,b,message", CONFLICTS, ids=[f"{a} x {b}" for a, b, _ in CONFLICTS])
+def test_conflicting_settings_are_refused_in_either_order(a, b, message):
+    import re
+    n, k, S = 5, 4, 8
+    sd = weights_from_fixture(n, "ckpt_saved")
+
+    def episode(e):
+        e.selfplay(2, seed0=31, max_plies=2)
+        return e.records(), e.games()
+
+    for first, second in ((a, b), (b, a)):
+        e = _engine(n, k, S)
+        e.load_weights(sd, 0)
+        SETTINGS[first][0](e)
+        before = episode(e)
+        with pytest.raises(az.AzError, match=r"\(-1\).*" + re.escape(message)):
+            SETTINGS[second][0](e)
+        reads_off = SETTINGS[second][1]
+        assert reads_off is None or reads_off(e), f"{first}, then {second}: the refused setting reads back as on"
+        rec, games = episode(e)
+        assert len(rec["actions"]) == 4
+        for key in rec:
+            assert np.array_equal(rec[key], before[0][key]), f"{first}, then {second}: {key} changed with the refused setting"
+        assert np.array_equal(games[0], before[1][0]) and np.array_equal(games[1], before[1][1])
+        e.close()

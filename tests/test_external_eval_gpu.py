@@ -379,6 +379,51 @@ def test_a_failing_evaluator_surfaces_and_the_engine_stays_usable():
     e.close()
 
 
+def test_search_callback_leaves_the_engines_state_alone():
+    """search_callback searches through an evaluator of the engine's own; the public one, its statistics and the counters of
+    the last call are as they were afterwards, whether the callback answered or raised."""
+    n, k, S = 5, 4, 8
+    sd = weights_from_fixture(n, "ckpt_saved")
+    onet, o = orc.Net(n, sd), orc.Oracle(n, k, S)
+    boards = np.zeros((3, n * n), np.uint8)
+    boards[1, [6, 7]] = 1; boards[1, 12] = 2
+    boards[2, [12, 13]] = 1; boards[2, [6, 18]] = 2
+    players, lasts = np.array([1, 2, 1], np.uint8), np.array([-1, 7, 18], np.int16)
+    e = _engine(n, k, S, 4)
+    ev = CpuEvaluator(e, net_eval(onet))
+    e.search_batch(boards, players, lasts, 1.0)
+    stats, counters = e.ext_stats(), e.counters()
+    assert stats["requests"] == len(ev.requests) > 0 and counters["root_evals"] == 3
+
+    def cb(cells, player, last):
+        _, P, v = onet.eval(o.encode(cells, player, last))
+        return P, v
+
+    def gives_up(cells, player, last):
+        raise KeyError("the callback gave up")
+
+    for fn in (cb, gives_up):
+        if fn is cb:
+            r = e.search_callback(boards[1], 2, 7, 1.0, fn)
+            assert int(r["N"].sum()) == S
+        else:
+            with pytest.raises(KeyError, match="gave up"):
+                e.search_callback(boards[1], 2, 7, 1.0, fn)
+        assert e.external_evaluator()
+        assert e.ext_stats() == stats and e.counters() == counters
+        assert len(ev.requests) == stats["requests"], "the public evaluator is not called by search_callback"
+        e.search_batch(boards, players, lasts, 1.0)
+        assert len(ev.requests) == 2 * stats["requests"] and e.ext_stats() == stats, "the public evaluator serves the next search_batch"
+        del ev.requests[stats["requests"]:]
+        counters = e.counters()
+    got =_episode(e, G=2, seed0=5, cut=2)
+    e.close()
+    fresh = _engine(n, k, S, 4)
+    fresh.load_weights(sd, 0)
+    assert _same_episode(got, _episode(fresh, G=2, seed0=5, cut=2))
+    fresh.close()
+
+
 def test_the_evaluation_cache_is_bypassed_and_back_in_force_after_clear():
     n, k, S = 5, 4, 16
     sd = weights_from_fixture(n, "ckpt_saved")

@@ -491,3 +491,73 @@ def test_one_engine_through_the_modes_and_back(monkeypatch, name):
     kept.close()
     _assert_same_episode(episodes[0], episodes[-2], f"{name}: after the reload vs the first episode")
     _assert_same_episode(episodes[0], episodes[-1], f"{name}: last episode vs the first")
+
+
+def _d_positions(n):
+    """three undecided positions: the empty board, three stones, four stones"""
+    boards = np.zeros((3, n * n), np.uint8)
+    boards[1, [n + 1, n + 2]] = 1; boards[1, 2 * n + 2] = 2
+    boards[2, [2 * n + 2, 2 * n + 3]] = 1; boards[2, [n + 1, 3 * n + 3]] = 2
+    players, lasts = np.array([1, 2, 1], np.uint8), np.array([-1, n + 2, 3 * n + 3], np.int16)
+    rs = np.random.RandomState(29)
+    noise = [rs.dirichlet([0.3] * int((b == 0).sum())) for b in boards]
+    return boards, players, lasts, noise, rs.random_sample(3), np.array([1.0, 0.6, 0.05])
+
+
+def _d_searches(e, n):
+    """every search entry point on the fixed positions -> {what: result}"""
+    from tests.ties import levels_of
+    boards, players, lasts, noise, us, Ts = _d_positions(n)
+    lv = np.exp(levels_of("three", n).astype(np.float64))
+    table, v = (lv / lv.sum()).astype(np.float32), float(np.tanh(-0.5))       # the constant evaluator of tests/test_ties_gpu.py
+    out = {}
+    for slot in (0, 1):
+        for i in range(3):
+            out[f"search {i} slot {slot}"] = e.search(boards[i], int(players[i]), int(lasts[i]), Ts[i], noise[i], us[i], slot=slot)
+            out[f"batch of one {i} slot {slot}"] = e.search_batch(boards[i:i + 1], players[i:i + 1], lasts[i:i + 1], Ts[i:i + 1], noise[i:i + 1], us[i:i + 1], slot=slot)
+        out[f"batch of three slot {slot}"] = e.search_batch(boards, players, lasts, Ts, noise, us, slot=slot)
+        out[f"batch of three without noise slot {slot}"] = e.search_batch(boards, players, lasts, Ts, None, us, slot=slot)
+    for i in range(3):
+        out[f"callback {i}"] = e.search_callback(boards[i], int(players[i]), int(lasts[i]), Ts[i], lambda cells, pl, la: (table, v), noise[i], us[i])
+        out[f"callback {i} without noise"] = e.search_callback(boards[i], int(players[i]), int(lasts[i]), Ts[i], lambda cells, pl, la: (table, v), None, us[i])
+    return out
+
+
+def test_searches_on_a_used_engine_equal_a_fresh_engine(monkeypatch):
+    """Every search entry point sets the whole lane state for itself: after resignation, start positions, a playout cap, a
+    self-play episode, an arena and a noised batch search on a two-lane engine, search / search_batch / search_callback give
+    exactly what an engine gives that did none of it.  And search is search_batch with one position."""
+    _clean_env(monkeypatch)
+    n, k, S, slots = 5, 4, 8, 4
+    sd, sd2 = weights_from_fixture(n, "ckpt_saved"), weights_from_fixture(n, "ckpt_0802")
+
+    def engine():
+        e = az.Engine(n, k, S, slots, engines=2, log_table=orc.numpy_log_table(S))
+        assert e.lanes() == 2
+        e.load_weights(sd, 0); e.load_weights(sd2, 1)
+        return e
+
+    boards, players, lasts, noise, us, Ts = _d_positions(n)
+    used = engine()
+    used.set_resign(0.05, min_ply=1)
+    used.set_start_positions(boards[1:], players[1:], lasts[1:])
+    used.set_playout_cap(3, full=0.5)
+    c = used.selfplay(5, seed0=88, max_plies=7)
+    assert c["plies"] > 0
+    assert used.arena(4, seed0=88, temperature_table=orc.arena_T_table(n * n))["total"] == 4
+    used.search_batch(boards, players, lasts, Ts, noise, us)
+    got = _d_searches(used, n)
+    used.close()
+    fresh = engine()
+    want = _d_searches(fresh, n)
+    fresh.close()
+    for what, w in want.items():
+        for key in ("action", "pi", "N", "W", "P"):
+            assert np.array_equal(got[what][key], w[key]), f"{what}: {key}: used engine vs fresh engine"
+    for slot in (0, 1):
+        for i in range(3):
+            one, batch = want[f"search {i} slot {slot}"], want[f"batch of one {i} slot {slot}"]
+            for key in ("pi", "N", "W", "P"):
+                assert np.array_equal(one[key], batch[key][0]), f"search vs search_batch of one: position {i}, slot {slot}: {key}"
+            assert one["action"] == int(batch["action"][0])
+            assert int(one["N"].sum()) == S
