@@ -33,7 +33,7 @@ struct DevBuf {
 
 struct PackedNet {
     bool loaded = false;
-    DevBuf c1, c2, c3, hd, pf, vf, c1b, c2b, c3b, hdb, pfb, vfb, v2w, v2b;
+    DevBuf c1, c2, c3, hd, hdq, pf, vf, c1b, c2b, c3b, hdb, pfb, vfb, v2w, v2b;
     DevBuf rblk[6], rblkb[6];          // ResidualBlock variant: the six 64->64 convs (c1/c1b hold the stem)
     DevBuf c1x[2], c2x[2], c3x[2], hdx[2];     // the convs (c1x: conv1 / stem) and head convs split into 16-bit MFMA fragments (az_net_emul.h): [0] bf16x3, [1] f16x2
     DevBuf rblkx[2][6];                // ... and the six 64 -> 64 convs of the ResidualBlock variant
@@ -463,6 +463,16 @@ static std::vector<float> pack_heads(const float *pw, int pc, const float *vw, i
         }
     return out;
 }
+static std::vector<float> pack_heads_blocks(const float *pw, const float *vw)
+{
+    // the plain net's policy_conv [4][128] and value_conv [2][128] for the 4-row blocks of v_mfma_f32_4x4x1_16b_f32 (trunk_heads):
+    // [k/4][8 rows][4] -- rows 0-3 policy_conv, 4-5 value_conv, 6-7 zeros; a lane takes four consecutive channels of its row at once
+    std::vector<float> out(32 * 8 * 4, 0.0f);
+    for (int k = 0; k < 128; k++)
+        for (int r = 0; r < 6; r++)
+            out[((size_t)(k / 4) * 8 + r) * 4 + (k % 4)] = r < 4 ? pw[r * 128 + k] : vw[(r - 4) * 128 + k];
+    return out;
+}
 static std::vector<float> pack_fc(const float *w, int nout, int kin)
 {
     // torch Linear [out][in]; tile t covers outputs 16t..16t+15; k-step s covers k = 4s..4s+3; group = 4 k-steps = 16 inputs.
@@ -888,7 +898,7 @@ extern "C" void az_destroy(az_engine *e)
     for (DevBuf *b : shared) dev_free(*b);
     for (int s = 0; s < 2; s++) {
         PackedNet &p = e->net[s];
-        DevBuf *nb[] = {&p.c1, &p.c2, &p.c3, &p.hd, &p.pf, &p.vf, &p.c1b, &p.c2b, &p.c3b, &p.hdb, &p.pfb, &p.vfb, &p.v2w, &p.v2b, &p.c1x[0], &p.c1x[1], &p.c2x[0], &p.c2x[1], &p.c3x[0], &p.c3x[1], &p.hdx[0], &p.hdx[1]};
+        DevBuf *nb[] = {&p.c1, &p.c2, &p.c3, &p.hd, &p.hdq, &p.pf, &p.vf, &p.c1b, &p.c2b, &p.c3b, &p.hdb, &p.pfb, &p.vfb, &p.v2w, &p.v2b, &p.c1x[0], &p.c1x[1], &p.c2x[0], &p.c2x[1], &p.c3x[0], &p.c3x[1], &p.hdx[0], &p.hdx[1]};
         for (DevBuf *b : nb) dev_free(*b);
         for (int i = 0; i < 6; i++) { dev_free(p.rblk[i]); dev_free(p.rblkb[i]); dev_free(p.rblkx[0][i]); dev_free(p.rblkx[1][i]); }
     }
@@ -963,6 +973,7 @@ extern "C" int az_load_weights(az_engine *e, int slot, const float *const *t)
     p.emul_ready[0] = p.emul_ready[1] = false;
     p.f16_ok = in_f16_range(p);
     up(p.hd, pack_heads(t[6], 4, t[10], 2, 128));
+    up(p.hdq, pack_heads_blocks(t[6], t[10]));
     float hb[6] = {t[7][0], t[7][1], t[7][2], t[7][3], t[11][0], t[11][1]};
     upraw(p.hdb, hb, 6);
     up(p.pf, pack_fc(t[8], nn, 4 * nn));  upraw(p.pfb, t[9], nn);
@@ -970,7 +981,7 @@ extern "C" int az_load_weights(az_engine *e, int slot, const float *const *t)
     upraw(p.v2w, t[14], 64); upraw(p.v2b, t[15], 1);
     if (rc) return rc;
     p.w.c1 = (const float *)p.c1.p; p.w.c2 = (const float *)p.c2.p; p.w.c3 = (const float *)p.c3.p;
-    p.w.hd = (const float *)p.hd.p; p.w.pf = (const float *)p.pf.p; p.w.vf = (const float *)p.vf.p;
+    p.w.hd = (const float *)p.hd.p; p.w.hdq = (const float *)p.hdq.p; p.w.pf = (const float *)p.pf.p; p.w.vf = (const float *)p.vf.p;
     p.w.c1b = (const float *)p.c1b.p; p.w.c2b = (const float *)p.c2b.p; p.w.c3b = (const float *)p.c3b.p;
     p.w.hdb = (const float *)p.hdb.p; p.w.pfb = (const float *)p.pfb.p; p.w.vfb = (const float *)p.vfb.p;
     e->cache_gen++;           // evaluations cached under the previous weights never match again

@@ -29,6 +29,7 @@
 struct NetWeights {
     // MFMA-fragment packed (see pack_* in az_engine.hip): [ntile][kstep/4][lane][4]
     const float *c1, *c2, *c3, *hd, *pf, *vf;
+    const float *hdq;                                 // the head convs again, in 4-row block order for the fused trunk (pack_heads_blocks): [k/4][8 rows][4]
     const float *c1b, *c2b, *c3b, *hdb, *pfb, *vfb;   // biases (hdb: 4 policy_conv + 2 value_conv)
     const void *c1x[2], *c2x[2], *c3x[2], *hdx[2];    // the convs and head convs split into 16-bit fragments (az_net_emul.h), [0] bf16x3, [1] f16x2
 };
@@ -42,14 +43,20 @@ __host__ __device__ constexpr int fc_chain_groups(int K) { return (((K + 15) / 1
 
 __host__ __device__ constexpr int up16(int x) { return x + ((16 - (x % 32) + 32) % 32); }   // smallest y >= x, y == 16 (mod 32)
 
+// Row stride (floats) of the fused trunk's cell-major conv3 image out3[tile cell][channel]: 128 channels + 4, so that consecutive
+// cells start 4 LDS banks apart and a row stays 16-byte aligned (528 B)
+constexpr int OUT3_CM_STRIDE = 128 + 4;
+
 // Boards per trunk workgroup for an n x n board: as many as fit the LDS budget, at most 4 (so that 1024 games still
 // give >= 256 workgroups).  chan = LDS floats per padded cell (96 plain net: 32+64 channels; 128 ResidualBlock net).
 __host__ __device__ constexpr int trunk_lds_floats(int n, int g, int chan)
 {
     const int cs = up16(g * (n + 2) * (n + 2));
     const int mr = ((g * n * n + 15) / 16) * 16;
-    const int a = chan * cs, b = chan == 96 ? 128 * up16(mr) : 0;     // plain net: the conv3 image overlays the inputs
-    return a > b ? a : b;
+    // plain net: the conv3 images overlay the inputs -- [co][cell] with stride up16(mr) (the emulated trunks) and the fused
+    // trunk's cell-major one, [cell][OUT3_CM_STRIDE]
+    const int a = chan * cs, b = chan == 96 ? 128 * up16(mr) : 0, c = chan == 96 ? OUT3_CM_STRIDE * mr : 0;
+    return a > b ? (a > c ? a : c) : (b > c ? b : c);
 }
 constexpr int TRUNK_LDS_BUDGET = 36500;     // LDS floats the packed images of one trunk workgroup may take (146 KB)
 __host__ __device__ constexpr int pick_boards(int n, int chan, int budget)
@@ -74,9 +81,12 @@ struct NetGeo {
     static constexpr bool BORDER_SKIP = ROWT && G == 1;            // cell tile t is board row t: conv_layer leaves out the taps on the zero rows
     static constexpr int CS = up16(G * PP);                        // channel stride of padded planes (floats), == 16 mod 32
     static constexpr int CS3 = up16(MR);                           // channel stride of the conv3 output image
-    static constexpr int LDSF = (96 * CS > 128 * CS3) ? 96 * CS : 128 * CS3;
+    static constexpr int LDSF = trunk_lds_floats(N, G, 96);       // max(96 CS, 128 CS3, OUT3_CM_STRIDE MR)
     static constexpr int RW = ((nn + 63) / 64) * 64;
     static constexpr int NW = 8;                                   // waves per trunk workgroup
+    static_assert(G == (N >= 12 ? 1 : N >= 8 ? 2 : 4), "the cell-major conv3 image must not change the boards per workgroup");
+    static_assert(LDSF >= 96 * CS && LDSF >= 128 * CS3 && LDSF >= OUT3_CM_STRIDE * MR, "LDS images of the trunk");
+    static_assert(LDSF * 4 + 2 * MR * 2 + 4096 + 64 <= 160 * 1024, "a trunk workgroup stays under the CU's 160 KB of LDS");
     // FC kernel
     static constexpr int PC = 4, VC = 2;                           // policy_conv / value_conv output channels (net.py:46,52)
     static constexpr int NTP = (nn + 15) / 16;                     // policy N-tiles
@@ -132,8 +142,9 @@ __device__ __forceinline__ int pk_index(int ci, int pos)
 }
 enum { CONV_OUT_PACKED = 0, CONV_OUT3 = 1, CONV_OUT_RESIDUAL = 2,    // RESIDUAL: relu(acc + bias + out[same index]) in place
        CONV_OUT3_RESIDUAL = 3,     // relu(acc + bias + res[packed index]) into the [co][cell] tile (the last block of a tile-split ResidualBlock trunk)
-       CONV_OUT3_PK = 4 };         // conv3 of the fused trunk: the output packed by tile cell, float index ((cg*4 + q)*MR + m)*4 + e for channel
-                                   // 16 cg + 4 e + q -- no padding ring (a 1x1 conv reads it), so that the heads' B operands of four k-steps are ONE ds_read_b128
+       CONV_OUT3_CM = 4 };         // conv3 of the fused trunk: the output cell-major, float index m * OUT3_CM_STRIDE + co for tile cell m -- no
+                                   // padding ring (a 1x1 conv reads it); a lane's four channels are ONE ds_write_b128, and four consecutive
+                                   // channels of a cell ONE ds_read_b128 of the heads
 
 // One conv layer on the workgroup's LDS image, computed as D[co][cell] = sum_k W[co][k] * X[k][cell]:
 // the weight fragment is the MFMA A operand (row = output channel), the activation fragment the B operand
@@ -221,7 +232,7 @@ __device__ __forceinline__ void conv_layer(const float *in, float *out, const fl
 #else
 #define AZ_LSTAMP(k) do { } while (0)
 #endif
-    constexpr bool OUT3 = MODE == CONV_OUT3 || MODE == CONV_OUT3_RESIDUAL || MODE == CONV_OUT3_PK;
+    constexpr bool OUT3 = MODE == CONV_OUT3 || MODE == CONV_OUT3_RESIDUAL || MODE == CONV_OUT3_CM;
     constexpr bool SUBSET = MTL < G::MT;                       // a tile-split kernel: waves without a tile skip the layer
     constexpr int NG = COUT / 16;                              // channel tiles
     constexpr int MG = (G::NW / NG) > 0 ? (G::NW / NG) : 1;    // cell-tile groups
@@ -370,15 +381,20 @@ __device__ __forceinline__ void conv_layer(const float *in, float *out, const fl
             const int m = (mt_base + mt) * 16 + r16;
             const bool valid = cellof[m] != 0xFFFFu;
             const int pos = (int)wpos[m] + out_pos_off;
+            if constexpr (MODE == CONV_OUT3_CM) {
+                // the lane's registers are channels 16 ng + 4 q + 0..3 of cell m: 16 contiguous bytes of the cell's row
+                float4 v4;
+                v4.x = acc[i][0] + bco[0]; v4.y = acc[i][1] + bco[1]; v4.z = acc[i][2] + bco[2]; v4.w = acc[i][3] + bco[3];
+                v4.x = v4.x > 0.0f ? v4.x : 0.0f; v4.y = v4.y > 0.0f ? v4.y : 0.0f;
+                v4.z = v4.z > 0.0f ? v4.z : 0.0f; v4.w = v4.w > 0.0f ? v4.w : 0.0f;
+                *reinterpret_cast<float4 *>(out + m * OUT3_CM_STRIDE + ng * 16 + q * 4) = v4;
+            } else
 #pragma unroll
             for (int rg = 0; rg < 4; rg++) {
                 const int co = ng * 16 + q * 4 + rg;      // = 16*cg + 4*e + q' with cg = ng, e = q, q' = rg
                 float v = acc[i][rg] + bco[rg];
                 v = v > 0.0f ? v : 0.0f;
-                if constexpr (MODE == CONV_OUT3_PK) {
-                    // co = 16 ng + 4 q + rg  ->  plane (ng, rg), component q: the 64 lanes of a store cover 256 contiguous bytes
-                    out[(((ng * 4 + rg) * G::MR + m) << 2) + q] = v;
-                } else if constexpr (MODE == CONV_OUT3_RESIDUAL) {
+                if constexpr (MODE == CONV_OUT3_RESIDUAL) {
                     float r = acc[i][rg] + bco[rg] + (valid ? res[pk_index<GO>(co, pos)] : 0.0f);
                     out[co * O3S + mt * 16 + r16 + (SUBSET ? 0 : mt_base * 16)] = r > 0.0f ? r : 0.0f;
                 } else if constexpr (OUT3) out[co * O3S + mt * 16 + r16 + (SUBSET ? 0 : mt_base * 16)] = v;
@@ -402,56 +418,48 @@ __device__ __forceinline__ void conv_layer(const float *in, float *out, const fl
     else body(std::integral_constant<int, MT_FULL>{}, any_group{});
 }
 
-// policy_conv (128->4) and value_conv (128->2), 1x1 (net.py:64,69): D[head channel][cell] over the float32 conv3 image
-// [co][cell] (stride CS3) in LDS, 32 k-steps on the f32 MFMA; relu(acc + bias) -> feature rows in HBM.
+// policy_conv (128->4) and value_conv (128->2), 1x1 (net.py:64,69) of the fused trunk, on v_mfma_f32_4x4x1_16b_f32: 16 independent
+// 4x4 outer products (blocks) with K = 1.  Block b of a wave is lanes 4b .. 4b + 3: its channel half is b & 1 (head rows 0-3
+// policy_conv, 4-5 value_conv, 6-7 zero weights) and its cell quad b >> 1, so one instruction adds ONE input channel to 8 head
+// rows x 32 tile cells, and wave w owns tile cells 32 w .. 32 w + 31.  Lane 4b + i supplies A = the weight of head row
+// 4 (b & 1) + i, lane 4b + j supplies B = out3[cell 4 (b >> 1) + j][k], and register i of lane 4b + j receives head row
+// 4 (b & 1) + i of that cell.  k runs 0..127 in program order on one accumulator from +0: the chain the 16x16x4 tiles computed
+// (16 s4 + 4 e + q ascending), bit for bit.  hdq_lds: the block-ordered weights (NetWeights::hdq) staged in LDS by the prologue;
+// out3: the cell-major conv3 image (CONV_OUT3_CM).  One ds_read_b128 of each feeds four MFMAs.
 template <class G>
 __device__ __forceinline__ void trunk_heads(const DevState &d, const NetWeights &w, int net_id, float *__restrict__ feat,
-                                            const float *lds, const unsigned short *cellof, int b0, int wave, int lane)
+                                            const float *out3, const float *hdq_lds, const unsigned short *cellof, int b0, int wave, int lane)
 {
-    const int q = lane >> 4, r16 = lane & 15;
-    const float4 *wp4 = reinterpret_cast<const float4 *>(w.hd) + lane;
+    static_assert(G::MR <= G::NW * 32, "one group of 32 tile cells per wave");
+    static_assert(G::NW * 64 * 2 == 32 * 8 * 4, "trunk_group stages the block-ordered head weights with one float2 per thread");
+    const int half = (lane >> 2) & 1;
+    const int m = wave * 32 + (lane >> 3) * 4 + (lane & 3);        // the lane's tile cell; past the image: cell 0 again, computed and dropped
     float hb[4];
 #pragma unroll
-    for (int rg = 0; rg < 4; rg++) hb[rg] = (q * 4 + rg) < 6 ? w.hdb[q * 4 + rg] : 0.0f;
-    constexpr int HT = (G::MT + G::NW - 1) / G::NW;     // tiles per wave
-    f32x4 acc[HT];
-    // the conv3 image is packed by tile cell (CONV_OUT3_PK): lane (q, r16) reads the float4 of plane (s4, q) at its cell -- the B
-    // operands of k-steps 4 s4 .. 4 s4 + 3 (channels 16 s4 + 4 e + q)
-    const float4 *ip[HT];
+    for (int i = 0; i < 4; i++) hb[i] = (half * 4 + i) < 6 ? w.hdb[half * 4 + i] : 0.0f;
+    const float4 *ap = reinterpret_cast<const float4 *>(hdq_lds) + (lane & 7);
+    const float4 *bp = reinterpret_cast<const float4 *>(out3 + (m < G::MR ? m : 0) * OUT3_CM_STRIDE);
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int i = 0; i < HT; i++) {
-        const int mt = wave + G::NW * i;
-        acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        ip[i] = reinterpret_cast<const float4 *>(lds) + q * G::MR + (mt < G::MT ? mt : 0) * 16 + r16;
+    for (int k4 = 0; k4 < 32; k4++) {
+        const float4 a = ap[k4 * 8], b = bp[k4];
+        acc = __builtin_amdgcn_mfma_f32_4x4x1f32(a.x, b.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_4x4x1f32(a.y, b.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_4x4x1f32(a.z, b.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_4x4x1f32(a.w, b.w, acc, 0, 0, 0);
     }
+    if (m < G::MR) {
+        const int cell = cellof[m];
+        if (cell != 0xFFFF) {
+            const int g = cell / G::nn, p = cell - g * G::nn;
+            const int b = b0 + g;
+            if (b < d.B && d.s_net[b] == net_id) {
 #pragma unroll
-    for (int s4 = 0; s4 < 8; s4++) {
-        const float4 bq = wp4[s4 * 64];
-        const float be[4] = {bq.x, bq.y, bq.z, bq.w};
-        float4 av[HT];
-#pragma unroll
-        for (int i = 0; i < HT; i++) av[i] = ip[i][s4 * 4 * G::MR];
-#pragma unroll
-        for (int e = 0; e < 4; e++)
-#pragma unroll
-            for (int i = 0; i < HT; i++) acc[i] = mfma4(be[e], e == 0 ? av[i].x : e == 1 ? av[i].y : e == 2 ? av[i].z : av[i].w, acc[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < HT; i++) {
-        const int mt = wave + G::NW * i;
-        if (mt < G::MT) {
-            const int cell = cellof[mt * 16 + r16];
-            if (cell != 0xFFFF) {
-                const int g = cell / G::nn, p = cell - g * G::nn;
-                const int b = b0 + g;
-                if (b < d.B && d.s_net[b] == net_id) {
-#pragma unroll
-                    for (int rg = 0; rg < 4; rg++) {
-                        const int j = q * 4 + rg;     // head channel: 0-3 policy_conv, 4-5 value_conv (net.py:64,69 flatten order)
-                        if (j < 6) {
-                            float v = acc[i][rg] + hb[rg];
-                            feat[(size_t)b * G::FROW + j * G::nn + p] = v > 0.0f ? v : 0.0f;
-                        }
+                for (int i = 0; i < 4; i++) {
+                    const int j = half * 4 + i;       // head channel: 0-3 policy_conv, 4-5 value_conv (net.py:64,69 flatten order)
+                    if (j < 6) {
+                        float v = acc[i] + hb[i];
+                        feat[(size_t)b * G::FROW + j * G::nn + p] = v > 0.0f ? v : 0.0f;
                     }
                 }
             }
@@ -462,7 +470,7 @@ __device__ __forceinline__ void trunk_heads(const DevState &d, const NetWeights 
 // The work of one board group: one k_trunk workgroup (several groups per workgroup measured the same).
 template <int N>
 __device__ __forceinline__ void trunk_group(const DevState &d, const NetWeights &w, int net_id, float *__restrict__ feat,
-                                                      unsigned long long *dbg, int grp, float *lds, unsigned short *wpos,
+                                                      unsigned long long *dbg, int grp, float *lds, float *hdq_lds, unsigned short *wpos,
                                                       unsigned short *cellof, int *any_active_p, int tid)
 {
     typedef NetGeo<N> G;
@@ -471,6 +479,9 @@ __device__ __forceinline__ void trunk_group(const DevState &d, const NetWeights 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b0 = grp * G::G;
     AZ_STAMP(0);
+    // the head weights in block order (4 KB, 8 bytes per thread): asked for first of all, so that they arrive with the leaf words
+    // requested below, and put into LDS in front of the zero fill; read by trunk_heads only
+    const float2 hq = reinterpret_cast<const float2 *>(w.hdq)[tid];
     if (tid == 0) any_active = 0;
     __syncthreads();
     if (tid < G::G) {
@@ -520,6 +531,7 @@ __device__ __forceinline__ void trunk_group(const DevState &d, const NetWeights 
             }
         }
     }
+    reinterpret_cast<float2 *>(hdq_lds)[tid] = hq;       // in front of the zero fill, whose writes cover this one's latency
     {
         float4 *z = reinterpret_cast<float4 *>(lds);
         for (int i = tid; i < (96 * G::CS) / 4; i += G::NW * 64) z[i] = float4{0.f, 0.f, 0.f, 0.f};
@@ -549,10 +561,10 @@ __device__ __forceinline__ void trunk_group(const DevState &d, const NetWeights 
 #else
     unsigned long long *lst3 = nullptr;
 #endif
-    conv_layer<G, 64, 128, CONV_OUT3_PK>(inB, lds, w.c3, w.c3b, wpos, cellof, wave, lane, 0, G::MT, 0, nullptr, lst3);
+    conv_layer<G, 64, 128, CONV_OUT3_CM>(inB, lds, w.c3, w.c3b, wpos, cellof, wave, lane, 0, G::MT, 0, nullptr, lst3);
     __syncthreads();
     AZ_STAMP(4);
-    trunk_heads<G>(d, w, net_id, feat, lds, cellof, b0, wave, lane);
+    trunk_heads<G>(d, w, net_id, feat, lds, hdq_lds, cellof, b0, wave, lane);
     AZ_STAMP(5);
 }
 
@@ -562,6 +574,7 @@ __global__ __launch_bounds__(NetGeo<N>::NW * 64) void k_trunk(DevState d, NetWei
 {
     typedef NetGeo<N> G;
     __shared__ __attribute__((aligned(16))) float lds[G::LDSF];
+    __shared__ __attribute__((aligned(16))) float hdq_lds[1024];     // head-conv weights in block order, [k/4][8 rows][4]
     __shared__ unsigned short wpos[G::MR];     // centre position of tile cell m in the padded image
     __shared__ unsigned short cellof[G::MR];   // g*nn + cell index, 0xFFFF for a junk lane
     __shared__ int any_active;
@@ -574,7 +587,7 @@ __global__ __launch_bounds__(NetGeo<N>::NW * 64) void k_trunk(DevState d, NetWei
         const int grp = blockIdx.x + it;
         if (grp >= ngroups) break;
         int tid = threadIdx.x;
-        trunk_group<N>(d, w, net_id, feat, dbg, grp, lds, wpos, cellof, &any_active, tid);
+        trunk_group<N>(d, w, net_id, feat, dbg, grp, lds, hdq_lds, wpos, cellof, &any_active, tid);
     }
 }
 
