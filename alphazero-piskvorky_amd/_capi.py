@@ -40,6 +40,7 @@ EXPORTS = [
     "az_set_gumbel", "az_get_gumbel", "az_gumbel_schedule", "az_gumbel_target", "az_gumbel_vmix", "az_rng_selfplay_tape_gumbel",
     "az_set_external_evaluator", "az_get_external_evaluator", "az_ext_capacity", "az_ext_stats",
     "az_set_solver", "az_get_solver", "az_last_proof", "az_selfplay_proofs", "az_solver_counts", "az_solver_stops",
+    "az_set_win_rule", "az_get_win_rule", "az_rules_winner",
     "az_dist_unique_id", "az_dist_init", "az_dist_rank", "az_dist_world", "az_dist_counts", "az_dist_gather_records",
     "az_dist_allreduce_sum", "az_dist_broadcast",
 ]
@@ -185,6 +186,10 @@ def lib():
             L.az_solver_stops.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
             L.az_selfplay_proofs.argtypes = [C.c_void_p, C.c_void_p]
             L.az_solver_counts.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "az_set_win_rule"):
+            L.az_set_win_rule.argtypes = [C.c_void_p, C.c_int]
+            L.az_get_win_rule.argtypes = [C.c_void_p]
+            L.az_rules_winner.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         _LIB = L
     return _LIB
 
@@ -275,6 +280,39 @@ def forced_prune(k, c_puct, visits, W, prior):
     if removed < 0:
         raise ValueError(f"az_forced_prune refused its arguments (k {k} in (0, {FORCED_K_MAX:g}], counts 0..65534 with at least one visit)")
     return out, removed
+
+
+WIN_RULES = {"freestyle": 0, "exact": 1}                       # az_set_win_rule: AZ_RULE_*
+
+
+def win_rule_id(rule):
+    """AZ_RULE_* of a rule given by name ("freestyle" | "exact"), by number (0 | 1) or as None (the default, freestyle)."""
+    if rule is None:
+        return 0
+    if isinstance(rule, str) and rule in WIN_RULES:
+        return WIN_RULES[rule]
+    if not isinstance(rule, (str, bool)) and rule in (0, 1):
+        return int(rule)
+    raise ValueError(f"win rule must be 'freestyle' or 'exact', got {rule!r}")
+
+
+def win_rule_name(rule):
+    return "exact" if win_rule_id(rule) == 1 else "freestyle"
+
+
+def rules_winner(board, n, k, rule="freestyle"):
+    """Full-board scan under a win rule (az_rules_winner; needs no GPU): board uint8[n*n] or [n, n] with 0 empty, 1 X, 2 O ->
+    1 / 2 when that colour holds a winning run, 3 for a full board without one, 0 otherwise.  ValueError for a bad argument or
+    a board on which both colours hold a winning run."""
+    rid = win_rule_id(rule)
+    b = np.ascontiguousarray(board, np.uint8).reshape(-1)
+    n, k = int(n), int(k)
+    if n < 1 or b.size != n * n:
+        raise ValueError(f"rules_winner: the board has {b.size} cells, n = {n}")
+    rc = int(lib().az_rules_winner(_p(b), n, k, rid))
+    if rc < 0:
+        raise ValueError(f"az_rules_winner refused its arguments (n {n} in 1..15, k {k} in 1..n, cells 0..2, at most one colour with a winning run)")
+    return rc
 
 
 PROOF_UNKNOWN, PROOF_WIN, PROOF_LOSS, PROOF_DRAW = 0, 1, 2, 3    # az_set_solver: AZ_PROOF_*
@@ -794,6 +832,18 @@ class Engine:
         k, p = C.c_double(0.0), C.c_int(0)
         self._check(lib().az_get_forced_playouts(self.h, C.byref(k), C.byref(p)), "az_get_forced_playouts")
         return dict(k=float(k.value), prune=bool(p.value))
+
+    # ---- win rule ----
+    def set_win_rule(self, rule):
+        """Which game is played: "freestyle" (default, the reference's: a run of win_length or more wins) or "exact" (standard
+        Gomoku: a maximal run of exactly win_length wins, overlines give nothing).  Holds for every search, self-play, arena and
+        rules_replay; refused while start positions are set under the other rule.  See include/az_engine.h."""
+        rid = win_rule_id(rule)                                 # ValueError before the engine is touched
+        self._check(lib().az_set_win_rule(self.h, rid), "az_set_win_rule")
+
+    def win_rule(self):
+        """The rule in force, "freestyle" | "exact" (az_get_win_rule)."""
+        return win_rule_name(lib().az_get_win_rule(self.h))
 
     # ---- MCTS-Solver ----
     def set_solver(self, on=True):

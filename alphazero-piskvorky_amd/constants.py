@@ -2,6 +2,7 @@
 Edit here or pass explicit arguments; the engine itself takes an explicit az_config."""
 BOARD_SIZE = 5
 WIN_LENGTH = 4
+WIN_RULE = "freestyle"     # "freestyle": a run of WIN_LENGTH or more wins (the reference's game) | "exact": standard Gomoku, exactly WIN_LENGTH
 NUM_EPISODES = 10
 NUM_WORKERS = 6            # unused by the GPU path (one engine per GPU replaces worker processes)
 DEVICE = "cuda"

@@ -259,25 +259,32 @@ __device__ __forceinline__ void pl_store(u64 *g, const Plane &p)
 
 // games.py:133-166 restricted to lines through the stone just placed at cell a of plane `me`
 // (any new run of >= k must contain it; overlines count, games.py:212-227).
-__device__ __forceinline__ bool wins_through(const Plane &me, int a, int n, int k)
+// rule (az_set_win_rule): WIN_RULE_FREESTYLE = the reference's game, a run of k or more wins; WIN_RULE_EXACT = standard Gomoku,
+// the maximal run through the stone must be exactly k long in at least one direction (a new exact run contains the new stone
+// as well).  Under EXACT each side is probed one cell further, up to k cells: a side reaches k only when the true run exceeds
+// k, and then the capped sum is at least k + 1, so the capped count still compares correctly with k.
+enum { WIN_RULE_FREESTYLE = 0, WIN_RULE_EXACT = 1 };
+__host__ __device__ __forceinline__ bool run_wins(int cnt, int k, int rule) { return rule == WIN_RULE_EXACT ? cnt == k : cnt >= k; }
+__device__ __forceinline__ bool wins_through(const Plane &me, int a, int n, int k, int rule)
 {
     int r = a / n, c = a - r * n;
     const int dr[4] = {0, 1, 1, 1}, dc[4] = {1, 0, 1, -1};
+    const int reach = rule == WIN_RULE_EXACT ? k + 1 : k;      // probes s = 1 .. reach - 1 per side
     bool win = false;
 #pragma unroll
     for (int d = 0; d < 4; d++) {
         int cnt = 1;
-        for (int s = 1; s < k; s++) {
+        for (int s = 1; s < reach; s++) {
             int rr = r + s * dr[d], cc = c + s * dc[d];
             if (rr < 0 || rr >= n || cc < 0 || cc >= n || !pl_get(me, rr * n + cc)) break;
             cnt++;
         }
-        for (int s = 1; s < k; s++) {
+        for (int s = 1; s < reach; s++) {
             int rr = r - s * dr[d], cc = c - s * dc[d];
             if (rr < 0 || rr >= n || cc < 0 || cc >= n || !pl_get(me, rr * n + cc)) break;
             cnt++;
         }
-        win = win || (cnt >= k);
+        win = win || run_wins(cnt, k, rule);
     }
     return win;
 }
@@ -316,15 +323,18 @@ __device__ __forceinline__ int sym_cell(const int *leaf_sym, int item, int p, in
 // The same test done by the 64 lanes of a wavefront together (every lane must be active and hold the same plane and a):
 // lane = 16 * direction + 8 * side + (s - 1) probes the cell s steps from a along that direction and side; one ballot
 // gathers the 64 probes, and the run through a is counted with count-trailing-zero on the inverted 8-bit groups.  Replaces
-// up to 8 (k - 1) dependent scalar probes on the selection's latency chain.  Falls back to the loop for k > 9.
-__device__ __forceinline__ bool wins_through_wave(const Plane &me, int a, int n, int k, int lane)
+// up to 8 (k - 1) dependent scalar probes on the selection's latency chain.  The 8 probe lanes per side serve k <= 9 under
+// FREESTYLE (probes s < k) and k <= 8 under EXACT (probes s <= k); beyond that it falls back to the loop.  The rule is
+// wave-uniform: a select on the probe bound and on the final compare.
+__device__ __forceinline__ bool wins_through_wave(const Plane &me, int a, int n, int k, int rule, int lane)
 {
-    if (k > 9) return wins_through(me, a, n, k);
+    const int reach = rule == WIN_RULE_EXACT ? k + 1 : k;      // probes s = 1 .. reach - 1 per side
+    if (reach > 9) return wins_through(me, a, n, k, rule);
     const int r = a / n, c = a - r * n;
     const int dsel = lane >> 4, s = (lane & 7) + 1, sgn = (lane & 8) ? -s : s;
     const int dr = dsel == 0 ? 0 : 1, dc = dsel == 0 ? 1 : (dsel == 1 ? 0 : (dsel == 2 ? 1 : -1));
     const int rr = r + sgn * dr, cc = c + sgn * dc;
-    const bool inb = s < k && rr >= 0 && rr < n && cc >= 0 && cc < n;
+    const bool inb = s < reach && rr >= 0 && rr < n && cc >= 0 && cc < n;
     const bool stone = inb && pl_get(me, inb ? rr * n + cc : 0);
     const u64 m = __ballot(stone);
     bool win = false;
@@ -333,7 +343,7 @@ __device__ __forceinline__ bool wins_through_wave(const Plane &me, int a, int n,
         const unsigned g = (unsigned)(m >> (16 * d)) & 0xFFFFu;
         const int fwd = __builtin_ctz(~(g & 0xFFu) | 0x100u);          // consecutive stones on the + side (0..8)
         const int bwd = __builtin_ctz(~((g >> 8) & 0xFFu) | 0x100u);   // ... and on the - side
-        win = win || (1 + fwd + bwd >= k);
+        win = win || run_wins(1 + fwd + bwd, k, rule);
     }
     return win;
 }

@@ -134,6 +134,8 @@ struct az_engine {
     // az_set_resign: 0 = off
     double resign_thr = 0.0;
     int resign_min_ply = 0, resign_permille = 0;
+    // az_set_win_rule: AZ_RULE_FREESTYLE (the reference's game) | AZ_RULE_EXACT (standard Gomoku)
+    int win_rule = AZ_RULE_FREESTYLE;
     // az_set_playout_cap: 0 = off; and what the last episode ran under (az_selfplay_sims and the export filter go by the hash)
     int cap_fast = 0, cap_permille = 0, cap_export_full = 0;
     int h_cap_fast = 0, h_cap_permille = 0, h_cap_export_full = 0;
@@ -795,7 +797,7 @@ static int create_engine(const az_config *cfg, az_engine **out, bool deep)
         ALLOC(budget, B * 4); ALLOC(cp_board, B * 8 * sizeof(u64)); ALLOC(cp_state, B * 4 * 4);
 #undef ALLOC
         DevState &d = L.d;
-        d.B = (int)B; d.R = e->R; d.S = cfg->num_simulations; d.k = cfg->win_length;
+        d.B = (int)B; d.R = e->R; d.S = cfg->num_simulations; d.k = cfg->win_length; d.rule = WIN_RULE_FREESTYLE;
         d.c_puct = cfg->c_puct; d.w_noise = cfg->dirichlet_weight;
         d.one_minus_w = (float)(1.0 - cfg->dirichlet_weight);   // Python float (1 - w) as a weak scalar -> float32 (Q8)
         d.board = (u64 *)L.board.p;
@@ -1126,6 +1128,7 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
         d.total_games = sp.num_games; d.reuse = e->reuse; d.game_key0 = sp.game_key0;
         d.cache = ext ? nullptr : (float *)e->cache.p; d.cache_mask = e->cache_mask; d.cache_gen = e->cache_gen;
         d.ext_eval = ext ? 1 : 0;
+        d.rule = e->win_rule;      // which game is played: every search, self-play, arena and preset episode alike
         // start positions are for the games k_refill claims: a preset episode (az_search, az_search_batch) brings its own
         const bool sps = !sp.preset && e->start_count > 0;
         d.start_pos = sps ? (const StartPos *)e->start_tab.p : nullptr;
@@ -2541,23 +2544,62 @@ extern "C" int az_search(az_engine *e, int slot, const uint8_t *board, int playe
     return search_one(e, slot, board, player, last, stones, temperature, noise, u, pi, action, visits, W, prior);
 }
 
-// ---- start positions: later self-play and arena games continue these instead of beginning on the empty board ----
-// a line of k or more stones of either colour anywhere on the board: the kernels test only lines through the last stone
-// (wins_through) and the reference's winner is sticky (games.py:140-141), so such a position would be played on
-static bool has_line(const uint8_t *bd, int n, int k)
+// ---- the win rule: which game is played ----
+static_assert(AZ_RULE_FREESTYLE == WIN_RULE_FREESTYLE && AZ_RULE_EXACT == WIN_RULE_EXACT, "the kernels' rule values are the C-ABI's");
+
+// Full-board scan (no engine, no GPU): every maximal run of either colour in the four directions, counted from its first
+// stone, is held against the rule (run_wins, the compare of the kernels' win test).
+extern "C" int az_rules_winner(const uint8_t *board, int n, int k, int rule)
 {
+    if (!board || n < 1 || n > 15 || k < 1 || k > n || (rule != AZ_RULE_FREESTYLE && rule != AZ_RULE_EXACT)) return AZ_ERR_INVALID;
     static const int dr[4] = {0, 1, 1, 1}, dc[4] = {1, 0, 1, -1};
+    bool won[3] = {false, false, false};
+    int stones = 0;
     for (int r = 0; r < n; r++)
         for (int c = 0; c < n; c++) {
-            const int v = bd[r * n + c];
+            const int v = board[r * n + c];
+            if (v > 2) return AZ_ERR_INVALID;
             if (!v) continue;
+            stones++;
             for (int t = 0; t < 4; t++) {
+                const int pr = r - dr[t], pc = c - dc[t];
+                if (pr >= 0 && pr < n && pc >= 0 && pc < n && board[pr * n + pc] == v) continue;     // not the first stone of its run
                 int len = 1;
-                for (int rr = r + dr[t], cc = c + dc[t]; rr >= 0 && rr < n && cc >= 0 && cc < n && bd[rr * n + cc] == v; rr += dr[t], cc += dc[t]) len++;
-                if (len >= k) return true;
+                for (int rr = r + dr[t], cc = c + dc[t]; rr >= 0 && rr < n && cc >= 0 && cc < n && board[rr * n + cc] == v; rr += dr[t], cc += dc[t]) len++;
+                if (run_wins(len, k, rule)) won[v] = true;
             }
         }
-    return false;
+    if (won[1] && won[2]) return AZ_ERR_INVALID;
+    if (won[1]) return AZ_RES_X;
+    if (won[2]) return AZ_RES_O;
+    return stones == n * n ? AZ_RES_DRAW : AZ_RES_NONE;
+}
+
+static const char *win_rule_name(int rule) { return rule == AZ_RULE_EXACT ? "exact" : "freestyle"; }
+
+extern "C" int az_set_win_rule(az_engine *e, int rule)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (rule != AZ_RULE_FREESTYLE && rule != AZ_RULE_EXACT) return fail(e, AZ_ERR_INVALID, "az_set_win_rule: rule %d (0 = freestyle, 1 = exact)", rule);
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_win_rule: an episode is open (az_selfplay_end first)");
+    if (e->start_count > 0 && rule != e->win_rule)
+        return fail(e, AZ_ERR_STATE, "az_set_win_rule: %d start positions are set, validated under the %s rule (clear them, set the rule, set them again)",
+                    e->start_count, win_rule_name(e->win_rule));
+    e->win_rule = rule;
+    each_state(e, [&](DevState &d) { d.rule = rule; });     // part of every launch's arguments: a captured ply graph is re-captured
+    return AZ_OK;
+}
+
+extern "C" int az_get_win_rule(const az_engine *e) { return e ? e->win_rule : AZ_ERR_INVALID; }
+
+// ---- start positions: later self-play and arena games continue these instead of beginning on the empty board ----
+// A winning run of either colour anywhere on the board, under the engine's rule: the kernels test only lines through the last
+// stone (wins_through) and the reference's winner is sticky (games.py:140-141), so such a position would be played on.
+// Under AZ_RULE_EXACT a position that holds only overlines has no winner and is a legal start.
+static bool has_line(const uint8_t *bd, int n, int k, int rule)
+{
+    const int w = az_rules_winner(bd, n, k, rule);
+    return w == AZ_RES_X || w == AZ_RES_O || w == AZ_ERR_INVALID;
 }
 
 extern "C" int az_set_start_positions(az_engine *e, int count, const uint8_t *boards, const uint8_t *players,
@@ -2585,7 +2627,9 @@ extern "C" int az_set_start_positions(az_engine *e, int count, const uint8_t *bo
         }
         if (st >= nn) return fail(e, AZ_ERR_INVALID, "az_set_start_positions: position %d: no legal action", i);
         if (lasts[i] >= nn || lasts[i] < -1 || (lasts[i] >= 0 && bd[lasts[i]] == 0)) return fail(e, AZ_ERR_INVALID, "az_set_start_positions: position %d: bad last action", i);
-        if (has_line(bd, e->n, e->cfg.win_length)) return fail(e, AZ_ERR_INVALID, "az_set_start_positions: position %d: already won (a line of %d)", i, e->cfg.win_length);
+        if (has_line(bd, e->n, e->cfg.win_length, e->win_rule))
+            return fail(e, AZ_ERR_INVALID, "az_set_start_positions: position %d: already won (a line of %s%d under the %s rule)", i,
+                        e->win_rule == AZ_RULE_EXACT ? "exactly " : "", e->cfg.win_length, win_rule_name(e->win_rule));
         ply[i] = st;
         max_ply = std::max(max_ply, st);
     }
@@ -2679,7 +2723,7 @@ extern "C" int az_rules_replay(az_engine *e, int games, int max_len, const int16
         if (max_len > 0) hr = az_memcpy(e->stream, da.p, actions, G * L * 2, hipMemcpyHostToDevice);
         else hr = hipMemsetAsync(da.p, 0xFF, G * L * 2, e->stream);
         if (hr == hipSuccess) {
-            hipLaunchKernelGGL(k_rules_replay, dim3((games + 63) / 64), dim3(64), 0, e->stream, e->n, e->cfg.win_length, games,
+            hipLaunchKernelGGL(k_rules_replay, dim3((games + 63) / 64), dim3(64), 0, e->stream, e->n, e->cfg.win_length, e->win_rule, games,
                                (int)L, (const short *)da.p, term_before ? (unsigned char *)dt.p : nullptr, (unsigned char *)db.p,
                                (int *)dp.p, (int *)dr.p, (int *)ds.p);
             hr = hipStreamSynchronize(e->stream);

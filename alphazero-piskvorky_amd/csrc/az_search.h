@@ -275,7 +275,7 @@ __device__ __forceinline__ void step_lds(const DevState &d, int b, int lane, Edg
         pl_set(me, a);                                        // games.py:79-81 place, flip player, remember action
         Plane t = me; me = opp; opp = t;
         last = a;
-        if (wins_through_wave(opp, a, N, d.k, lane)) { out_kind = LEAF_TERM_LOSS; break; }  // the side to move has lost
+        if (wins_through_wave(opp, a, N, d.k, d.rule, lane)) { out_kind = LEAF_TERM_LOSS; break; }  // the side to move has lost
         if (pl_count(me) + pl_count(opp) == G::nn) { out_kind = LEAF_TERM_DRAW; break; }
         if constexpr (SOLVER) {
             // a proven edge ends the simulation like a terminal: the value of the side to move below it, no evaluation, no row

@@ -47,6 +47,7 @@ struct DevState {
     int B, R, S, k, max_plies, add_noise, arena, total_games;
     double c_puct, w_noise;
     float one_minus_w;
+    int rule;              // az_set_win_rule: WIN_RULE_FREESTYLE (a run of k or more wins) | WIN_RULE_EXACT (exactly k), beside k in every win test
     // --- slots (current real game per slot) ---
     u64 *board;            // [B][8] absolute bit-planes: words 0-3 X, 4-7 O
     int *s_game, *s_ply, *s_player, *s_last, *s_status, *s_net;
@@ -803,7 +804,7 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
         pl_set(me, a);                                        // games.py:79-81 place, flip player, remember action
         Plane t = me; me = opp; opp = t;
         last = a;
-        if (wins_through_wave(opp, a, N, d.k, lane)) { out_kind = LEAF_TERM_LOSS; break; }  // the side to move has lost
+        if (wins_through_wave(opp, a, N, d.k, d.rule, lane)) { out_kind = LEAF_TERM_LOSS; break; }  // the side to move has lost
         if (pl_count(me) + pl_count(opp) == G::nn) { out_kind = LEAF_TERM_DRAW; break; }
         if constexpr (SOLVER) {
             // a proven edge ends the simulation like a terminal: no evaluation, no row; the value of the side to move below it
@@ -1120,7 +1121,7 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
             pl_set(me, a);                                        // games.py:79-81 place, flip player, remember action
             Plane t = me; me = opp; opp = t;
             last = a;
-            if (wins_through_wave(opp, a, N, d.k, lane)) { out_kind = LEAF_TERM_LOSS; break; }
+            if (wins_through_wave(opp, a, N, d.k, d.rule, lane)) { out_kind = LEAF_TERM_LOSS; break; }
             if (pl_count(me) + pl_count(opp) == G::nn) { out_kind = LEAF_TERM_DRAW; break; }
             if (child == 0) { out_kind = LEAF_EXPAND; break; }    // mcts.py:127 node.is_leaf()
             npar = an;
@@ -1438,7 +1439,7 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
     pl_set(mine, a);
     Plane occ2 = occ;
     pl_set(occ2, a);
-    bool win = wins_through(mine, a, N, d.k);
+    bool win = wins_through(mine, a, N, d.k, d.rule);
     bool full = pl_count(occ2) == G::nn;
     const bool resign = crossed && !exempt && !(win || full);     // a natural end by this very move takes precedence
     if (lane == 0) {
@@ -1697,7 +1698,7 @@ __global__ __launch_bounds__(1024) void k_refill(DevState d, int claim_cap, int 
 // az_rules_replay: Gomoku.apply_action / is_terminal / get_game_result (games.py:64-82,133-179) for whole action lists,
 // one thread per game, with the bit-plane helpers the search kernels use (pl_set, wins_through, pl_count).  The winner is
 // sticky like the reference's cached `winner` that clone() copies (games.py:140-141,206).
-__global__ void k_rules_replay(int n, int k, int games, int max_len, const short *actions, unsigned char *term_before,
+__global__ void k_rules_replay(int n, int k, int rule, int games, int max_len, const short *actions, unsigned char *term_before,
                                unsigned char *boards, int *players, int *results, int *status)
 {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1713,7 +1714,7 @@ __global__ void k_rules_replay(int n, int k, int games, int max_len, const short
         Plane &mine = pl == 1 ? X : O;
         pl_set(mine, a);
         if (res == 0) {
-            if (wins_through(mine, a, n, k)) res = pl;
+            if (wins_through(mine, a, n, k, rule)) res = pl;
             else if (pl_count(X) + pl_count(O) == nn) res = 3;
         }
         pl = 3 - pl;

@@ -7,7 +7,7 @@ import torch
 
 from . import constants as _c
 from . import parallel
-from ._capi import AZ_MAX_SIMULATIONS, Engine
+from ._capi import AZ_MAX_SIMULATIONS, Engine, win_rule_name
 from .controller import device_index, make_batch_policy_value_fn, merge_batch_evaluators, model_kind
 from .mcts import check_solver, numpy_log_table
 from .self_play import check_resign
@@ -19,8 +19,10 @@ def temperature_schedule(move: int) -> float:
 
 class ModelEvaluator:
     def __init__(self, game_class=None, print_games=False, device=None, seed=None, virtual_loss=1, eval_cache=0,
-                 start_positions=None, resign: dict = None, evaluators=None, solver: bool = False):
+                 start_positions=None, resign: dict = None, evaluators=None, solver: bool = False, win_rule: str = None):
         self.game_class = game_class
+        # which game the arena plays: "freestyle" (constants.WIN_RULE's default) or "exact" (standard Gomoku; az_set_win_rule)
+        self.win_rule = win_rule_name(_c.WIN_RULE if win_rule is None else win_rule)
         # opt-in: the arena's evaluations leave the engine (az_set_external_evaluator).  A (candidate, baseline) pair of
         # controller.BatchPolicyValueFn, one BatchPolicyValueFn that serves both nets by its `net` argument, or True = the
         # two controllers' own torch modules, wrapped at every evaluate().
@@ -73,6 +75,11 @@ class ModelEvaluator:
         seed0 = self.seed if self.seed is not None else int(np.random.randint(0, 2 ** 31 - 1))
         if self.seed is None:
             seed0 = parallel.broadcast_seed(seed0, dev)
+        self.win_rule = win_rule_name(self.win_rule)
+        if eng.win_rule() != self.win_rule:
+            if eng.start_positions():
+                eng.clear_start_positions()                               # they were validated under the other rule
+            eng.set_win_rule(self.win_rule)
         if self.start_positions is not None:
             eng.set_start_positions(*self.start_positions, first=lo)      # lo is even (parallel.arena_block): no pair is torn apart
         elif eng.start_positions():

@@ -38,12 +38,16 @@ def positions_from_actions(action_lists, board_size, first_player=1):
 
 
 class Gomoku:
-    def __init__(self, board_size=None, win_length=None):
+    def __init__(self, board_size=None, win_length=None, win_rule=None):
         board_size = _c.BOARD_SIZE if board_size is None else board_size
         if not isinstance(board_size, int):
             raise ValueError("Board size must be an integer.")
         self.board_size = board_size
         self.win_length = _c.WIN_LENGTH if win_length is None else win_length
+        win_rule = _c.WIN_RULE if win_rule is None else win_rule
+        if win_rule not in ("freestyle", "exact"):
+            raise ValueError(f"win rule must be 'freestyle' or 'exact', got {win_rule!r}")
+        self.win_rule = win_rule                                 # "exact": standard Gomoku, an overline wins nothing
         self.cells = np.zeros(board_size * board_size, dtype=np.uint8)   # 0 empty, 1 X, 2 O
         self.current_player = _c.X
         self.winner = None
@@ -102,14 +106,25 @@ class Gomoku:
                 return False
         return True
 
+    def _exact_run_from(self, r, c, dr, dc, who):
+        """A maximal run of exactly win_length stones of `who` begins at (r, c) in direction (dr, dc): the cell before it and
+        the cell behind it are off the board, empty or the opponent's."""
+        n = self.board_size
+
+        def mine(rr, cc):
+            return 0 <= rr < n and 0 <= cc < n and self.cells[rr * n + cc] == who
+        k = self.win_length
+        return not mine(r - dr, c - dc) and self._line_from(r, c, dr, dc, who) and not mine(r + k * dr, c + k * dc)
+
     def is_terminal(self):
         if self.winner is not None:
             return True
         n = self.board_size
+        wins_from = self._exact_run_from if self.win_rule == "exact" else self._line_from
         for idx in np.flatnonzero(self.cells):                  # row-major scan, games.py:144-158
             r, c = divmod(int(idx), n)
             who = int(self.cells[idx])
-            if any(self._line_from(r, c, dr, dc, who) for dr, dc in _DIRS):
+            if any(wins_from(r, c, dr, dc, who) for dr, dc in _DIRS):
                 self.winner = _c.X if who == 1 else _c.O
                 return True
         if not (self.cells == 0).any():
@@ -122,7 +137,7 @@ class Gomoku:
 
     # -- copies -----------------------------------------------------------------------------
     def clone(self):
-        g = Gomoku(self.board_size, self.win_length)
+        g = Gomoku(self.board_size, self.win_length, self.win_rule)
         g.cells = self.cells.copy()
         g.current_player = self.current_player
         g.winner = self.winner

@@ -7,7 +7,7 @@ them to the engine, so np.random.seed(s) reproduces the reference's choices."""
 import numpy as np
 
 from . import constants as _c
-from ._capi import AZ_MAX_SIMULATIONS, FORCED_K_MAX, GUMBEL_DEFAULTS, GUMBEL_M_MAX, Engine
+from ._capi import AZ_MAX_SIMULATIONS, FORCED_K_MAX, GUMBEL_DEFAULTS, GUMBEL_M_MAX, Engine, win_rule_name
 from .controller import BatchPolicyValueFn, PolicyValueFn, device_index, model_kind, weights_version
 
 
@@ -119,6 +119,19 @@ class MCTS:
             eng.set_solver(True)
         return eng
 
+    @staticmethod
+    def _state_rule(state):
+        """the win rule a state carries ("freestyle" | "exact"); a state object without the attribute plays the reference's game"""
+        return win_rule_name(getattr(state, "win_rule", None))
+
+    @staticmethod
+    def _ruled(eng, rule):
+        """the searches read the rule from the state, like board_size and win_length: a cached engine is set to it on reuse"""
+        if getattr(eng, "_searched_rule", "freestyle") != rule:     # the engines here are this object's own: new ones are freestyle
+            eng.set_win_rule(rule)
+            eng._searched_rule = rule
+        return eng
+
     def _root_noise(self, legal):
         """the draws of one noised root from numpy's global RNG: the Dirichlet sample, or Gumbel(0, 1) under gumbel=..."""
         if self.gumbel is not None:
@@ -135,16 +148,16 @@ class MCTS:
 
     def _run_external(self, root_state, temperature, noise, u):
         from .games import Gomoku
-        n, k = root_state.board_size, root_state.win_length
+        n, k, rule = root_state.board_size, root_state.win_length, self._state_rule(root_state)
 
         def evaluate(cells, player, last):
-            g = Gomoku(n, k)
+            g = Gomoku(n, k, rule)
             g.cells = cells
             g.current_player = _c.X if player == 1 else _c.O
             g.last_action = None if last < 0 else (last // n, last % n)
             return self.policy_value_fn(g)
 
-        return self._eng_external(n, k).search_callback(root_state.cells, root_state.player_code(), root_state.last_index(),
+        return self._ruled(self._eng_external(n, k), rule).search_callback(root_state.cells, root_state.player_code(), root_state.last_index(),
                                                         float(temperature), evaluate, noise, u)
 
     def _eng(self, n, k):
@@ -173,12 +186,12 @@ class MCTS:
         if self._external:
             r = self._run_external(root_state, temperature, noise, u)
         elif self._batched:
-            rb = self._eng_batch(n, root_state.win_length, 1).search_batch(
+            rb = self._ruled(self._eng_batch(n, root_state.win_length, 1), self._state_rule(root_state)).search_batch(
                 np.asarray(root_state.cells, np.uint8).reshape(1, n * n), [root_state.player_code()], [root_state.last_index()],
                 float(temperature), None if noise is None else [noise], [u])
             r = {key: val[0] for key, val in rb.items()}
         else:
-            eng = self._eng(n, root_state.win_length)
+            eng = self._ruled(self._eng(n, root_state.win_length), self._state_rule(root_state))
             r = eng.search(root_state.cells, root_state.player_code(), root_state.last_index(), float(temperature), noise, u)
             if self.solver:
                 edges, root = eng.last_proof()
@@ -253,6 +266,9 @@ class MCTS:
         n, k = states[0].board_size, states[0].win_length
         if any((s.board_size, s.win_length) != (n, k) for s in states):
             raise ValueError("run_many: the states differ in board size or win length")
+        rule = self._state_rule(states[0])
+        if any(self._state_rule(s) != rule for s in states):
+            raise ValueError("run_many: the states differ in their win rule")
         if self._external:
             out, visits = [], np.zeros((count, n, n), np.int32)
             for i, s in enumerate(states):
@@ -273,7 +289,7 @@ class MCTS:
         out = [(np.zeros((n, n), dtype=np.float32), None) for _ in range(count)]     # mcts.py:152-153 for the full boards
         visits = np.zeros((count, n, n), np.int32)
         if live:
-            eng = self._eng_batch(n, k, len(live))
+            eng = self._ruled(self._eng_batch(n, k, len(live)), rule)
             r = eng.search_batch(np.stack([np.asarray(states[i].cells, np.uint8).reshape(n * n) for i in live]),
                                  [states[i].player_code() for i in live], [states[i].last_index() for i in live],
                                  T[live], noise if add_root_noise else None, us)

@@ -7,7 +7,7 @@ import torch
 
 from . import constants as _c
 from . import parallel
-from ._capi import AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine, playout_cap_permille, resign_permille
+from ._capi import AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine, playout_cap_permille, resign_permille, win_rule_name
 from .controller import BatchPolicyValueFn, device_index, model_kind
 from .mcts import check_forced_playouts, check_gumbel, check_solver, numpy_log_table
 
@@ -114,8 +114,13 @@ class SelfPlayManager:
                  engines_per_gpu: int = None, subtree_reuse: bool = False, gather_to: int = None,
                  eval_cache: int = 0, virtual_loss: int = 1, trunk: str = "f32", leaf_symmetry: bool = False,
                  start_positions=None, resign: dict = None, evaluator: BatchPolicyValueFn = None,
-                 playout_cap: dict = None, forced_playouts: dict = None, gumbel: dict = None, solver: bool = False):
+                 playout_cap: dict = None, forced_playouts: dict = None, gumbel: dict = None, solver: bool = False,
+                 win_rule: str = None):
         self.controller = controller
+        # which game is played: "freestyle" (constants.WIN_RULE's default, the reference's: a run of WIN_LENGTH or more wins) or
+        # "exact" (standard Gomoku: exactly WIN_LENGTH, an overline wins nothing; az_set_win_rule).  Combines with every option.
+        # Whether exact-rule self-play trains a stronger standard-rule net has not been measured.
+        self.win_rule = win_rule_name(_c.WIN_RULE if win_rule is None else win_rule)
         # opt-in: a controller.BatchPolicyValueFn evaluates every leaf instead of the engine's own net kernels (any torch
         # net on the same GPU; az_set_external_evaluator).  Not with subtree_reuse or leaf_symmetry; eval_cache and trunk
         # have no effect while it is set.
@@ -246,6 +251,11 @@ class SelfPlayManager:
         if eng.trunk_mode() != self.trunk:
             eng.set_trunk_mode(self.trunk)
         T = np.array([float(self.temperature_schedule(m)) for m in range(n * n + 1)], dtype=np.float64)
+        self.win_rule = win_rule_name(self.win_rule)
+        if eng.win_rule() != self.win_rule:
+            if eng.start_positions():
+                eng.clear_start_positions()                               # they were validated under the other rule
+            eng.set_win_rule(self.win_rule)
         if self.start_positions is not None:
             eng.set_start_positions(*self.start_positions, first=lo)      # by global game id, like the seed
         elif eng.start_positions():

@@ -365,7 +365,7 @@ int az_arena(az_engine *e, const az_arena_args *args, az_arena_result *out, int3
 
 /* ---- rules only: Gomoku.apply_action / is_terminal / get_game_result (games.py:64-82,133-179) ----
  * Replays `games` action lists (actions[g][max_len], r*n+c, -1 = end of list) from the empty board with X to move, on the
- * device, with the same bit-plane win test the search kernels use.  Like the reference, apply_action does not look at
+ * device, with the same bit-plane win test the search kernels use (under the engine's win rule, az_set_win_rule).  Like the reference, apply_action does not look at
  * the terminal flag (a list may continue past the end of the game; the winner stays the first one, games.py:140-141).
  * Outputs (term_before may be NULL): term_before[g][i] = is_terminal() before move i; boards[g][n*n] final cells
  * (0 empty, 1 X, 2 O); players[g] = side to move afterwards; results[g] = AZ_RES_*; first_illegal[g] = index of the
@@ -449,7 +449,7 @@ int az_set_leaf_symmetry(az_engine *e, int on);
  *     start position.  Counters: plies = records = root_evals (less retained roots) count searched plies.
  *   Checked on the host before anything is uploaded, by az_search_batch's rules (cell values, a legal action exists, last
  *     in range and on an occupied cell or -1, player 1 or 2) and one more: no line of win_length or more stones of either
- *     colour anywhere on the board (an already won position would be played on).  AZ_ERR_INVALID with the index of the first
+ *     colour anywhere on the board (an already won position would be played on; under AZ_RULE_EXACT: no run of exactly win_length).  AZ_ERR_INVALID with the index of the first
  *     offending position in az_last_error; the previous setting is kept.  first >= 0.  AZ_ERR_STATE while an episode is
  *     open.  az_selfplay_begin / az_selfplay return AZ_ERR_INVALID when max_plies > 0 and some position already holds
  *     max_plies or more stones.
@@ -458,6 +458,28 @@ int az_set_leaf_symmetry(az_engine *e, int on);
 int az_set_start_positions(az_engine *e, int count, const uint8_t *boards /* [count][n*n] 0 / 1 X / 2 O */,
                            const uint8_t *players, const int16_t *lasts, int64_t first);
 int az_get_start_positions(const az_engine *e);   /* count in force, 0 = none */
+
+/* Opt-in: the win rule, i.e. which game is played.  AZ_RULE_FREESTYLE is the default and the reference's game (games.py:212-227):
+ * a run of win_length OR MORE stones wins.  AZ_RULE_EXACT is standard Gomoku: the stone just placed wins when, in at least one
+ * of the four directions, the maximal run of the mover's stones through it is EXACTLY win_length long; board edges end a run like
+ * an empty cell.  A stone that makes an overline in one direction and an exact run in another wins; a stone that makes only
+ * overlines does not, and the game goes on; a full board without a winner is a draw; the winner stays sticky.  A new exact run
+ * must contain the new stone, so the kernels' test of the lines through the last stone stays sufficient under both rules.
+ * The rule holds wherever the win test runs: every descent of the tree kernels, the game's own terminal test, az_selfplay*,
+ * az_arena, az_search, az_search_batch, az_search_callback, az_rules_replay, the external evaluator path and deep engines; the
+ * solver proves what the descent's win test finds, so it proves the game that is played.  It combines with every option:
+ * there is no refused pair.  An engine whose rule is never set plays the reference's game bit for bit.
+ * az_set_win_rule: AZ_ERR_INVALID for a rule other than 0 / 1; AZ_ERR_STATE while an episode is open, and when start positions
+ * are set and the rule would change -- they were validated under the other rule: clear them (count = 0), set the rule, set them
+ * again.  az_set_start_positions checks "already won" under the rule in force: under AZ_RULE_EXACT a position that holds only
+ * overlines is a legal start, one that holds an exact run is refused.
+ * az_rules_winner(board, n, k, rule) is a host-side helper (no engine, no GPU): a scan of the whole board[n*n] (0 empty, 1 X,
+ * 2 O; 1 <= n <= 15, 1 <= k <= n) that returns AZ_RES_X / AZ_RES_O when that colour holds a winning run under `rule`, AZ_RES_DRAW
+ * for a full board without one, AZ_RES_NONE otherwise, and AZ_ERR_INVALID for a bad argument or when both colours hold one. */
+enum { AZ_RULE_FREESTYLE = 0, AZ_RULE_EXACT = 1 };
+int az_set_win_rule(az_engine *e, int rule);
+int az_get_win_rule(const az_engine *e);
+int az_rules_winner(const uint8_t *board, int n, int k, int rule);
 
 /* The search value per record, and opt-in resignation (AlphaGo Zero resigned below a value threshold and let a share of its
  * games play out to measure the false positives; the reference plays every game to the end, self_play.py:52-58).
