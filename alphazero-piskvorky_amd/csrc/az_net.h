@@ -76,9 +76,10 @@ struct NetGeo {
     static constexpr int M = G * nn;                               // real GEMM columns (board cells)
     // 16-cell MFMA tiles.  n = 15: one tile = one board row + its right padding cell (contiguous in the padded
     // image, so the 16 lanes of a fragment hit 16 consecutive LDS banks); other sizes: 16 consecutive cells.
+    // Row tiles are what k_tile (grid: boards x board rows), the emulated trunks and the FC constants use at n = 15; the fused
+    // float32 trunk keeps MT, MR and the images but lays its 15 tiles round the board instead (RingGeo below).
     static constexpr bool ROWT = (N == 15);
     static constexpr int MT = ROWT ? G * N : (M + 15) / 16, MR = MT * 16;
-    static constexpr bool BORDER_SKIP = ROWT && G == 1;            // cell tile t is board row t: conv_layer leaves out the taps on the zero rows
     static constexpr int CS = up16(G * PP);                        // channel stride of padded planes (floats), == 16 mod 32
     static constexpr int CS3 = up16(MR);                           // channel stride of the conv3 output image
     static constexpr int LDSF = trunk_lds_floats(N, G, 96);       // max(96 CS, 128 CS3, OUT3_CM_STRIDE MR)
@@ -99,6 +100,143 @@ struct NetGeo {
     static constexpr int FSTR0 = 64 * (QGP + QGV);
     static constexpr int FSTR = FSTR0 + ((4 - (FSTR0 % 32) + 32) % 32);   // LDS row stride, == 4 (mod 32), multiple of 4
 };
+
+// The ring tiling of the fused float32 trunk at n = 15 (RingGeo below): tile lane -> padded-image position and board cell.
+//   tile 0 / n - 1     : row 0 / row n - 1, all 15 columns                         1 junk lane each
+//   tile 1 / n - 2     : column 0 / column n - 1, rows 1..13                       3 junk lanes each
+//   tiles 2 .. n - 3   : the 13 x 13 interior, 169 cells in 11 x 16 lanes          7 junk lanes
+// so that a whole tile, not one lane of sixteen, faces each zero border: the row tiles have nothing to add at ky = 0 / ky = 2
+// as before, and the column tiles nothing at kx = 0 / kx = 2 (conv_layer, BorderSkip).
+// Banks: a fragment read is one ds_read_b128 per lane at float4 index (cg*4 + q) * CS + pos, served 16 lanes at a time (each
+// group takes lanes r16 {0-3, 12-15} of one q and {4-11} of the next, i.e. sixteen DIFFERENT r16); the bank is 4 (index mod 16) and
+// CS is a multiple of 16, so a read is conflict-free exactly when the 16 lanes of a tile have distinct pos mod 16 =
+// (r + c + 2) mod 16.  A row has 15 consecutive residues and a column's positions are PW = 17 apart.  The interior cannot have it
+// everywhere: the diagonals r + c = 13, 14, 15 hold 12, 13 and 12 interior cells against 11 tiles, so at least 4 cells share a
+// residue with a tile-mate.  The fill reaches 4: the cells in row-major order, each into the first interior tile that has fewer than
+// 15 cells and none of its residue (L-shaped runs of the board, so the heads' feature stores stay mostly contiguous); the four
+// cells that find no such tile take the 16th lane of tiles 2..5, one each.
+// Each of the 4 pairs costs its tile a second pass in EVERY 16-lane group of a read (a group holds one lane of each r16): 8 cycles
+// instead of 4 for the reads of tiles 2..5 (SQ_LDS_BANK_CONFLICT, and that it stays behind the MFMA issue).
+// A junk lane repeats the position of its tile's last cell: an identical LDS address is a broadcast (measured: the conflict
+// counter reads the same to the digit with every junk lane on a residue of its own instead), it stays inside the image at
+// every tap offset, and it keeps a border tile's dead taps dead.  Its cellof is 0xFFFF.
+template <int N>
+struct RingMap {
+    unsigned short pos[N * 16], cell[N * 16];
+    int cnt[N];
+    __host__ __device__ constexpr void put(int t, int r, int c)
+    {
+        pos[t * 16 + cnt[t]] = (unsigned short)((r + 1) * (N + 2) + (c + 1));
+        cell[t * 16 + cnt[t]] = (unsigned short)(r * N + c);
+        cnt[t]++;
+    }
+    __host__ __device__ constexpr bool has_residue(int t, int res) const
+    {
+        for (int i = 0; i < cnt[t]; i++) if ((pos[t * 16 + i] & 15) == res) return true;
+        return false;
+    }
+};
+template <int N>
+__host__ __device__ constexpr RingMap<N> ring_map()
+{
+    RingMap<N> m{};
+    for (int c = 0; c < N; c++) { m.put(0, 0, c); m.put(N - 1, N - 1, c); }
+    for (int r = 1; r < N - 1; r++) { m.put(1, r, 0); m.put(N - 2, r, N - 1); }
+    int spill_r[N] = {}, spill_c[N] = {}, ns = 0;
+    for (int r = 1; r < N - 1; r++)
+        for (int c = 1; c < N - 1; c++) {
+            int t = 2;
+            while (t < N - 2 && (m.cnt[t] >= 15 || m.has_residue(t, (r + c + 2) & 15))) t++;
+            if (t < N - 2) m.put(t, r, c);
+            else if (ns < N) { spill_r[ns] = r; spill_c[ns] = c; ns++; }
+        }
+    for (int j = 0; j < ns && j < N - 4; j++) m.put(2 + j, spill_r[j], spill_c[j]);
+    for (int t = 0; t < N; t++)
+        for (int i = m.cnt[t]; i < 16; i++) { m.pos[t * 16 + i] = m.pos[t * 16 + m.cnt[t] - 1]; m.cell[t * 16 + i] = 0xFFFF; }
+    return m;
+}
+// what RingGeo asserts of the map
+template <int N>
+__host__ __device__ constexpr bool ring_cells_once(const RingMap<N> &m)
+{
+    int seen[N * N] = {};
+    for (int i = 0; i < N * 16; i++) if (m.cell[i] != 0xFFFF) { if (m.cell[i] >= N * N) return false; seen[m.cell[i]]++; }
+    for (int p = 0; p < N * N; p++) if (seen[p] != 1) return false;
+    return true;
+}
+template <int N>
+__host__ __device__ constexpr bool ring_borders(const RingMap<N> &m)      // the border tiles hold cells of their border only, at their positions
+{
+    for (int i = 0; i < N * 16; i++) {
+        const int t = i >> 4, p = m.cell[i];
+        if (p == 0xFFFF) continue;
+        const int r = p / N, c = p - r * N;
+        if (m.pos[i] != (r + 1) * (N + 2) + (c + 1)) return false;
+        if ((t == 0 && r != 0) || (t == N - 1 && r != N - 1) || (t == 1 && c != 0) || (t == N - 2 && c != N - 1)) return false;
+    }
+    return true;
+}
+template <int N>
+__host__ __device__ constexpr int ring_conflicts(const RingMap<N> &m, bool worst_tile)     // lane pairs at different positions with equal pos mod 16
+{
+    int total = 0, worst = 0;
+    for (int t = 0; t < N; t++) {
+        int k = 0;
+        for (int i = 0; i < 16; i++)
+            for (int j = i + 1; j < 16; j++) {
+                const int a = m.pos[t * 16 + i], b = m.pos[t * 16 + j];
+                if (a != b && (a & 15) == (b & 15)) k++;
+            }
+        total += k;
+        if (k > worst) worst = k;
+    }
+    return worst_tile ? worst : total;
+}
+template <int N>
+__host__ __device__ constexpr bool ring_in_image(const RingMap<N> &m)
+{
+    for (int i = 0; i < N * 16; i++)
+        if (m.pos[i] < (N + 2) + 1 || m.pos[i] > (N + 2) * (N + 2) - (N + 2) - 2) return false;
+    for (int t = 0; t < N; t++)          // a junk lane repeats a cell of its own tile
+        for (int i = 0; i < 16; i++) {
+            if (m.cell[t * 16 + i] != 0xFFFF) continue;
+            bool twin = false;
+            for (int j = 0; j < 16; j++) if (m.cell[t * 16 + j] != 0xFFFF && m.pos[t * 16 + j] == m.pos[t * 16 + i]) twin = true;
+            if (!twin) return false;
+        }
+    return true;
+}
+
+// Geometry of the fused float32 plain trunk at n = 15 (trunk_group<15> / k_trunk<15> only): NetGeo<15>'s images, tile count, waves
+// and LDS, with the tiles laid round the board (RingMap above) and the predicate that tells conv_layer which (tile, tap) pairs
+// multiply nothing but a zero border: 12 of the 135 per layer.
+template <int N>
+struct RingGeo : NetGeo<N> {
+    typedef NetGeo<N> B;
+    static_assert(N == 15 && B::G == 1 && B::MT == N, "one board per workgroup, as many tiles as board rows");
+    static constexpr bool BORDER_SKIP = true;                      // conv_layer leaves out the taps that tap_dead names
+    static constexpr RingMap<N> map = ring_map<N>();
+    // tile t has nothing to add at this tap: every cell of it reads the zero row above / below or the zero column left / right
+    __host__ __device__ static constexpr bool tap_dead(int t, int tap)
+    {
+        const int ky = tap / 3, kx = tap % 3;
+        return (t == 0 && ky == 0) || (t == N - 1 && ky == 2) || (t == 1 && kx == 0) || (t == N - 2 && kx == 2);
+    }
+    __host__ __device__ static constexpr int live_pairs()
+    {
+        int v = 0;
+        for (int t = 0; t < B::MT; t++) for (int tap = 0; tap < 9; tap++) v += tap_dead(t, tap) ? 0 : 1;
+        return v;
+    }
+    static_assert(ring_cells_once(map), "every board cell is in exactly one tile lane");
+    static_assert(ring_borders(map), "tiles 0, 14, 1, 13 hold only cells of row 0, row 14, column 0, column 14");
+    static_assert(ring_conflicts(map, true) <= 1 && ring_conflicts(map, false) == 4, "at most one lane pair per tile shares a bank group, four in all");
+    static_assert(ring_in_image(map), "every lane's 3x3 window lies inside the padded image; a junk lane repeats a tile-mate");
+    static_assert(live_pairs() == 9 * B::MT - 12, "123 live (tile, tap) pairs per layer");
+};
+// the geometry trunk_group / k_trunk run on
+template <int N>
+using FusedGeo = std::conditional_t<N == 15, RingGeo<N>, NetGeo<N>>;
 
 
 // Geometry of the ResidualBlock variant (BASELINE config 5; topology from the reference's historical checkpoints,
@@ -179,33 +317,35 @@ __device__ __forceinline__ ConvPre<CIN> conv_prefetch(const float *__restrict__ 
     return r;
 }
 
-// Border rows of a row-tiled single-board geometry (n = 15: cell tile t is board row t).  The three taps with ky = 0 of row 0 and
-// the three with ky = 2 of row n - 1 read nothing but the top / bottom padding row of the LDS image, which is zero by
-// construction: conv_layer leaves their MFMAs (and fragment reads) out.  Only a geometry that says so (BORDER_SKIP) is
-// touched: the tile-split geometries (TileGeoT::A / B) and the persistent search kernel's have no such member and compile to
-// the code they had.
+// Border tiles of a single-board geometry whose tiles lie along the borders (RingGeo, n = 15).  For the tile of row 0 the three
+// taps with ky = 0 read nothing but the top padding row of the LDS image, for the tile of row n - 1 the three with ky = 2 nothing
+// but the bottom one; likewise the tile of column 0 at the three taps with kx = 0 reads only the left padding column and the
+// tile of column n - 1 at kx = 2 only the right one (its junk lanes repeat a cell of the same column).  The padding ring is zero
+// by construction: conv_layer leaves those MFMAs (and fragment reads) out.  Which (tile, tap) pairs they are is the
+// geometry's word (G::tap_dead).  Only a geometry that says so (BORDER_SKIP) is touched: NetGeo, the tile-split geometries
+// (TileGeoT::A / B) and the persistent search kernel's have no such member and compile to the code they had.
 // Exactness: for a finite weight fma(w, +0, acc) == acc bit for bit unless acc is -0 (then +0).  A -0 accumulator can only
 // come from a real product that underflowed, and the layer's output erases its sign in both variants: acc + bias, then
 // v > 0 ? v : +0 (the residual paths likewise), so every layer output keeps its bits.  With a non-finite weight the full chain
-// made NaN on the border rows where the oracle (conv3x3_core: out-of-board taps skipped) does not: the skip is the definition.
+// made NaN on the border cells where the oracle (conv3x3_core: out-of-board taps skipped) does not: the skip is the definition.
+// Which tile and lane computes an output element does not enter: it is the same k-ordered chain over the same 3x3 window.
 template <class G, class = void>
-struct BorderSkip { static constexpr bool value = false; static constexpr int n = 0; };
+struct BorderSkip { static constexpr bool value = false; };
 template <class G>
-struct BorderSkip<G, std::void_t<decltype(G::BORDER_SKIP)>> { static constexpr bool value = G::BORDER_SKIP; static constexpr int n = G::n; };
+struct BorderSkip<G, std::void_t<decltype(G::BORDER_SKIP)>> { static constexpr bool value = G::BORDER_SKIP; };
 
-// tile i of cell-tile group mgc (board row mgc + i * MG) has nothing to add at this tap
-template <bool SKIP, int N, int MG>
+// tile i of cell-tile group mgc (tile mgc + i * MG of the geometry) has nothing to add at this tap
+template <bool SKIP, class G, int MG>
 __host__ __device__ constexpr bool border_dead(int mgc, int i, int tap)
 {
-    if (!SKIP) return false;
-    const int row = mgc + i * MG;
-    return (row == 0 && tap / 3 == 0) || (row == N - 1 && tap / 3 == 2);
+    if constexpr (SKIP) return G::tap_dead(mgc + i * MG, tap);
+    else return false;
 }
-template <bool SKIP, int N, int MG>
+template <bool SKIP, class G, int MG>
 __host__ __device__ constexpr int border_live(int mgc, int mtw, int tap)
 {
     int c = 0;
-    for (int i = 0; i < mtw; i++) c += border_dead<SKIP, N, MG>(mgc, i, tap) ? 0 : 1;
+    for (int i = 0; i < mtw; i++) c += border_dead<SKIP, G, MG>(mgc, i, tap) ? 0 : 1;
     return c;
 }
 
@@ -245,10 +385,9 @@ __device__ __forceinline__ void conv_layer(const float *in, float *out, const fl
     constexpr int KS4 = (KS + 3) / 4;
     const int ng = wave % NG, mg = wave / NG;       // wave is wave-uniform (readfirstlane) -> scalar control flow
     const int q = lane >> 4, r16 = lane & 15;
-    // border rows (BorderSkip above): the packed-input layers of a fused row-tiled kernel; the cell-tile group is then a
-    // compile-time value of the body (MGC), so that "tile i is row 0 / row n - 1" folds away in the unrolled tap loop
+    // border tiles (BorderSkip above): the packed-input layers of a fused kernel whose geometry names dead taps; the cell-tile
+    // group is then a compile-time value of the body (MGC), so that G::tap_dead(tile, tap) folds away in the unrolled tap loop
     constexpr bool SKIP = BorderSkip<G>::value && !SUBSET && CIN >= 32;
-    constexpr int BN = BorderSkip<G>::n;
 
     auto body = [&](auto mtw_c, auto mg_c) __attribute__((always_inline)) {
     constexpr int MTW = decltype(mtw_c)::value;
@@ -309,7 +448,7 @@ __device__ __forceinline__ void conv_layer(const float *in, float *out, const fl
         for (int j = 0; j < NQ; j++) bw[j] = pre ? pre->bw[j] : wp4[(size_t)j * 64];
 #pragma unroll
         for (int i = 0; i < MTW; i++)
-            if (!border_dead<SKIP, BN, MG>(MGC, i, 0)) a0[i] = in4[ra[i]];
+            if (!border_dead<SKIP, G, MG>(MGC, i, 0)) a0[i] = in4[ra[i]];
         // The nine taps unrolled, so that every fragment address is the tile's base register + a constant (the ds_read's
         // 16-bit immediate: at most ((NQ - 1) 4 CS + 2 PW + 2) x 16 B = 58.9 KB at n = 15) and the weight registers of
         // consecutive taps are renamed instead of copied.  The rolled loop kept a running index per tile and recomputed
@@ -338,24 +477,24 @@ __device__ __forceinline__ void conv_layer(const float *in, float *out, const fl
                 // first group of the next tap (the last group of all reads its own again: never used)
                 const int gtap = sq + 1 < NQ ? tap : tn, gsq = sq + 1 < NQ ? sq + 1 : (tap + 1 < 9 ? 0 : sq);
                 const int noff = gsq * 4 * G::CS + (gtap / 3) * G::PW + (gtap % 3);
-                // a tile on a border row neither reads nor multiplies the fragments of its zero row
+                // a border tile neither reads nor multiplies the fragments of its zero row or column
 #pragma unroll
                 for (int i = 0; i < MTW; i++)
-                    if (!border_dead<SKIP, BN, MG>(MGC, i, gtap)) nxt[i] = in4[ra[i] + noff];
+                    if (!border_dead<SKIP, G, MG>(MGC, i, gtap)) nxt[i] = in4[ra[i] + noff];
 #pragma unroll
                 for (int e = 0; e < 4; e++)
 #pragma unroll
                     for (int i = 0; i < MTW; i++) {
-                        if (border_dead<SKIP, BN, MG>(MGC, i, tap)) continue;
+                        if (border_dead<SKIP, G, MG>(MGC, i, tap)) continue;
                         const float4 wv = bw[sq];
                         const float we = e == 0 ? wv.x : e == 1 ? wv.y : e == 2 ? wv.z : wv.w;
                         const float ae = e == 0 ? cur[i].x : e == 1 ? cur[i].y : e == 2 ? cur[i].z : cur[i].w;
                         acc[i] = mfma4(we, ae, acc[i]);
                     }
-                // one read after the four MFMAs of a tile; where this group and the next differ in live tiles (the taps next to a
-                // change of ky), the surplus reads follow the last MFMAs, surplus MFMAs go without a read
-                const int nm = border_live<SKIP, BN, MG>(MGC, MTW, tap);
-                const int nr = border_live<SKIP, BN, MG>(MGC, MTW, gtap);
+                // one read after the four MFMAs of a tile; where this group and the next differ in live tiles (with the ring
+                // tiling at every change of tap), the surplus reads follow the last MFMAs, surplus MFMAs go without a read
+                const int nm = border_live<SKIP, G, MG>(MGC, MTW, tap);
+                const int nr = border_live<SKIP, G, MG>(MGC, MTW, gtap);
 #pragma unroll
                 for (int i = 0; i < MTW; i++) {
                     if (i < nm) __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);         // 4 MFMAs
@@ -473,7 +612,8 @@ __device__ __forceinline__ void trunk_group(const DevState &d, const NetWeights 
                                                       unsigned long long *dbg, int grp, float *lds, float *hdq_lds, unsigned short *wpos,
                                                       unsigned short *cellof, int *any_active_p, int tid)
 {
-    typedef NetGeo<N> G;
+    typedef FusedGeo<N> G;
+    constexpr bool RING = BorderSkip<G>::value;       // the tile tables come from G::map
     int &any_active = *any_active_p;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -482,6 +622,12 @@ __device__ __forceinline__ void trunk_group(const DevState &d, const NetWeights 
     // the head weights in block order (4 KB, 8 bytes per thread): asked for first of all, so that they arrive with the leaf words
     // requested below, and put into LDS in front of the zero fill; read by trunk_heads only
     const float2 hq = reinterpret_cast<const float2 *>(w.hdq)[tid];
+    // ring tiling: the thread's entry of the tile map (960 B of constant data, in L2 after the first workgroups), asked for with
+    // the head weights and stored with them
+    unsigned short map_pos = 0, map_cell = 0xFFFF;
+    if constexpr (RING) {
+        if (tid < G::MR) { map_pos = G::map.pos[tid]; map_cell = G::map.cell[tid]; }
+    }
     if (tid == 0) any_active = 0;
     __syncthreads();
     if (tid < G::G) {
@@ -504,7 +650,15 @@ __device__ __forceinline__ void trunk_group(const DevState &d, const NetWeights 
     for (int e = 0; e < EPT; e++) {
         const int m = tid + e * G::NW * 64;
         int pos = G::PW + 1, cell = 0xFFFF;
-        if (m < G::MR) {
+        if constexpr (RING) {
+            // thread m encodes board CELL m, whichever tile lane reads it later: its leaf words do not wait for the map
+            static_assert(EPT == 1 && G::G == 1, "one tile lane per thread, one board");
+            if (m < G::nn) {
+                const int r = m / N, c = m - r * N;
+                pos = (r + 1) * G::PW + (c + 1);
+                cell = m;
+            }
+        } else if (m < G::MR) {
             if constexpr (G::ROWT) {
                 const int t = m >> 4, c = m & 15, g = t / N, r = t - g * N;
                 pos = g * G::PP + (r + 1) * G::PW + (c + 1);                 // c == N is the right padding cell of the row
@@ -532,6 +686,9 @@ __device__ __forceinline__ void trunk_group(const DevState &d, const NetWeights 
         }
     }
     reinterpret_cast<float2 *>(hdq_lds)[tid] = hq;       // in front of the zero fill, whose writes cover this one's latency
+    if constexpr (RING) {
+        if (tid < G::MR) { wpos[tid] = map_pos; cellof[tid] = map_cell; }
+    }
     {
         float4 *z = reinterpret_cast<float4 *>(lds);
         for (int i = tid; i < (96 * G::CS) / 4; i += G::NW * 64) z[i] = float4{0.f, 0.f, 0.f, 0.f};
@@ -572,7 +729,7 @@ template <int N>
 __global__ __launch_bounds__(NetGeo<N>::NW * 64) void k_trunk(DevState d, NetWeights w, int net_id, float *__restrict__ feat,
                                                unsigned long long *dbg)
 {
-    typedef NetGeo<N> G;
+    typedef FusedGeo<N> G;                    // n = 15: the ring tiling; sizes, waves and LDS are NetGeo<N>'s
     __shared__ __attribute__((aligned(16))) float lds[G::LDSF];
     __shared__ __attribute__((aligned(16))) float hdq_lds[1024];     // head-conv weights in block order, [k/4][8 rows][4]
     __shared__ unsigned short wpos[G::MR];     // centre position of tile cell m in the padded image
