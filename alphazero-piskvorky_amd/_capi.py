@@ -41,6 +41,7 @@ EXPORTS = [
     "az_set_external_evaluator", "az_get_external_evaluator", "az_ext_capacity", "az_ext_stats",
     "az_set_solver", "az_get_solver", "az_last_proof", "az_selfplay_proofs", "az_solver_counts", "az_solver_stops",
     "az_set_win_rule", "az_get_win_rule", "az_rules_winner",
+    "az_set_threat_search", "az_get_threat_search", "az_threat_batch", "az_threat_solve", "az_selfplay_threats", "az_threat_stats",
     "az_dist_unique_id", "az_dist_init", "az_dist_rank", "az_dist_world", "az_dist_counts", "az_dist_gather_records",
     "az_dist_allreduce_sum", "az_dist_broadcast",
 ]
@@ -190,6 +191,13 @@ def lib():
             L.az_set_win_rule.argtypes = [C.c_void_p, C.c_int]
             L.az_get_win_rule.argtypes = [C.c_void_p]
             L.az_rules_winner.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        if hasattr(L, "az_set_threat_search"):
+            L.az_set_threat_search.argtypes = [C.c_void_p, C.c_int, C.c_int]
+            L.az_get_threat_search.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+            L.az_threat_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
+            L.az_threat_solve.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4
+            L.az_selfplay_threats.argtypes = [C.c_void_p, C.c_void_p]
+            L.az_threat_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 5
         _LIB = L
     return _LIB
 
@@ -329,6 +337,48 @@ def solver_counts(visits, status):
     if lib().az_solver_counts(len(visits), _p(visits), _p(status), _p(out)):
         raise ValueError("az_solver_counts refused its arguments (at least one child, counts >= 0, statuses 0..3)")
     return out
+
+
+THREAT_MAX_DEPTH = 16                                          # az_set_threat_search: AZ_THREAT_MAX_DEPTH
+THREAT_DEFAULTS = dict(max_depth=8, node_budget=256)
+
+
+def check_threat_search(threat_search, solver=True):
+    """None (off) or the checked dict(max_depth, node_budget) of a seam's threat_search option (az_set_threat_search).  True means
+    the defaults.  ValueError for unknown keys, values out of range, or without the solver it hands its results to."""
+    if not threat_search:
+        return None
+    cfg = dict(THREAT_DEFAULTS)
+    if threat_search is not True:
+        unknown = set(threat_search) - set(cfg)
+        if unknown:
+            raise ValueError(f"threat_search: unknown keys {sorted(unknown)}")
+        cfg.update(threat_search)
+    cfg = {k: int(v) for k, v in cfg.items()}
+    if not 1 <= cfg["max_depth"] <= THREAT_MAX_DEPTH or not 1 <= cfg["node_budget"] <= 65535:
+        raise ValueError(f"threat_search: max_depth in 1..{THREAT_MAX_DEPTH} and node_budget in 1..65535, got {cfg}")
+    if not solver:
+        raise ValueError("threat_search needs solver=True: it hands its results to the solver")
+    return cfg
+
+
+def threat_solve(board, n, k, rule="freestyle", player=1, max_depth=8, node_budget=256):
+    """The root threat search of one position on the host (az_threat_solve; needs no GPU): board uint8[n*n] or [n, n] with
+    0 empty, 1 X, 2 O and `player` to move -> dict(status, move, depth, nodes, edges int8[n*n]).  status and edges are PROOF_*
+    seen from the mover; move = -1 and depth = 0 without a win; the search was exhausted iff nodes > node_budget.  ValueError
+    for a bad argument, a full board or a position that is already won."""
+    rid = win_rule_id(rule)
+    b = np.ascontiguousarray(board, np.uint8).reshape(-1)
+    n, k = int(n), int(k)
+    if n < 1 or b.size != n * n:
+        raise ValueError(f"threat_solve: the board has {b.size} cells, n = {n}")
+    mv, dp, nd = (np.zeros(1, np.int32) for _ in range(3))
+    edges = np.zeros(n * n, np.int8)
+    rc = int(lib().az_threat_solve(_p(b), n, k, rid, int(player), int(max_depth), int(node_budget), _p(mv), _p(dp), _p(nd), _p(edges)))
+    if rc < 0:
+        raise ValueError("az_threat_solve refused its arguments (n in 1..15, k in 1..n, cells 0..2, player 1 / 2, max_depth in 1..16, "
+                         "node_budget in 1..65535, a legal action, no winning run on the board)")
+    return dict(status=rc, move=int(mv[0]), depth=int(dp[0]), nodes=int(nd[0]), edges=edges)
 
 
 GUMBEL_M_MAX = 64                                              # az_set_gumbel: m <= min(n * n, 64)
@@ -879,6 +929,48 @@ class Engine:
         v = C.c_int64(0)
         self._check(lib().az_solver_stops(self.h, C.byref(v)), "az_solver_stops")
         return int(v.value)
+
+    # ---- root threat search ----
+    def set_threat_search(self, max_depth=8, node_budget=256):
+        """Opt-in: an exact forced-four search (VCF) on every root before the simulations; its proven wins and forced blocks go
+        to the solver as premarked root statuses.  max_depth = 0 switches it off.  Needs set_solver(True).  See
+        include/az_engine.h."""
+        self._check(lib().az_set_threat_search(self.h, int(max_depth), int(node_budget)), "az_set_threat_search")
+
+    def threat_search(self):
+        """(max_depth, node_budget) in force, (0, 0) = off (az_get_threat_search)."""
+        d, b = C.c_int(0), C.c_int(0)
+        self._check(lib().az_get_threat_search(self.h, C.byref(d), C.byref(b)), "az_get_threat_search")
+        return int(d.value), int(b.value)
+
+    def threat_batch(self, boards, players, max_depth=8, node_budget=256, outputs=("status", "move", "depth", "nodes", "edges")):
+        """The threat search kernel on its own (az_threat_batch): boards uint8[count, n*n] (0 empty, 1 X, 2 O), players
+        uint8[count] -> dict of the requested outputs: status int8[count], move / depth / nodes int32[count], edges
+        int8[count, n*n]."""
+        boards = np.ascontiguousarray(boards, np.uint8).reshape(-1, self.nn) if np.size(boards) else np.zeros((0, self.nn), np.uint8)
+        players = np.ascontiguousarray(players, np.uint8).reshape(-1)
+        count = len(boards)
+        if len(players) != count:
+            raise ValueError("threat_batch: one player per board")
+        shapes = dict(status=((count,), np.int8), move=((count,), np.int32), depth=((count,), np.int32), nodes=((count,), np.int32),
+                      edges=((count, self.nn), np.int8))
+        out = {k: np.zeros(*shapes[k]) for k in outputs}
+        self._check(lib().az_threat_batch(self.h, count, _p(boards), _p(players), int(max_depth), int(node_budget),
+                                          *[_p(out.get(k)) for k in ("status", "move", "depth", "nodes", "edges")]), "az_threat_batch")
+        return out
+
+    def threats(self):
+        """int8 depth of the threat search's win at every record's root of the last episode, 0 = none, in the order of
+        records() (az_selfplay_threats)."""
+        v = np.zeros(self.last_records, np.int8)
+        self._check(lib().az_selfplay_threats(self.h, _p(v)), "az_selfplay_threats")
+        return v
+
+    def threat_stats(self):
+        """dict(win_roots, lost_roots, block_roots, exhausted, nodes) of the last (or open) episode or search call (az_threat_stats)."""
+        v = [C.c_int64(0) for _ in range(5)]
+        self._check(lib().az_threat_stats(self.h, *[C.byref(x) for x in v]), "az_threat_stats")
+        return dict(zip(("win_roots", "lost_roots", "block_roots", "exhausted", "nodes"), (int(x.value) for x in v)))
 
     # ---- Gumbel root search ----
     def set_gumbel(self, m, c_visit=50.0, c_scale=1.0):

@@ -61,6 +61,7 @@ struct Lane {
     DevBuf budget, cp_board, cp_state;     // per slot, playout cap: the ply's simulation budget, and the staging of k_refill's partition
     DevBuf root_logits, root_v;            // per slot, az_set_gumbel: the root's logits row and value of the running ply (allocated by the setter)
     DevBuf proof, root_proof, proof_stops; // per slot, az_set_solver: the status of every edge and of the root, the stops on proven edges (allocated by the setter)
+    DevBuf threat_edges, threat_root, threat_depth, threat_move, threat_nodes, threat_stat;   // per slot, the root threat search (allocated on first use)
     // one ply (k_begin, (S+1) x {trunk, fc, step}, k_move) captured once as a hipGraph and replayed every ply:
     // 3(S+1)+2 launches (6(S+1)+2 with the split trunk) become one submission.  Indexed [split trunk][arena].
     struct PlyGraph {
@@ -153,6 +154,11 @@ struct az_engine {
     int episode_solver = 0;        // ... and whether the last (or open) episode ran with it: az_selfplay_proofs speaks of that one
     DevBuf rec_proof;
     std::vector<int8_t> proof_edges, proof_roots;
+    // az_set_threat_search: max_depth = 0 = off; the depth of every record's root; the sums of the last (or open) episode / search call
+    int threat_depth = 0, threat_budget = 0;
+    int episode_threat = 0;        // whether the last (or open) episode ran with it: az_selfplay_threats speaks of that one
+    DevBuf rec_threat;
+    int64_t threat_stats[THREAT_STATS] = {0, 0, 0, 0, 0};
     PackedNet net[2];
     az_counters last{};
     // running episode (az_selfplay_begin .. az_selfplay_end)
@@ -886,7 +892,8 @@ extern "C" void az_destroy(az_engine *e)
         DevBuf *all[] = {&L.board, &L.s_game, &L.s_ply, &L.s_player, &L.s_last, &L.s_status, &L.s_net, &L.edges, &L.rows_used,
                          &L.path, &L.depth, &L.leaf_kind, &L.leaf, &L.leaf_last, &L.logits, &L.vhid, &L.pol_feat, &L.cnt,
                          &L.active_dev, &L.carried, &L.dbg, &L.scratch, &L.it_status, &L.it_net, &L.leaf_sym, &L.inflight,
-                         &L.budget, &L.cp_board, &L.cp_state, &L.root_logits, &L.root_v, &L.proof, &L.root_proof, &L.proof_stops};
+                         &L.budget, &L.cp_board, &L.cp_state, &L.root_logits, &L.root_v, &L.proof, &L.root_proof, &L.proof_stops,
+                         &L.threat_edges, &L.threat_root, &L.threat_depth, &L.threat_move, &L.threat_nodes, &L.threat_stat};
         for (DevBuf *b : all) dev_free(*b);
         for (hipEvent_t ev : L.ev) (void)hipEventDestroy(ev);
         for (int i = 0; i < 4; i++)
@@ -895,7 +902,7 @@ extern "C" void az_destroy(az_engine *e)
     DevBuf *shared[] = {&e->T_table, &e->log_table, &e->sqrt_table, &e->noise_off, &e->next_game, &e->noise, &e->u,
                         &e->rec_planes, &e->rec_last, &e->rec_action, &e->rec_mover, &e->rec_pi, &e->rec_visits, &e->g_nply,
                         &e->g_result, &e->src_index, &e->rec_value, &e->g_cross, &e->cache, &e->start_tab, &e->bt_cells, &e->bt_players, &e->bt_lasts, &e->bt_T,
-                        &e->bt_zero_off, &e->bt_visits, &e->bt_W, &e->bt_prior, &e->bt_pi, &e->bt_action, &e->ext.map, &e->ext.count, &e->gumbel_seq, &e->rec_proof,
+                        &e->bt_zero_off, &e->bt_visits, &e->bt_W, &e->bt_prior, &e->bt_pi, &e->bt_action, &e->ext.map, &e->ext.count, &e->gumbel_seq, &e->rec_proof, &e->rec_threat,
                         &e->cb_planes, &e->cb_policy, &e->cb_value};
     for (DevBuf *b : shared) dev_free(*b);
     for (int s = 0; s < 2; s++) {
@@ -1054,6 +1061,7 @@ static int ensure_episode_buffers(az_engine *e, int games, bool need_noise)
     ALLOC(g_nply, G * 4, true); ALLOC(g_result, G * 4, true);
     ALLOC(rec_value, G * nn * 4, false); ALLOC(g_cross, G * 4, false);
     if (e->solver) ALLOC(rec_proof, G * nn, false);
+    if (e->threat_depth) ALLOC(rec_threat, G * nn, false);
     if (!rc) HIPCHECK(e, hipMemsetAsync(e->g_cross.p, 0xFF, G * 4, e->stream));      // -1: no game has crossed
     ALLOC(u, G * nn * sizeof(double), false);
     if (need_noise) ALLOC(noise, G * (size_t)e->tape_len * sizeof(double), false);
@@ -1106,6 +1114,36 @@ static int lane_fail(Lane &L, int code, const char *fmt, ...)
             return lane_fail(L, AZ_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_r), __FILE__, __LINE__); \
     } while (0)
 
+// the threat search's view of a lane's buffers (L = nullptr: the option is off, every pointer null)
+static void set_threat_state(DevState &d, const Lane *L, int max_depth, int budget)
+{
+    d.threat_edges = L ? (unsigned char *)L->threat_edges.p : nullptr;
+    d.threat_root = L ? (signed char *)L->threat_root.p : nullptr;
+    d.threat_depth = L ? (signed char *)L->threat_depth.p : nullptr;
+    d.threat_move = L ? (short *)L->threat_move.p : nullptr;
+    d.threat_nodes = L ? (int *)L->threat_nodes.p : nullptr;
+    d.threat_stat = L ? (unsigned long long *)L->threat_stat.p : nullptr;
+    d.threat_max_depth = L ? max_depth : 0;
+    d.threat_budget = L ? budget : 0;
+}
+
+static int ensure_threat_buffers(az_engine *e)
+{
+    int rc = AZ_OK;
+    for (Lane &L : e->lanes) {
+        const size_t B = (size_t)L.d.B;
+        if (!rc && !L.threat_edges.p) rc = dev_alloc(e, L.threat_edges, B * (size_t)e->RW);
+        if (!rc && !L.threat_root.p) rc = dev_alloc(e, L.threat_root, B);
+        if (!rc && !L.threat_depth.p) rc = dev_alloc(e, L.threat_depth, B);
+        if (!rc && !L.threat_move.p) rc = dev_alloc(e, L.threat_move, B * 2);
+        if (!rc && !L.threat_nodes.p) rc = dev_alloc(e, L.threat_nodes, B * 4);
+        if (!rc && !L.threat_stat.p) rc = dev_alloc(e, L.threat_stat, B * THREAT_STATS * sizeof(unsigned long long));
+    }
+    if (rc) return rc;
+    HIPCHECK(e, hipStreamSynchronize(e->stream));
+    return AZ_OK;
+}
+
 static int episode_begin(az_engine *e, const EpisodeSpec &sp)
 {
     const bool ext = e->ext.on;            // the evaluator is outside the engine: no weights, no cache, priors as given
@@ -1123,7 +1161,10 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
         if (rc) return rc;
         e->ext.requests = e->ext.items = 0;
     }
+    // the root threat search is for every search the solver serves; its buffers were allocated by az_set_threat_search
+    for (Lane &L : e->lanes) set_threat_state(L.d, e->threat_depth ? &L : nullptr, e->threat_depth, e->threat_budget);
     each_state(e, [&](DevState &d) {
+        d.rec_threat = e->threat_depth ? (signed char *)e->rec_threat.p : nullptr;
         d.max_plies = sp.max_plies; d.add_noise = sp.add_noise ? 1 : 0; d.arena = sp.arena ? 1 : 0;
         d.total_games = sp.num_games; d.reuse = e->reuse; d.game_key0 = sp.game_key0;
         d.cache = ext ? nullptr : (float *)e->cache.p; d.cache_mask = e->cache_mask; d.cache_gen = e->cache_gen;
@@ -1154,11 +1195,13 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
     });
     e->episode_solver = e->solver;
     e->solver_stops = 0;
+    e->episode_threat = e->threat_depth;
+    for (int64_t &x : e->threat_stats) x = 0;
     if (!sp.preset) { e->proof_edges.clear(); e->proof_roots.clear(); }     // az_last_proof speaks of the last preset search only
     const bool capped = !sp.preset && !sp.arena && e->cap_fast > 0;
     // persistent search kernel: plain net or synthetic evaluator, the reference's sequential search, trees that fit into LDS
     e->persist_gp = 0;
-    if (e->persist_allowed && !ext && !e->vl_kernel && !capped && e->trunk_mode == AZ_TRUNK_F32) {
+    if (e->persist_allowed && !ext && !e->vl_kernel && !capped && !e->threat_depth && e->trunk_mode == AZ_TRUNK_F32) {
         const int synth = e->cfg.eval_kind == AZ_EVAL_SYNTHETIC ? 1 : 0;
         const int S = e->cfg.num_simulations;
         if (!sp.arena && (!sp.preset || sp.batch) && e->ops->search_prepare(S, 2, synth, e->cfg.model, e->solver)) e->persist_gp = 2;
@@ -1189,6 +1232,7 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
         L.trunk_ms = L.nn_ms = L.step_ms = 0.0; L.tape_wait_s = 0.0; L.rc = AZ_OK; L.err.clear();
         HIPCHECK(e, hipMemsetAsync(L.cnt.p, 0, L.cnt.bytes, L.stream));
         if (e->solver) HIPCHECK(e, hipMemsetAsync(L.proof_stops.p, 0, L.proof_stops.bytes, L.stream));
+        if (e->threat_depth) HIPCHECK(e, hipMemsetAsync(L.threat_stat.p, 0, L.threat_stat.bytes, L.stream));
         HIPCHECK(e, hipMemsetAsync(L.carried.p, 0xFF, L.carried.bytes, L.stream));      // -1: every slot starts from a fresh root
         if (!sp.preset) {
             HIPCHECK(e, hipMemsetAsync(L.s_status.p, 0, L.s_status.bytes, L.stream));
@@ -1245,6 +1289,7 @@ static hipError_t launch_ply(az_engine *e, const LaunchCtx &lc, bool use_split, 
     hipError_t rc = hipSuccess;
     auto record = [&](int i) { if (ev) rc = hipEventRecord(ev[i], lc.stream); return rc == hipSuccess; };
     hipLaunchKernelGGL(k_begin, dim3((d.B + 255) / 256), dim3(256), 0, lc.stream, d);
+    if (d.threat_edges) e->ops->threat(lc);     // the root threat search premarks the root statuses before the root expansion
     if (e->persist_gp) {               // small boards: the whole search of the ply in one persistent kernel (az_search.h)
         if (!record(0)) return rc;
         e->ops->search(lc, e->persist_gp);
@@ -1590,6 +1635,14 @@ static int read_counters(az_engine *e, az_counters &c)
         if (L.tape_wait_s > tape_wait) tape_wait = L.tape_wait_s;
     }
     e->solver_stops = stops;
+    if (e->episode_threat) {
+        for (int64_t &x : e->threat_stats) x = 0;
+        for (Lane &L : e->lanes) {
+            std::vector<unsigned long long> ht((size_t)L.d.B * THREAT_STATS);
+            HIPCHECK(e, az_memcpy(L.stream, ht.data(), L.threat_stat.p, ht.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < ht.size(); i++) e->threat_stats[i % THREAT_STATS] += (int64_t)ht[i];
+        }
+    }
     c.tape_wait_seconds = tape_wait;
     c.tape_threads = e->tapes || e->stream_tapes ? e->tape_threads : 0;
     c.host_cpus = e->host_cpus;
@@ -2257,6 +2310,7 @@ extern "C" int az_set_solver(az_engine *e, int on)
     if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_solver: an episode is open (az_selfplay_end first)");
     if (on != 0 && on != 1) return fail(e, AZ_ERR_INVALID, "az_set_solver: on %d (0 / 1)", on);
     if (!on) {
+        if (e->threat_depth) return fail(e, AZ_ERR_INVALID, "az_set_solver: the threat search is on and needs the solver (az_set_threat_search(e, 0, 0) first)");
         e->solver = 0;
         e->proof_edges.clear(); e->proof_roots.clear();
         return AZ_OK;
@@ -2428,6 +2482,7 @@ static int preset_search(az_engine *e, bool batch, int slot, int count, const ui
     az_counters total{};
     int64_t ext_requests = 0, ext_items = 0;       // az_ext_stats reports the whole call, like the counters
     int64_t batch_stops = 0;                       // ... and so does az_solver_stops
+    int64_t batch_threat[THREAT_STATS] = {0, 0, 0, 0, 0};     // ... and az_threat_stats
     std::vector<double> hu(wn);
     for (int w0 = 0; w0 < count; w0 += Wv) {
         const int m = std::min(Wv, count - w0);
@@ -2477,6 +2532,7 @@ static int preset_search(az_engine *e, bool batch, int slot, int count, const ui
         if ((rc = run_episode(e, sp, &c))) return rc;
         add_counters(total, c);
         batch_stops += e->solver_stops;
+        for (int i = 0; i < THREAT_STATS; i++) batch_threat[i] += e->threat_stats[i];
         ext_requests += e->ext.requests; ext_items += e->ext.items;
         // the lanes' streams are drained: every slot's root row and record into the compact staging, one copy per output
         e->ops->gather_roots(e->stream, bl, e->lanes[0].d, (const unsigned char *)e->bt_cells.p, visits ? (int *)e->bt_visits.p : nullptr, W ? (double *)e->bt_W.p : nullptr,
@@ -2500,6 +2556,7 @@ static int preset_search(az_engine *e, bool batch, int slot, int count, const ui
     }
     e->last = total;
     e->solver_stops = batch_stops;
+    for (int i = 0; i < THREAT_STATS; i++) e->threat_stats[i] = batch_threat[i];
     if (e->ext.on) { e->ext.requests = ext_requests; e->ext.items = ext_items; }
     return AZ_OK;
 }
@@ -2663,6 +2720,190 @@ extern "C" int az_set_start_positions(az_engine *e, int count, const uint8_t *bo
 }
 
 extern "C" int az_get_start_positions(const az_engine *e) { return e ? e->start_count : AZ_ERR_INVALID; }
+
+// ---- root threat search: forced-four wins and forced blocks, proven exactly (csrc/az_threat.h) ----
+static_assert(AZ_THREAT_MAX_DEPTH == THREAT_MAX_DEPTH, "the kernel's stack holds the C-ABI's depth");
+
+extern "C" int az_set_threat_search(az_engine *e, int max_depth, int node_budget)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_threat_search: an episode is open (az_selfplay_end first)");
+    if (max_depth == 0) {
+        e->threat_depth = e->threat_budget = 0;
+        return AZ_OK;
+    }
+    if (max_depth < 1 || max_depth > AZ_THREAT_MAX_DEPTH || node_budget < 1 || node_budget > 65535)
+        return fail(e, AZ_ERR_INVALID, "az_set_threat_search: max_depth %d (0 = off, 1 .. %d), node_budget %d (1 .. 65535)", max_depth,
+                    AZ_THREAT_MAX_DEPTH, node_budget);
+    if (!e->solver) return fail(e, AZ_ERR_INVALID, "az_set_threat_search: the threat search hands its results to the solver (az_set_solver(e, 1) first)");
+    DEVICE_GUARD(e);
+    const int rc = ensure_threat_buffers(e);
+    if (rc) return rc;
+    e->threat_depth = max_depth;
+    e->threat_budget = node_budget;
+    return AZ_OK;
+}
+
+extern "C" int az_get_threat_search(const az_engine *e, int *max_depth, int *node_budget)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (max_depth) *max_depth = e->threat_depth;
+    if (node_budget) *node_budget = e->threat_budget;
+    return AZ_OK;
+}
+
+extern "C" int az_threat_solve(const uint8_t *board, int n, int k, int rule, int player, int max_depth, int node_budget,
+                               int32_t *move, int32_t *depth, int32_t *nodes, int8_t *edges)
+{
+    if (!board || n < 1 || n > 15 || k < 1 || k > n || (rule != AZ_RULE_FREESTYLE && rule != AZ_RULE_EXACT) || (player != 1 && player != 2) ||
+        max_depth < 1 || max_depth > AZ_THREAT_MAX_DEPTH || node_budget < 1 || node_budget > 65535)
+        return AZ_ERR_INVALID;
+    int stones = 0;
+    for (int j = 0; j < n * n; j++) {
+        if (board[j] > 2) return AZ_ERR_INVALID;
+        stones += board[j] != 0;
+    }
+    if (stones >= n * n || az_rules_winner(board, n, k, rule) != AZ_RES_NONE) return AZ_ERR_INVALID;     // no legal action, or already won
+    int mv = -1, dp = 0, nd = 0;
+    const int root = threat_solve_host(board, n, k, rule, player, max_depth, node_budget, &mv, &dp, &nd, (signed char *)edges);
+    if (move) *move = mv;
+    if (depth) *depth = dp;
+    if (nodes) *nodes = nd;
+    return root;
+}
+
+extern "C" int az_threat_batch(az_engine *e, int count, const uint8_t *boards, const uint8_t *players, int max_depth, int node_budget,
+                               int8_t *status, int32_t *move, int32_t *depth, int32_t *nodes, int8_t *edges)
+{
+    if (!e || count < 0) return fail(e, AZ_ERR_INVALID, "az_threat_batch: bad argument");
+    if (max_depth < 1 || max_depth > AZ_THREAT_MAX_DEPTH || node_budget < 1 || node_budget > 65535)
+        return fail(e, AZ_ERR_INVALID, "az_threat_batch: max_depth %d (1 .. %d), node_budget %d (1 .. 65535)", max_depth, AZ_THREAT_MAX_DEPTH, node_budget);
+    if (count == 0) return AZ_OK;
+    if (!boards || !players) return fail(e, AZ_ERR_INVALID, "az_threat_batch: null argument");
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_threat_batch: a self-play episode is open on this engine");
+    const int nn = e->nn, K = (int)e->lanes.size();
+    if (K > BATCH_MAX_LANES) return fail(e, AZ_ERR_INVALID, "az_threat_batch: more than %d lanes", BATCH_MAX_LANES);
+    // every position is checked on the host before any GPU work: an error leaves every output untouched
+    for (int i = 0; i < count; i++) {
+        char who[48];
+        snprintf(who, sizeof who, "az_threat_batch: position %d", i);
+        const uint8_t *bd = boards + (size_t)i * nn;
+        if (check_position(e, who, bd, players[i], -1, nullptr)) return AZ_ERR_INVALID;
+        if (has_line(bd, e->n, e->cfg.win_length, e->win_rule))
+            return fail(e, AZ_ERR_INVALID, "az_threat_batch: position %d: already won (a line of %s%d under the %s rule)", i,
+                        e->win_rule == AZ_RULE_EXACT ? "exactly " : "", e->cfg.win_length, win_rule_name(e->win_rule));
+    }
+    DEVICE_GUARD(e);
+    const int Wv = std::min(count, e->cfg.slots);
+    int rc = ensure_threat_buffers(e);
+    if (!rc) rc = dev_alloc(e, e->bt_cells, (size_t)Wv * nn, false);
+    if (!rc) rc = dev_alloc(e, e->bt_players, (size_t)Wv, false);
+    if (!rc) rc = dev_alloc(e, e->bt_lasts, (size_t)Wv * 2, false);
+    if (rc) return rc;
+    struct Idle {          // the slots go back idle on every way out
+        az_engine *e;
+        ~Idle()
+        {
+            for (Lane &L : e->lanes) { (void)hipMemsetAsync(L.s_status.p, 0, L.s_status.bytes, e->stream); L.preset_m = 0; }
+            (void)hipStreamSynchronize(e->stream);
+        }
+    } idle{e};
+    const std::vector<int16_t> no_last((size_t)Wv, (int16_t)-1);
+    HIPCHECK(e, hipMemcpyAsync(e->bt_lasts.p, no_last.data(), (size_t)Wv * 2, hipMemcpyHostToDevice, e->stream));
+    std::vector<int8_t> h8;
+    std::vector<int16_t> h16;
+    for (int w0 = 0; w0 < count; w0 += Wv) {
+        const int m = std::min(Wv, count - w0);
+        // the wave's positions over the lanes, as az_search_batch spreads them
+        BatchLanes bl{};
+        bl.K = K; bl.L = e->lanes[0].d.L;
+        int left = m;
+        for (int l = 0; l < K; l++) {
+            Lane &L = e->lanes[l];
+            L.preset_m = std::min(L.d.B, (left + (K - l) - 1) / (K - l));
+            left -= L.preset_m;
+        }
+        for (int l = 0; l < K && left > 0; l++) {
+            Lane &L = e->lanes[l];
+            const int add = std::min(L.d.B - L.preset_m, left);
+            L.preset_m += add; left -= add;
+        }
+        int first = 0;
+        for (int l = 0; l < K; l++) {
+            const Lane &L = e->lanes[l];
+            BatchLane &b = bl.lane[l];
+            b.board = L.d.board; b.s_game = L.d.s_game; b.s_ply = L.d.s_ply; b.s_player = L.d.s_player; b.s_last = L.d.s_last;
+            b.s_status = L.d.s_status; b.leaf_kind = L.d.leaf_kind; b.carried = L.d.carried; b.edges = L.d.edges;
+            b.B = L.d.B; b.first = first; b.m = L.preset_m;
+            first += L.preset_m;
+        }
+        HIPCHECK(e, hipMemcpyAsync(e->bt_cells.p, boards + (size_t)w0 * nn, (size_t)m * nn, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(e->bt_players.p, players + w0, (size_t)m, hipMemcpyHostToDevice, e->stream));
+        e->ops->set_positions(e->stream, bl, (const unsigned char *)e->bt_cells.p, (const unsigned char *)e->bt_players.p,
+                              (const short *)e->bt_lasts.p);
+        for (Lane &L : e->lanes) {
+            if (L.preset_m == 0) continue;
+            LaunchCtx lc = ctx_of_impl(e, L);
+            lc.stream = e->stream;
+            set_threat_state(lc.d, &L, max_depth, node_budget);
+            lc.d.rule = e->win_rule;
+            lc.d.B = L.preset_m;
+            e->ops->threat(lc);
+        }
+        HIPCHECK(e, hipStreamSynchronize(e->stream));
+        HIPCHECK(e, hipGetLastError());
+        first = 0;
+        for (Lane &L : e->lanes) {
+            const size_t pm = (size_t)L.preset_m, at = (size_t)(w0 + first);
+            first += L.preset_m;
+            if (pm == 0) continue;
+            if (status) HIPCHECK(e, az_memcpy(e->stream, status + at, L.threat_root.p, pm, hipMemcpyDeviceToHost));
+            if (depth) {
+                h8.resize(pm);
+                HIPCHECK(e, az_memcpy(e->stream, h8.data(), L.threat_depth.p, pm, hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < pm; i++) depth[at + i] = h8[i];
+            }
+            if (move) {
+                h16.resize(pm);
+                HIPCHECK(e, az_memcpy(e->stream, h16.data(), L.threat_move.p, pm * 2, hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < pm; i++) move[at + i] = h16[i];
+            }
+            if (nodes) HIPCHECK(e, az_memcpy(e->stream, nodes + at, L.threat_nodes.p, pm * 4, hipMemcpyDeviceToHost));
+            if (edges) HIPCHECK(e, az_memcpy2d(e->stream, edges + at * nn, (size_t)nn, L.threat_edges.p, (size_t)e->RW, (size_t)nn, pm, hipMemcpyDeviceToHost));
+        }
+    }
+    return AZ_OK;
+}
+
+extern "C" int az_selfplay_threats(az_engine *e, int8_t *depth)
+{
+    if (!e || !e->have_episode) return fail(e, AZ_ERR_STATE, "no episode has been run");
+    if (!depth) return fail(e, AZ_ERR_INVALID, "az_selfplay_threats: null buffer");
+    if (!e->episode_threat || !e->rec_threat.p) return fail(e, AZ_ERR_STATE, "az_selfplay_threats: the episode ran without the threat search");
+    DEVICE_GUARD(e);
+    const int nn = e->nn, G = e->episode_games;
+    std::vector<int8_t> val((size_t)G * nn);
+    HIPCHECK(e, az_memcpy(e->stream, val.data(), e->rec_threat.p, val.size(), hipMemcpyDeviceToHost));
+    size_t r = 0;
+    for (int g = 0; g < G; g++)
+        for (int m = 0; m < e->h_nply[g]; m++) depth[r++] = val[(size_t)g * nn + e->h_start[g] + m];
+    return AZ_OK;
+}
+
+extern "C" int az_threat_stats(az_engine *e, int64_t *win_roots, int64_t *lost_roots, int64_t *block_roots, int64_t *exhausted, int64_t *nodes)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (e->run.open && e->episode_threat) {       // the open episode so far
+        DEVICE_GUARD(e);
+        az_counters c = e->run.c;
+        const int rc = read_counters(e, c);
+        if (rc) return rc;
+    }
+    int64_t *out[THREAT_STATS] = {win_roots, lost_roots, block_roots, exhausted, nodes};
+    for (int i = 0; i < THREAT_STATS; i++)
+        if (out[i]) *out[i] = e->threat_stats[i];
+    return AZ_OK;
+}
 
 extern "C" int az_arena(az_engine *e, const az_arena_args *a, az_arena_result *out, int32_t *results, int16_t *actions,
                         int32_t *nply)

@@ -246,11 +246,16 @@ void ext_scatter(const LaunchCtx &c, int item_base, int count, const int *map, c
     dim3 g((count + 3) / 4), b(256);
     hipLaunchKernelGGL(k_ext_scatter<N>, g, b, 0, c.stream, c.dv, item_base, count, map, policy, value);
 }
+
+void threat(const LaunchCtx &c)
+{
+    hipLaunchKernelGGL(k_threat<N>, dim3(c.d.B), dim3(64), 0, c.stream, c.d);
+}
 }   // namespace
 
 const SizeOps *AZ_CAT(az_size_ops_, AZ_N)()
 {
     static const SizeOps ops = {trunk, trunk_split, split_scratch_floats, fc, step, step_vl, root_cache, search_prepare, search, move, eval_tail_l,
-                                set_positions, gather_roots, build_positions, ext_gather, ext_scatter};
+                                set_positions, gather_roots, build_positions, ext_gather, ext_scatter, threat};
     return &ops;
 }

@@ -6,6 +6,7 @@
 #include "az_search.h"
 #include "az_batch.h"
 #include "az_ext.h"
+#include "az_threat.h"
 
 struct LaunchCtx {
     hipStream_t stream;
@@ -49,6 +50,8 @@ struct SizeOps {
     // to the request (first: a new request), and the evaluator's priors and values of `count` entries back into their rows
     void (*ext_gather)(const LaunchCtx &, int net, int item_base, int first, int capacity, float *planes, int *map, int *count);
     void (*ext_scatter)(const LaunchCtx &, int item_base, int count, const int *map, const float *policy, const float *value);
+    // az_set_threat_search / az_threat_batch (az_threat.h): the root threat search of the first d.B slots, one wavefront each
+    void (*threat)(const LaunchCtx &);
 };
 
 const SizeOps *az_size_ops(int n);     // nullptr for unsupported sizes

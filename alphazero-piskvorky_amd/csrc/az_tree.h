@@ -134,6 +134,16 @@ struct DevState {
     signed char *root_proof;   // [B] status of the root of the running ply, seen from its side to move
     signed char *rec_proof;    // [G*nn] ... and of every record's root, written by k_move
     unsigned long long *proof_stops;   // [B] simulations that ended on a proven edge (a terminal hit in cnt as well)
+    // --- opt-in root threat search (az_set_threat_search, csrc/az_threat.h): threat_edges = nullptr with the option off, nothing below
+    // is read, written or executed then.  k_threat writes them for the slot's ply before the root expansion ---
+    unsigned char *threat_edges;   // [B][RW] premarked status of every root edge: the SOLVER k_step copies the row in at root expansion
+    signed char *threat_root;      // [B] ... and of the root itself
+    signed char *threat_depth;     // [B] depth of the win found, 0 = none
+    short *threat_move;            // [B] its first move, -1 = none
+    int *threat_nodes;             // [B] fours tried; > threat_budget = the search of this root was exhausted
+    unsigned long long *threat_stat;   // [B][THREAT_STATS] roots proven WIN / LOSS, block-only roots, exhausted searches, nodes
+    signed char *rec_threat;       // [G*nn] threat_depth of every record's root, written by k_move
+    int threat_max_depth, threat_budget;
 };
 __device__ __forceinline__ int game_key(const DevState &d, int game) { return (int)(d.game_key0 + d.key_stride * (unsigned)game); }
 // az_set_playout_cap's rule, a function of the game's global name and the absolute ply only (the host's az_playout_cap_full)
@@ -672,6 +682,13 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
 #pragma unroll
                 for (int i = 0; i < G::CPL; i++) prow[lane + 64 * i] = PROOF_UNKNOWN;
                 if (kind == LEAF_ROOT && lane == 0) d.root_proof[b] = PROOF_UNKNOWN;
+                // az_set_threat_search: a root starts from the statuses the threat search premarked (a test of the pointer, the root only)
+                if (kind == LEAF_ROOT && d.threat_edges) {
+                    const unsigned char *pre = d.threat_edges + (size_t)b * G::RW;
+#pragma unroll
+                    for (int i = 0; i < G::CPL; i++) prow[lane + 64 * i] = pre[lane + 64 * i];
+                    if (lane == 0) d.root_proof[b] = d.threat_root[b];
+                }
             }
             if (lane == 0) d.rows_used[b] = row + 1;
             if (kind == LEAF_EXPAND) {
@@ -1457,6 +1474,7 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
         d.s_ply[b] = ply + 1;
         d.rec_value[ri] = (float)v;
         if (d.proof) d.rec_proof[ri] = (signed char)rproof;
+        if (d.threat_edges) d.rec_threat[ri] = d.threat_depth[b];
         if (crossed && d.g_cross[g] < 0) d.g_cross[g] = ply;
         int res = win ? pl : (full ? 3 : 0);
         if (resign) res = 3 - pl;           // the mover resigns: on a crossing ply this is the result, max_plies or not

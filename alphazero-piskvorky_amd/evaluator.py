@@ -7,7 +7,7 @@ import torch
 
 from . import constants as _c
 from . import parallel
-from ._capi import AZ_MAX_SIMULATIONS, Engine, win_rule_name
+from ._capi import AZ_MAX_SIMULATIONS, Engine, check_threat_search, win_rule_name
 from .controller import device_index, make_batch_policy_value_fn, merge_batch_evaluators, model_kind
 from .mcts import check_solver, numpy_log_table
 from .self_play import check_resign
@@ -19,7 +19,8 @@ def temperature_schedule(move: int) -> float:
 
 class ModelEvaluator:
     def __init__(self, game_class=None, print_games=False, device=None, seed=None, virtual_loss=1, eval_cache=0,
-                 start_positions=None, resign: dict = None, evaluators=None, solver: bool = False, win_rule: str = None):
+                 start_positions=None, resign: dict = None, evaluators=None, solver: bool = False, win_rule: str = None,
+                 threat_search: dict = None):
         self.game_class = game_class
         # which game the arena plays: "freestyle" (constants.WIN_RULE's default) or "exact" (standard Gomoku; az_set_win_rule)
         self.win_rule = win_rule_name(_c.WIN_RULE if win_rule is None else win_rule)
@@ -40,6 +41,9 @@ class ModelEvaluator:
         self.resign = check_resign(resign)
         # opt-in MCTS-Solver in both sides' searches (az_set_solver).  Not with virtual_loss > 1 or outside evaluators.
         self.solver = check_solver(solver, virtual_loss=virtual_loss, evaluator=self.evaluators)
+        # opt-in root threat search in both sides' searches, dict(max_depth=8, node_budget=256) or True (az_set_threat_search).
+        # Needs solver=True.
+        self.threat_search = check_threat_search(threat_search, self.solver)
         self._engine = None
 
     def evaluate(self, candidate_controller, baseline_controller, num_games=20, debug=False):
@@ -90,8 +94,13 @@ class ModelEvaluator:
         elif eng.resign()["threshold"]:
             eng.set_resign(0.0)
         self.solver = check_solver(self.solver, virtual_loss=self.virtual_loss, evaluator=self.evaluators)
+        self.threat_search = check_threat_search(self.threat_search, self.solver)
+        if self.threat_search is None and eng.threat_search()[0]:
+            eng.set_threat_search(0)                      # before the solver it needs may go
         if self.solver != eng.solver():
             eng.set_solver(self.solver)
+        if self.threat_search is not None:
+            eng.set_threat_search(**self.threat_search)
         r = eng.arena(mine, seed0=seed0 + lo, temperature_table=T) if mine > 0 else {"wins": 0, "losses": 0, "draws": 0, "total": 0, "win_rate": 0.0}
         if world > 1:
             w, l, d = parallel.all_reduce_tally(r["wins"], r["losses"], r["draws"], dev, engine=eng)

@@ -7,7 +7,7 @@ them to the engine, so np.random.seed(s) reproduces the reference's choices."""
 import numpy as np
 
 from . import constants as _c
-from ._capi import AZ_MAX_SIMULATIONS, FORCED_K_MAX, GUMBEL_DEFAULTS, GUMBEL_M_MAX, Engine, win_rule_name
+from ._capi import AZ_MAX_SIMULATIONS, FORCED_K_MAX, GUMBEL_DEFAULTS, GUMBEL_M_MAX, Engine, check_threat_search, win_rule_name
 from .controller import BatchPolicyValueFn, PolicyValueFn, device_index, model_kind, weights_version
 
 
@@ -76,7 +76,7 @@ def check_gumbel(gumbel, subtree_reuse=False, virtual_loss=1, forced_playouts=No
 
 class MCTS:
     def __init__(self, policy_value_fn, num_simulations, c_puct, dirichlet_alpha=0.3, dirichlet_weight=0.25, virtual_loss=1,
-                 forced_playouts=None, gumbel=None, solver=False):
+                 forced_playouts=None, gumbel=None, solver=False, threat_search=None):
         if not callable(policy_value_fn):
             raise TypeError("policy_value_fn must be callable: state -> (policy [n, n], value)")
         # make_policy_value_fn(controller): the leaves are evaluated inside the HIP engine.  Any other callable keeps the
@@ -103,6 +103,9 @@ class MCTS:
         # run()'s (edge statuses [n, n], root status), after run_many() one pair per state.  Controller-backed evaluators only.
         self.solver = check_solver(solver, virtual_loss=virtual_loss, forced_playouts=self.forced_playouts, gumbel=self.gumbel,
                                    evaluator=policy_value_fn if (self._external or self._batched) else None)
+        # opt-in: dict(max_depth=8, node_budget=256) or True, the root threat search in front of every search (az_set_threat_search):
+        # forced-four wins and forced blocks reach the solver as premarked root statuses.  Needs solver=True.
+        self.threat_search = check_threat_search(threat_search, self.solver)
         self.last_proof = None
         self._engine = None
         self._version = None
@@ -117,6 +120,8 @@ class MCTS:
             eng.set_gumbel(min(self.gumbel["m"], eng.nn), self.gumbel["c_visit"], self.gumbel["c_scale"])     # a board has n * n cells
         if self.solver:
             eng.set_solver(True)
+        if self.threat_search is not None:
+            eng.set_threat_search(**self.threat_search)
         return eng
 
     @staticmethod

@@ -7,7 +7,7 @@ import torch
 
 from . import constants as _c
 from . import parallel
-from ._capi import AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine, playout_cap_permille, resign_permille, win_rule_name
+from ._capi import check_threat_search, AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine, playout_cap_permille, resign_permille, win_rule_name
 from .controller import BatchPolicyValueFn, device_index, model_kind
 from .mcts import check_forced_playouts, check_gumbel, check_solver, numpy_log_table
 
@@ -115,7 +115,7 @@ class SelfPlayManager:
                  eval_cache: int = 0, virtual_loss: int = 1, trunk: str = "f32", leaf_symmetry: bool = False,
                  start_positions=None, resign: dict = None, evaluator: BatchPolicyValueFn = None,
                  playout_cap: dict = None, forced_playouts: dict = None, gumbel: dict = None, solver: bool = False,
-                 win_rule: str = None):
+                 win_rule: str = None, threat_search: dict = None):
         self.controller = controller
         # which game is played: "freestyle" (constants.WIN_RULE's default, the reference's: a run of WIN_LENGTH or more wins) or
         # "exact" (standard Gomoku: exactly WIN_LENGTH, an overline wins nothing; az_set_win_rule).  Combines with every option.
@@ -156,6 +156,10 @@ class SelfPlayManager:
         # virtual_loss > 1, forced_playouts, gumbel or an external evaluator.  Whether it trains a stronger net per GPU hour
         # has not been measured.
         self.solver = check_solver(solver, subtree_reuse, virtual_loss, self.forced_playouts, self.gumbel, evaluator)
+        # opt-in root threat search, dict(max_depth=8, node_budget=256) or True: an exact forced-four search on every root before
+        # the simulations, its proven wins and forced blocks premarked for the solver (az_set_threat_search).  Needs solver=True.
+        # Whether it trains a stronger net per GPU hour has not been measured.
+        self.threat_search = check_threat_search(threat_search, self.solver)
         self.temperature_schedule = temperature_schedule
         self.concurrent_games = concurrent_games or _c.CONCURRENT_GAMES
         self.augmentation = augmentation      # 4 = the reference's rotations (self_play.py:94-108), 8 = full dihedral group, 1 = none
@@ -285,8 +289,13 @@ class SelfPlayManager:
         elif eng.gumbel()["m"]:
             eng.set_gumbel(0)
         self.solver = check_solver(self.solver, self.subtree_reuse, self.virtual_loss, self.forced_playouts, self.gumbel, self.evaluator)
+        self.threat_search = check_threat_search(self.threat_search, self.solver)
+        if self.threat_search is None and eng.threat_search()[0]:
+            eng.set_threat_search(0)                      # before the solver it needs may go
         if self.solver != eng.solver():
             eng.set_solver(self.solver)
+        if self.threat_search is not None:
+            eng.set_threat_search(**self.threat_search)
         if mine > 0:
             self.last_counters = eng.selfplay(mine, seed0=seed0 + lo, temperature_table=T)
             if self.resign is not None:

@@ -28,7 +28,7 @@ PROMOTION_THRESHOLD = 0.55          # promoter.py:19, strict ">" with draws coun
 
 def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=None, log=print, device_replay=False,
         subtree_reuse=False, trunk="f32", eval_sims=None, start_positions=None, resign=None, torch_eval=False,
-        playout_cap=None, forced_playouts=None, gumbel=None, solver=False, win_rule=None):
+        playout_cap=None, forced_playouts=None, gumbel=None, solver=False, win_rule=None, threat_search=None):
     """eval_sims: simulations per move in the arena (evaluator.py:53-62 takes NUM_EVAL_SIMULATIONS = 200 whatever the
     self-play count is; main() passes that constant); None = as many as self-play, which keeps small test runs short.
     device_replay=True keeps the examples on the GPU from the episode-end gather to the optimizer step (packed records
@@ -50,6 +50,9 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
     solver=True: MCTS-Solver in the self-play searches (Engine.set_solver): proven wins, losses and draws are kept in the tree,
     the policy target leaves refuted moves out and a proven root records an exact value.  Not with forced_playouts, gumbel,
     subtree_reuse or torch_eval.  The arena is untouched.  Whether it trains a stronger net per GPU hour is not measured.
+    threat_search: dict(max_depth, node_budget) for the self-play searches (Engine.set_threat_search): an exact forced-four search
+    on every root before the simulations; its proven wins and forced blocks reach the solver as premarked root statuses.  Needs
+    solver=True.  The arena is untouched.  Whether it trains a stronger net per GPU hour is not measured.
     win_rule: "freestyle" (constants.WIN_RULE's default: a run of WIN_LENGTH or more wins) or "exact" (standard Gomoku: exactly
     WIN_LENGTH, overlines win nothing; Engine.set_win_rule).  It is the game itself, so self-play AND the arena play it, and it
     combines with every option.  Whether exact-rule self-play trains a stronger standard-rule net is not measured.
@@ -67,7 +70,7 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
     manager = SelfPlayManager(candidate, device, mcts_params={"num_simulations": sims, "c_puct": C.SELF_PLAY_EXPLORATION_CONSTANT},
                               seed=seed, subtree_reuse=subtree_reuse, gather_to=0 if world > 1 else None, trunk=trunk,
                               start_positions=start_positions, resign=resign, playout_cap=playout_cap,
-                              forced_playouts=forced_playouts, gumbel=gumbel, solver=solver, win_rule=win_rule,
+                              forced_playouts=forced_playouts, gumbel=gumbel, solver=solver, win_rule=win_rule, threat_search=threat_search,
                               evaluator=make_batch_policy_value_fn(candidate.net, device) if torch_eval else None)
     evaluator = ModelEvaluator(game_class=Gomoku, print_games=False, device=device, seed=seed,
                                evaluators=True if torch_eval else None, win_rule=win_rule)
@@ -167,6 +170,10 @@ def main():
     ap.add_argument("--solver", action="store_true",
                     help="MCTS-Solver in the self-play searches: proven wins, losses and draws are kept in the tree, the policy "
                          "target leaves refuted moves out and a proven root records an exact value")
+    ap.add_argument("--threat-depth", type=int, default=None, metavar="D",
+                    help="root threat search in the self-play searches: an exact forced-four search of depth D (1..16) on every root "
+                         "before the simulations, handed to the solver; implies --solver")
+    ap.add_argument("--threat-nodes", type=int, default=None, metavar="N", help="with --threat-depth: fours tried per root at most (default 256)")
     ap.add_argument("--win-rule", choices=("freestyle", "exact"), default=None,
                     help="the game that self-play and the arena play: freestyle (default; a run of WIN_LENGTH or more wins) or "
                          "exact (standard Gomoku: exactly WIN_LENGTH, an overline wins nothing)")
@@ -199,6 +206,14 @@ def main():
             gumbel["c_scale"] = a.gumbel_c_scale
     elif a.gumbel_c_visit is not None or a.gumbel_c_scale is not None:
         ap.error("--gumbel-c-visit and --gumbel-c-scale need --gumbel")
+    threat_search = None
+    if a.threat_depth is not None:
+        threat_search = {"max_depth": a.threat_depth}
+        if a.threat_nodes is not None:
+            threat_search["node_budget"] = a.threat_nodes
+        a.solver = True
+    elif a.threat_nodes is not None:
+        ap.error("--threat-nodes needs --threat-depth")
     start_positions = None
     if a.start_positions:
         with np.load(a.start_positions) as z:
@@ -215,7 +230,7 @@ def main():
     run(a.episodes, a.games, a.sims, a.eval_games, a.device, model_dir=a.model_dir, device_replay=a.device_replay,
         subtree_reuse=a.subtree_reuse, trunk=a.trunk, eval_sims=C.NUM_EVAL_SIMULATIONS, start_positions=start_positions,
         resign=resign, torch_eval=a.torch_eval, playout_cap=playout_cap, forced_playouts=forced_playouts,
-        gumbel=gumbel, solver=a.solver, win_rule=a.win_rule)
+        gumbel=gumbel, solver=a.solver, win_rule=a.win_rule, threat_search=threat_search)
     if world > 1:
         td.barrier()
         td.destroy_process_group()

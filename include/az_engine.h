@@ -721,6 +721,70 @@ int az_solver_stops(const az_engine *e, int64_t *stops);
 int az_selfplay_proofs(az_engine *e, int8_t *roots);
 int az_solver_counts(int count, const int32_t *visits, const int8_t *status, int32_t *out);
 
+/* Opt-in root threat search: forced-four wins ("victory by continuous fours", VCF) and forced blocks, proven exactly over the
+ * rules of the game by a kernel of its own (csrc/az_threat.h) on every root before the simulations, and handed to the solver as
+ * premarked root statuses.  The solver alone proves only what the search happens to reach; this widens it at the root.  Off by
+ * default, and with the option off nothing below is read, written or executed.
+ *
+ * Rule.  For a position P with side to move A and opponent D, win(P, c) is the set of empty cells where a stone of colour c
+ * wins at once under the win rule in force (az_set_win_rule).  Cells are taken in ascending row-major order.  T(P, d) returns
+ * (found, move, depth) and counts nodes in one counter shared by the whole search of a root:
+ *   1. Wa = win(P, A).  If it is non-empty: found, move = the lowest cell of Wa, depth 1.
+ *   2. If d <= 1: not found.
+ *   3. Wd = win(P, D).  If |Wd| >= 2: not found.  The candidates are the single cell of Wd if |Wd| == 1, otherwise every empty
+ *      cell.
+ *   4. For each candidate x in ascending order: P' = P + A at x, W = win(P', A).  If W is empty x is not a four: it is skipped
+ *      and counts no node.  Otherwise nodes += 1; if nodes > node_budget the whole search of this root ends "exhausted" and no
+ *      win is reported.  If win(P', D) is non-empty x is skipped (D wins instead of blocking).  If |W| >= 2: found, move x,
+ *      depth 2.  Otherwise let w be the single cell of W, P'' = P' + D at w and r = T(P'', d - 1); if r is found: found, move x,
+ *      depth r.depth + 1.
+ *   5. Not found.
+ * The depth is that of the line found, not necessarily the shortest.  The root search is T(root, max_depth).
+ * Root statuses, AZ_PROOF_* seen from the mover.  A win found at step 1: every cell of Wa is WIN and the root is WIN.  A win
+ * found deeper: the edge `move` is WIN and the root is WIN.  Otherwise, exhausted searches included, if Wd of the root is
+ * non-empty: every legal cell outside Wd is LOSS; with |Wd| >= 2 the cells of Wd are LOSS too and the root is LOSS; with
+ * |Wd| == 1 that cell stays UNKNOWN.  Everything else is UNKNOWN.  The root's Wd is computed before any node is counted, so
+ * these marks do not depend on the budget.
+ * Soundness.  A WIN of depth d means A wins within 2d - 1 plies against any defence; a LOSS edge means D completes a line on
+ * the next move.  Both hold under both win rules: a stone of the other colour on an empty cell never changes a maximal run
+ * of one's own stones.
+ *
+ * az_set_threat_search(e, max_depth, node_budget): max_depth = 0 is off (the default); otherwise 1 <= max_depth <=
+ * AZ_THREAT_MAX_DEPTH and 1 <= node_budget <= 65535.  It needs the solver: AZ_ERR_INVALID while az_get_solver(e) == 0, and
+ * az_set_solver(e, 0) while it is on is refused with AZ_ERR_INVALID (switch the threat search off first).  It inherits the
+ * solver's refused pairs and adds none.  With it on, every search the solver serves -- self-play, arena, az_search and
+ * az_search_batch, FULL and FAST plies alike -- runs the kernel over the active slots after the roots are set up and before the
+ * root expansion, and the root row and the root start from the premarked statuses instead of UNKNOWN.  From there on the
+ * solver's rule as written does the rest: a WIN edge scores +infinity, a descent onto a premarked WIN edge that is not a real
+ * terminal ends there (no evaluation, no row), pi is made from the WIN edges' counts, the record's value is exactly +1 / -1, a
+ * proven loss resigns by itself.  The root is still evaluated once.  While the option is on the persistent search kernel is
+ * never chosen (az_get_persistent == 0), as under the playout cap.  AZ_ERR_STATE while an episode is open; arguments out of range keep the
+ * previous setting.
+ * az_threat_batch(e, count, boards, players, max_depth, node_budget, status, move, depth, nodes, edges): the kernel on its
+ * own, for analysis and tests; it searches any number of positions in waves of the engine's slots and ignores the setter.
+ * status[count] = the root status, move[count] = the winning move or -1, depth[count] = the depth or 0, nodes[count] (the search
+ * was exhausted iff nodes > node_budget), edges[count][n*n] (0 on occupied cells).  Any output may be NULL; count = 0 returns
+ * AZ_OK.  Positions are checked on the host by az_search_batch's rules (without `last`) and must not already be won under the
+ * rule in force (az_set_start_positions' check): AZ_ERR_INVALID with the index of the first offender in az_last_error.
+ * AZ_ERR_STATE while an episode is open.
+ * az_threat_solve(board, n, k, rule, player, max_depth, node_budget, move, depth, nodes, edges): the same on the host for one
+ * position (no engine, no GPU, like az_rules_winner; 1 <= n <= 15, 1 <= k <= n).  Returns the root status, or AZ_ERR_INVALID
+ * for a bad argument, a full board or a position already won.  move, depth, nodes, edges may be NULL.
+ * az_selfplay_threats(e, depth): per record, in the order and count of az_selfplay_values, 0 = none, d = a win of depth d;
+ * AZ_ERR_STATE without an episode or when it ran without the option.
+ * az_threat_stats: over the last (or open) episode or the last az_search / az_search_batch call: roots proven WIN, roots proven
+ * LOSS, roots with a single forced block and no win, exhausted searches, and nodes; any pointer may be NULL; 0 with the option
+ * off. */
+#define AZ_THREAT_MAX_DEPTH 16
+int az_set_threat_search(az_engine *e, int max_depth, int node_budget);
+int az_get_threat_search(const az_engine *e, int *max_depth, int *node_budget);
+int az_threat_batch(az_engine *e, int count, const uint8_t *boards, const uint8_t *players, int max_depth, int node_budget,
+                    int8_t *status, int32_t *move, int32_t *depth, int32_t *nodes, int8_t *edges);
+int az_threat_solve(const uint8_t *board, int n, int k, int rule, int player, int max_depth, int node_budget,
+                    int32_t *move, int32_t *depth, int32_t *nodes, int8_t *edges);
+int az_selfplay_threats(az_engine *e, int8_t *depth);
+int az_threat_stats(az_engine *e, int64_t *win_roots, int64_t *lost_roots, int64_t *block_roots, int64_t *exhausted, int64_t *nodes);
+
 /* Opt-in: fp32-emulating conv trunks.  AZ_TRUNK_F32 (default) computes the net's forward (net.py:55-72) on the float32
  * matrix instruction in the build's canonical fp order: bit-identical to the oracle.  The other two run every conv but the
  * first (99 % of the net's arithmetic) and the 1x1 head convs on the 16 x faster 16-bit matrix instructions with split
