@@ -42,6 +42,7 @@ EXPORTS = [
     "az_set_solver", "az_get_solver", "az_last_proof", "az_selfplay_proofs", "az_solver_counts", "az_solver_stops",
     "az_set_win_rule", "az_get_win_rule", "az_rules_winner",
     "az_set_threat_search", "az_get_threat_search", "az_threat_batch", "az_threat_solve", "az_selfplay_threats", "az_threat_stats",
+    "az_set_delta_eval", "az_get_delta_eval", "az_delta_max_tiles", "az_delta_stats", "az_net_eval_delta", "az_delta_lists",
     "az_dist_unique_id", "az_dist_init", "az_dist_rank", "az_dist_world", "az_dist_counts", "az_dist_gather_records",
     "az_dist_allreduce_sum", "az_dist_broadcast",
 ]
@@ -198,6 +199,13 @@ def lib():
             L.az_threat_solve.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4
             L.az_selfplay_threats.argtypes = [C.c_void_p, C.c_void_p]
             L.az_threat_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 5
+        if hasattr(L, "az_set_delta_eval"):
+            L.az_set_delta_eval.argtypes = [C.c_void_p, C.c_int]
+            L.az_get_delta_eval.argtypes = [C.c_void_p]
+            L.az_delta_max_tiles.argtypes = [C.c_void_p, C.c_int]
+            L.az_delta_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 4 + [C.c_void_p]
+            L.az_net_eval_delta.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
+            L.az_delta_lists.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5
         _LIB = L
     return _LIB
 
@@ -520,6 +528,49 @@ class Engine:
         self._check(lib().az_net_eval(self.h, int(slot), cnt, _p(boards), _p(players), _p(lasts), _p(logits),
                                       _p(policy), _p(value)), "az_net_eval")
         return logits, policy, value
+
+    # ---- delta evaluation (include/az_engine.h) ----
+    def set_delta_eval(self, on):
+        """Leaves evaluated as deltas from the ply's root activations where the configuration is eligible (on by default);
+        results are bit-identical either way."""
+        self._check(lib().az_set_delta_eval(self.h, 1 if on else 0), "az_set_delta_eval")
+
+    def delta_eval(self):
+        return lib().az_get_delta_eval(self.h) == 1
+
+    def delta_max_tiles(self, tiles=0):
+        """Sets (1 .. 15) and returns the conv3 tile count above which a leaf is evaluated in full; 0 only asks."""
+        rc = lib().az_delta_max_tiles(self.h, int(tiles))
+        if rc < 0:
+            self._check(rc, "az_delta_max_tiles")
+        return int(rc)
+
+    def delta_stats(self, by_tiles=False):
+        """dict(delta, full, tiles, base) of the last (or open) episode or search call (az_delta_stats); by_tiles: also the
+        delta evaluations by conv3 tile count, 16 entries."""
+        v = [C.c_int64(0) for _ in range(4)]
+        h = np.zeros(16, np.int64)
+        self._check(lib().az_delta_stats(self.h, *[C.byref(x) for x in v], _p(h)), "az_delta_stats")
+        d = dict(zip(("delta", "full", "tiles", "base"), (int(x.value) for x in v)))
+        if by_tiles:
+            d["by_tiles"] = h.tolist()
+        return d
+
+    def net_eval_delta(self, root, root_player, boards, players, lasts, slot=0):
+        """The positions evaluated as deltas from one root position: (logits, policy, value, path) with path[i] = conv3 tiles
+        the delta path computed for position i, -1 = evaluated in full (az_net_eval_delta)."""
+        root = np.ascontiguousarray(root, np.uint8).reshape(self.nn)
+        boards = np.ascontiguousarray(boards, np.uint8).reshape(-1, self.nn)
+        cnt = boards.shape[0]
+        players = np.ascontiguousarray(players, np.uint8).reshape(cnt)
+        lasts = np.ascontiguousarray(lasts, np.int16).reshape(cnt)
+        logits = np.zeros((cnt, self.nn), np.float32)
+        policy = np.zeros((cnt, self.nn), np.float32)
+        value = np.zeros(cnt, np.float32)
+        path = np.zeros(cnt, np.int32)
+        self._check(lib().az_net_eval_delta(self.h, int(slot), _p(root), int(root_player), cnt, _p(boards), _p(players), _p(lasts),
+                                            _p(logits), _p(policy), _p(value), _p(path)), "az_net_eval_delta")
+        return logits, policy, value, path
 
     # ---- single search ----
     def search(self, board, player, last, temperature, noise=None, u=0.5, slot=0):

@@ -62,6 +62,7 @@ struct Lane {
     DevBuf root_logits, root_v;            // per slot, az_set_gumbel: the root's logits row and value of the running ply (allocated by the setter)
     DevBuf proof, root_proof, proof_stops; // per slot, az_set_solver: the status of every edge and of the root, the stops on proven edges (allocated by the setter)
     DevBuf threat_edges, threat_root, threat_depth, threat_move, threat_nodes, threat_stat;   // per slot, the root threat search (allocated on first use)
+    DevBuf delta_base, delta_done, delta_cnt;     // per slot, delta evaluation (az_delta.h): allocated by the first episode that is eligible with the switch on
     // one ply (k_begin, (S+1) x {trunk, fc, step}, k_move) captured once as a hipGraph and replayed every ply:
     // 3(S+1)+2 launches (6(S+1)+2 with the split trunk) become one submission.  Indexed [split trunk][arena].
     struct PlyGraph {
@@ -159,6 +160,10 @@ struct az_engine {
     int episode_threat = 0;        // whether the last (or open) episode ran with it: az_selfplay_threats speaks of that one
     DevBuf rec_threat;
     int64_t threat_stats[THREAT_STATS] = {0, 0, 0, 0, 0};
+    // az_set_delta_eval: leaves evaluated as deltas from the ply's root activations where the episode is eligible (delta_eligible)
+    bool delta_on = true;
+    int delta_tiles = DELTA_TILES_DEFAULT;
+    int64_t delta_stats[DELTA_CNT] = {};       // of the last (or open) episode: delta, full, conv3 tiles, base evaluations, delta evaluations by tile count
     PackedNet net[2];
     az_counters last{};
     // running episode (az_selfplay_begin .. az_selfplay_end)
@@ -167,6 +172,7 @@ struct az_engine {
         int num_games = 0, max_plies = 0;
         bool add_noise = true, arena = false, preset = false, profile = true;
         bool ext = false;          // the episode's evaluations go to the external evaluator (az_set_external_evaluator)
+        bool delta = false;        // the episode's lock-step trunk launches are base + delta evaluations (az_delta.h)
         int ext_net = -1;          // net id its requests carry instead of the items' own (az_search*: the slot argument), -1 = the items'
         az_counters c{};
         int64_t reused_roots = 0;
@@ -207,6 +213,12 @@ static LaunchCtx ctx_of_impl(const az_engine *e, const Lane &L)
     c.dbg = (unsigned long long *)L.dbg.p;
     c.scratch = (float *)L.scratch.p;
     c.inflight = (unsigned char *)L.inflight.p;
+    if (e->run.delta && L.delta_base.p) {
+        c.delta_base = (float *)L.delta_base.p;
+        c.delta_done = (unsigned char *)L.delta_done.p;
+        c.delta_cnt = (unsigned long long *)L.delta_cnt.p;
+        c.delta_tiles = e->delta_tiles;
+    }
     return c;
 }
 
@@ -845,6 +857,12 @@ static int create_engine(const az_config *cfg, az_engine **out, bool deep)
     e->profile = pe && pe[0] == '1';
     const char *pz = getenv("AZ_PERSIST");
     e->persist_allowed = !(pz && pz[0] == '0');
+    // AZ_DELTA=0: engines start with delta evaluation switched off; AZ_DELTA_TILES=t: with the threshold t (measurements
+    // through programs that do not call az_set_delta_eval / az_delta_max_tiles)
+    const char *dz = getenv("AZ_DELTA");
+    e->delta_on = !(dz && dz[0] == '0');
+    const char *dt = getenv("AZ_DELTA_TILES");
+    if (dt && atoi(dt) >= 1 && atoi(dt) <= 15) e->delta_tiles = atoi(dt);
     const char *cz = getenv("AZ_COMPACT");
     e->compact = !(cz && cz[0] == '0');
     const char *ge = getenv("AZ_GRAPH");
@@ -893,7 +911,8 @@ extern "C" void az_destroy(az_engine *e)
                          &L.path, &L.depth, &L.leaf_kind, &L.leaf, &L.leaf_last, &L.logits, &L.vhid, &L.pol_feat, &L.cnt,
                          &L.active_dev, &L.carried, &L.dbg, &L.scratch, &L.it_status, &L.it_net, &L.leaf_sym, &L.inflight,
                          &L.budget, &L.cp_board, &L.cp_state, &L.root_logits, &L.root_v, &L.proof, &L.root_proof, &L.proof_stops,
-                         &L.threat_edges, &L.threat_root, &L.threat_depth, &L.threat_move, &L.threat_nodes, &L.threat_stat};
+                         &L.threat_edges, &L.threat_root, &L.threat_depth, &L.threat_move, &L.threat_nodes, &L.threat_stat,
+                         &L.delta_base, &L.delta_done, &L.delta_cnt};
         for (DevBuf *b : all) dev_free(*b);
         for (hipEvent_t ev : L.ev) (void)hipEventDestroy(ev);
         for (int i = 0; i < 4; i++)
@@ -1144,6 +1163,28 @@ static int ensure_threat_buffers(az_engine *e)
     return AZ_OK;
 }
 
+// Delta evaluation serves the lock-step path of the plain float32 trunk at the size that has the kernels (n = 15), one net, one
+// leaf per game and batch, positions shown to the net as they are; everything else evaluates in full.
+static bool delta_eligible(const az_engine *e, bool arena, bool ext, bool capped)
+{
+    return e->delta_on && e->ops->trunk_delta && e->cfg.eval_kind == AZ_EVAL_NET && e->cfg.model == AZ_MODEL_PLAIN &&
+           e->trunk_mode == AZ_TRUNK_F32 && e->vl == 1 && !e->vl_kernel && !e->leaf_symmetry && !e->reuse && !arena && !ext && !capped &&
+           e->cfg.num_simulations <= DEFAULT_MAX_S;
+}
+static int ensure_delta_buffers(az_engine *e)
+{
+    int rc = AZ_OK;
+    for (Lane &L : e->lanes) {
+        const size_t B = (size_t)L.d.B;
+        if (!rc) rc = dev_alloc(e, L.delta_base, B * (size_t)e->ops->delta_floats_per_slot * sizeof(float), false);
+        if (!rc) rc = dev_alloc(e, L.delta_done, B, true);
+        if (!rc) rc = dev_alloc(e, L.delta_cnt, B * DELTA_CNT * sizeof(unsigned long long), true);
+    }
+    if (rc) return rc;
+    HIPCHECK(e, hipStreamSynchronize(e->stream));
+    return AZ_OK;
+}
+
 static int episode_begin(az_engine *e, const EpisodeSpec &sp)
 {
     const bool ext = e->ext.on;            // the evaluator is outside the engine: no weights, no cache, priors as given
@@ -1214,6 +1255,12 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
     r.ext = ext; r.ext_net = sp.ext_net;
     r.game_key0 = sp.game_key0;
     if (capped) { r.cap_fast = e->cap_fast; r.cap_permille = e->cap_permille; r.cap_export_full = e->cap_export_full; }
+    for (int64_t &x : e->delta_stats) x = 0;
+    if (!e->persist_gp && delta_eligible(e, sp.arena, ext, capped)) {
+        int rcd = ensure_delta_buffers(e);
+        if (rcd) return rcd;
+        r.delta = true;
+    }
     if (!sp.preset && e->start_count > 0) {
         r.start.resize(sp.num_games);
         for (int g = 0; g < sp.num_games; g++) {
@@ -1298,6 +1345,10 @@ static hipError_t launch_ply(az_engine *e, const LaunchCtx &lc, bool use_split, 
         return rc;
     }
     if (net && d.cache) e->ops->root_cache(lc);
+    // delta evaluation: the two base evaluations of every active slot, then every batch as deltas from them (also where the
+    // tile-split trunk would run: a delta workgroup is shorter than a split stage)
+    const bool delta = net && lc.delta_base && nnets == 1 && !cap;
+    if (delta) e->ops->trunk_base(lc, 0);
     const int nb = cap_batches(e, cap), nb_a = cap ? cap->nb_a : nb;
     LaunchCtx lcb = lc;                // phase B of a capped ply: the same kernels over fewer slots
     if (cap) { lcb.d.B = cap->slots_b; lcb.dv.B = cap->slots_b * d.L; }
@@ -1306,7 +1357,7 @@ static hipError_t launch_ply(az_engine *e, const LaunchCtx &lc, bool use_split, 
         const bool split = idx < nb_a ? use_split : cap->split_b;
         if (net) {
             if (!record(4 * idx)) return rc;
-            for (int id = 0; id < nnets; id++) { if (split) e->ops->trunk_split(c, id); else e->ops->trunk(c, id); }
+            for (int id = 0; id < nnets; id++) { if (delta) e->ops->trunk_delta(c, id); else if (split) e->ops->trunk_split(c, id); else e->ops->trunk(c, id); }
             if (!record(4 * idx + 1)) return rc;
             for (int id = 0; id < nnets; id++) e->ops->fc(c, id);
             if (!record(4 * idx + 2)) return rc;
@@ -1635,6 +1686,14 @@ static int read_counters(az_engine *e, az_counters &c)
         if (L.tape_wait_s > tape_wait) tape_wait = L.tape_wait_s;
     }
     e->solver_stops = stops;
+    if (e->run.delta) {
+        for (int64_t &x : e->delta_stats) x = 0;
+        for (Lane &L : e->lanes) {
+            std::vector<unsigned long long> hd((size_t)L.d.B * DELTA_CNT);
+            HIPCHECK(e, az_memcpy(L.stream, hd.data(), L.delta_cnt.p, hd.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < hd.size(); i++) e->delta_stats[i % DELTA_CNT] += (int64_t)hd[i];
+        }
+    }
     if (e->episode_threat) {
         for (int64_t &x : e->threat_stats) x = 0;
         for (Lane &L : e->lanes) {
@@ -2363,6 +2422,134 @@ extern "C" int az_solver_stops(const az_engine *e, int64_t *stops)
     if (!e || !stops) return AZ_ERR_INVALID;
     *stops = e->solver_stops;
     return AZ_OK;
+}
+
+// ---- delta evaluation (az_delta.h) ----
+extern "C" int az_set_delta_eval(az_engine *e, int on)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_delta_eval: an episode is open");
+    e->delta_on = on != 0;
+    return AZ_OK;
+}
+
+extern "C" int az_get_delta_eval(const az_engine *e) { return e ? (e->delta_on ? 1 : 0) : AZ_ERR_INVALID; }
+
+extern "C" int az_delta_max_tiles(az_engine *e, int tiles)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (tiles == 0) return e->delta_tiles;
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_delta_max_tiles: an episode is open");
+    if (tiles < 1 || tiles > 15) return fail(e, AZ_ERR_INVALID, "az_delta_max_tiles: 1 .. 15 conv3 tiles, 0 asks");
+    e->delta_tiles = tiles;
+    return tiles;
+}
+
+extern "C" int az_delta_stats(const az_engine *e, int64_t *delta, int64_t *full, int64_t *tiles, int64_t *base, int64_t *by_tiles)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (delta) *delta = e->delta_stats[0];
+    if (full) *full = e->delta_stats[1];
+    if (tiles) *tiles = e->delta_stats[2];
+    if (base) *base = e->delta_stats[3];
+    if (by_tiles) for (int t = 0; t < 16; t++) by_tiles[t] = e->delta_stats[4 + t];
+    return AZ_OK;
+}
+
+// the tile lists of a set of changed cells at n = 15, with the functions the kernel uses (az_delta.h; no GPU needed)
+extern "C" int az_delta_lists(int n, int count, const uint8_t *changed, uint16_t *wpos, uint16_t *cell, uint16_t *halo, int32_t *cnt)
+{
+    if (n != 15 || count < 0 || count > DELTA_MAX_CHANGED || (count && !changed) || !wpos || !cell || !halo || !cnt) return AZ_ERR_INVALID;
+    for (int i = 0; i < count; i++) if (changed[i] >= 15 * 15) return AZ_ERR_INVALID;
+    static DeltaLists<15> L;
+    static std::mutex m;
+    std::lock_guard<std::mutex> lock(m);
+    memset(&L, 0xEE, sizeof L);          // whatever the function does not write reads as 0xEEEE
+    delta_lists_serial<15>(changed, count, L);
+    memcpy(wpos, L.wpos, sizeof L.wpos);
+    memcpy(cell, L.cell, sizeof L.cell);
+    memcpy(halo, L.halo, sizeof L.halo);
+    for (int l = 0; l < 5; l++) cnt[l] = L.cnt[l];
+    return AZ_OK;
+}
+
+extern "C" int az_net_eval_delta(az_engine *e, int slot, const uint8_t *root, int root_player, int count, const uint8_t *boards,
+                                 const uint8_t *players, const int16_t *lasts, float *logits, float *policy, float *value, int32_t *path)
+{
+    if (!e || slot < 0 || slot > 1 || count < 0 || !root || !boards || !players || !lasts || (root_player != 1 && root_player != 2))
+        return fail(e, AZ_ERR_INVALID, "az_net_eval_delta: bad argument");
+    if (!e->net[slot].loaded) return fail(e, AZ_ERR_NO_WEIGHTS, "weights slot %d not loaded", slot);
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_net_eval_delta: a self-play episode is open on this engine");
+    if (!e->ops->trunk_delta || e->cfg.model != AZ_MODEL_PLAIN || e->cfg.eval_kind != AZ_EVAL_NET)
+        return fail(e, AZ_ERR_INVALID, "az_net_eval_delta: no delta evaluation for this board size or net");
+    DEVICE_GUARD(e);
+    int rc = ensure_delta_buffers(e);
+    if (rc) return rc;
+    Lane &L = e->lanes[0];
+    const int nn = e->nn, B = L.d.B;
+    DevBuf dpol, dval;
+    rc = dev_alloc(e, dpol, (size_t)B * nn * 4);
+    if (!rc) rc = dev_alloc(e, dval, (size_t)B * 4);
+    u64 rx[4], ro[4];
+    planes_from_cells(root, nn, rx, ro);
+    for (int c0 = 0; !rc && c0 < count; c0 += B) {
+        const int cnt = std::min(B, count - c0);
+        std::vector<u64> lf((size_t)B * 8, 0), bd((size_t)B * 8, 0);
+        std::vector<int> kind(B, LEAF_NONE), st(B, SLOT_IDLE), nets(B, slot), ll(B, -1), pl(B, root_player);
+        for (int i = 0; i < cnt; i++) {
+            u64 x[4], o[4];
+            planes_from_cells(boards + (size_t)(c0 + i) * nn, nn, x, o);
+            const bool xm = players[c0 + i] == 1;
+            for (int q = 0; q < 4; q++) {
+                lf[(size_t)i * 8 + q] = xm ? x[q] : o[q]; lf[(size_t)i * 8 + 4 + q] = xm ? o[q] : x[q];
+                bd[(size_t)i * 8 + q] = rx[q]; bd[(size_t)i * 8 + 4 + q] = ro[q];
+            }
+            kind[i] = LEAF_ROOT; st[i] = SLOT_ACTIVE; ll[i] = lasts[c0 + i];
+        }
+        hipError_t hr = az_memcpy(e->stream, L.leaf.p, lf.data(), lf.size() * 8, hipMemcpyHostToDevice);
+        if (hr == hipSuccess) hr = az_memcpy(e->stream, L.board.p, bd.data(), bd.size() * 8, hipMemcpyHostToDevice);
+        if (hr == hipSuccess) hr = az_memcpy(e->stream, L.leaf_kind.p, kind.data(), (size_t)B * 4, hipMemcpyHostToDevice);
+        if (hr == hipSuccess) hr = az_memcpy(e->stream, L.s_status.p, st.data(), (size_t)B * 4, hipMemcpyHostToDevice);
+        if (hr == hipSuccess) hr = az_memcpy(e->stream, L.s_net.p, nets.data(), (size_t)B * 4, hipMemcpyHostToDevice);
+        if (hr == hipSuccess) hr = az_memcpy(e->stream, L.s_player.p, pl.data(), (size_t)B * 4, hipMemcpyHostToDevice);
+        if (hr == hipSuccess) hr = az_memcpy(e->stream, L.leaf_last.p, ll.data(), (size_t)B * 4, hipMemcpyHostToDevice);
+        if (hr != hipSuccess) { rc = fail(e, AZ_ERR_HIP, "az_net_eval_delta upload: %s", hipGetErrorString(hr)); break; }
+        std::vector<unsigned char> done(B, 0);
+        {
+            LaunchCtx lc = ctx_of_impl(e, L);
+            lc.d.leaf_sym = lc.dv.leaf_sym = nullptr;
+            lc.d.B = lc.dv.B = cnt;
+            // one leaf per slot here, whatever az_set_virtual_loss says: the items are the slots
+            lc.dv = lc.d;
+            lc.delta_base = (float *)L.delta_base.p;
+            lc.delta_done = (unsigned char *)L.delta_done.p;
+            lc.delta_cnt = (unsigned long long *)L.delta_cnt.p;
+            lc.delta_tiles = e->delta_tiles;
+            e->ops->trunk_base(lc, slot);
+            e->ops->trunk_delta(lc, slot);
+            e->ops->fc(lc, slot);
+            e->ops->eval_tail(lc, cnt, (float *)dpol.p, (float *)dval.p);
+        }
+        hr = hipStreamSynchronize(e->stream);
+        if (hr == hipSuccess) hr = hipGetLastError();
+        if (hr == hipSuccess && logits)
+            hr = az_memcpy2d(e->stream, logits + (size_t)c0 * nn, (size_t)nn * 4, L.logits.p, (size_t)e->RW * 4, (size_t)nn * 4, cnt, hipMemcpyDeviceToHost);
+        if (hr == hipSuccess && policy) hr = az_memcpy(e->stream, policy + (size_t)c0 * nn, dpol.p, (size_t)cnt * nn * 4, hipMemcpyDeviceToHost);
+        if (hr == hipSuccess && value) hr = az_memcpy(e->stream, value + c0, dval.p, (size_t)cnt * 4, hipMemcpyDeviceToHost);
+        if (hr == hipSuccess && path) {
+            hr = az_memcpy(e->stream, done.data(), L.delta_done.p, (size_t)cnt, hipMemcpyDeviceToHost);
+            for (int i = 0; i < cnt; i++) path[c0 + i] = (int)done[i] - 1;      // conv3 tiles of a delta evaluation, -1 = evaluated in full
+        }
+        if (hr != hipSuccess) { rc = fail(e, AZ_ERR_HIP, "az_net_eval_delta: %s", hipGetErrorString(hr)); break; }
+    }
+    // leave the slots idle and empty
+    (void)hipMemsetAsync(L.s_status.p, 0, L.s_status.bytes, e->stream);
+    (void)hipMemsetAsync(L.leaf_kind.p, 0, L.leaf_kind.bytes, e->stream);
+    (void)hipMemsetAsync(L.board.p, 0, L.board.bytes, e->stream);
+    (void)hipStreamSynchronize(e->stream);
+    dev_free(dpol);
+    dev_free(dval);
+    return rc;
 }
 
 extern "C" int az_selfplay_proofs(az_engine *e, int8_t *roots)

@@ -251,11 +251,33 @@ void threat(const LaunchCtx &c)
 {
     hipLaunchKernelGGL(k_threat<N>, dim3(c.d.B), dim3(64), 0, c.stream, c.d);
 }
+
+constexpr bool HAS_DELTA = N == 15;      // the plain float32 trunk of the headline size (az_delta.h)
+
+void trunk_base(const LaunchCtx &c, int net_id)
+{
+    if constexpr (HAS_DELTA)
+        hipLaunchKernelGGL(k_trunk_base<N>, dim3(c.d.B, 2), dim3(NetGeo<N>::NW * 64), 0, c.stream, c.d, c.w[net_id], net_id, c.delta_base, c.delta_cnt);
+}
+
+void trunk_delta(const LaunchCtx &c, int net_id)
+{
+    if constexpr (HAS_DELTA) {
+        const dim3 g(c.dv.B), b(NetGeo<N>::NW * 64);
+        hipLaunchKernelGGL(k_trunk_delta<N>, g, b, 0, c.stream, c.dv, c.w[net_id], net_id, c.feat, (const float *)c.delta_base, c.delta_done,
+                           c.delta_cnt, c.delta_tiles);
+        hipLaunchKernelGGL(k_trunk_rest<N>, g, b, 0, c.stream, c.dv, c.w[net_id], net_id, c.feat, (const unsigned char *)c.delta_done);
+    }
+}
+
+template <bool ON>
+long long delta_floats() { if constexpr (ON) return 2ll * DeltaGeo<N>::STRIDE; else return 0; }
 }   // namespace
 
 const SizeOps *AZ_CAT(az_size_ops_, AZ_N)()
 {
     static const SizeOps ops = {trunk, trunk_split, split_scratch_floats, fc, step, step_vl, root_cache, search_prepare, search, move, eval_tail_l,
-                                set_positions, gather_roots, build_positions, ext_gather, ext_scatter, threat};
+                                set_positions, gather_roots, build_positions, ext_gather, ext_scatter, threat,
+                                HAS_DELTA ? trunk_base : nullptr, HAS_DELTA ? trunk_delta : nullptr, delta_floats<HAS_DELTA>()};
     return &ops;
 }

@@ -3,6 +3,7 @@
 #pragma once
 #include "az_net.h"
 #include "az_net_emul.h"
+#include "az_delta.h"
 #include "az_search.h"
 #include "az_batch.h"
 #include "az_ext.h"
@@ -24,6 +25,11 @@ struct LaunchCtx {
     unsigned long long *dbg;
     float *scratch;     // split-trunk images, SizeOps::split_floats_per_group floats per board group (or null)
     unsigned char *inflight;   // deep search (S > DEFAULT_MAX_S) with virtual-loss batching: in-flight count per edge [B][R][RW], else null
+    // delta evaluation (az_delta.h, az_set_delta_eval; part of the graph key): null = off, every board through SizeOps::trunk
+    float *delta_base;              // [slots][2] base images and feature rows of the running ply
+    unsigned char *delta_done;      // [slots] which boards the delta kernel evaluated in the running batch
+    unsigned long long *delta_cnt;  // [slots][DELTA_CNT] (az_delta.h)
+    int delta_tiles;                // a board with more conv3 tiles than this is evaluated in full
 };
 
 struct SizeOps {
@@ -52,6 +58,11 @@ struct SizeOps {
     void (*ext_scatter)(const LaunchCtx &, int item_base, int count, const int *map, const float *policy, const float *value);
     // az_set_threat_search / az_threat_batch (az_threat.h): the root threat search of the first d.B slots, one wavefront each
     void (*threat)(const LaunchCtx &);
+    // delta evaluation (az_delta.h), null where the size has none: the base evaluations of every active slot, once per ply; and
+    // the trunk of one batch, bit-identical to trunk's
+    void (*trunk_base)(const LaunchCtx &, int net_id);
+    void (*trunk_delta)(const LaunchCtx &, int net_id);
+    long long delta_floats_per_slot;
 };
 
 const SizeOps *az_size_ops(int n);     // nullptr for unsupported sizes

@@ -416,6 +416,38 @@ int az_set_virtual_loss(az_engine *e, int leaves);
  * bytes each.  Hits are reported in az_counters.cache_lookups / cache_hits.  Not allowed while an episode is open. */
 int az_set_eval_cache(az_engine *e, int64_t entries);
 
+/* Delta evaluation, ON by default: within one ply a game's root does not change, and a leaf is the root plus
+ * `depth` stones, so the trunk evaluates the root's stones once per ply and side to move (two base evaluations per active
+ * slot) and every root and leaf of the ply only where its 3x3 / 5x5 / 7x7 footprints in the three conv layers differ from
+ * them.  Every output element is the same k-ordered fma chain as in the full trunk: results are bit-identical with the
+ * switch on or off.  A leaf with more than 8 changed cells, or with more conv3 tiles than az_delta_max_tiles, is evaluated
+ * in full.
+ * Serves the lock-step pipeline of the plain float32 trunk at 15x15 with one net and one leaf per game and batch
+ * (az_selfplay*, az_search, az_search_batch); every other configuration -- other sizes, the ResidualBlock net, the
+ * emulated trunks, the arena, virtual-loss batching, leaf symmetry, subtree reuse, the playout cap, deep searches above
+ * 1024 simulations, the external evaluator, az_net_eval -- evaluates in full whatever the switch says.  Costs
+ * 2 x 122 KB of HBM per slot, allocated by the first eligible episode.
+ * az_set_delta_eval: AZ_ERR_STATE while an episode is open.
+ * az_delta_max_tiles(e, tiles): sets the threshold (1 .. 15 conv3 tiles of 16 cells) and returns it; tiles = 0 only asks.
+ * az_delta_stats: of the last (or open) episode or search call: evaluations on the delta path, evaluations in full on
+ * an eligible episode (fallbacks), conv3 tiles computed on the delta path, base evaluations, and by_tiles[16]: the delta
+ * evaluations by their conv3 tile count 0 .. 15.  Any pointer may be NULL.
+ * az_net_eval_delta (tests, measurements): `count` positions evaluated as deltas from ONE root position (root[n*n] cells,
+ * root_player to move there): outputs as az_net_eval, plus path[count]: the conv3 tiles the delta path computed for the
+ * position, -1 when it was evaluated in full.  The positions need not be reachable from the root: what differs is what
+ * is recomputed.  AZ_ERR_INVALID where no delta kernels exist (board size, net). */
+int az_set_delta_eval(az_engine *e, int on);
+int az_get_delta_eval(const az_engine *e);
+int az_delta_max_tiles(az_engine *e, int tiles);
+int az_delta_stats(const az_engine *e, int64_t *delta, int64_t *full, int64_t *tiles, int64_t *base, int64_t *by_tiles);
+/* The integer logic of the delta path on the host (no GPU needed), n = 15 and at most 8 changed cells (AZ_ERR_INVALID
+ * otherwise): the three tile lists -- wpos / cell [3][240]: padded-image position (r + 1) * 17 + c + 1 and board cell of every
+ * tile lane of conv1 / conv2 / conv3, cell 0xFFFF = a junk lane -- the two window lists halo [2][289] (positions of the base
+ * conv1 / conv2 images copied) and the five counts; entries behind a list's last tile read 0xEEEE. */
+int az_delta_lists(int n, int count, const uint8_t *changed, uint16_t *wpos, uint16_t *cell, uint16_t *halo, int32_t *cnt);
+int az_net_eval_delta(az_engine *e, int slot, const uint8_t *root, int root_player, int count, const uint8_t *boards,
+                      const uint8_t *players, const int16_t *lasts, float *logits, float *policy, float *value, int32_t *path);
+
 /* Opt-in: random-symmetry leaf evaluation, the optional half of SURVEY §8f-2 (the reference's README.md:61,82 names the 8-fold
  * symmetry of the board, its code only uses it to augment the examples and leaves Gomoku.rot90 / flip unused,
  * games.py:183-197).  With it every net evaluation of a search -- the root (mcts.py:109) and each expanded leaf
