@@ -278,6 +278,26 @@ static void dev_free(DevBuf &b)
     b.p = nullptr;
     b.bytes = 0;
 }
+// one allocation of a run that stops at the first failure: the caller has `e` and an `int rc`; further arguments as dev_alloc
+#define ALLOC(buf, ...) if (!rc) rc = dev_alloc(e, buf, __VA_ARGS__)
+
+// Per-slot buffers an option brings with it: every lane gets the ones it does not have yet (zeroed), sized by its slots, then
+// one stream sync.  rezero: a buffer that is already there is zeroed again.
+struct LaneBuf {
+    DevBuf Lane::*buf;
+    size_t bytes_per_slot;
+    bool rezero;
+};
+static int ensure_lane_buffers(az_engine *e, std::initializer_list<LaneBuf> list)
+{
+    int rc = AZ_OK;
+    for (Lane &L : e->lanes)
+        for (const LaneBuf &a : list)
+            if (!(L.*a.buf).p || a.rezero) ALLOC(L.*a.buf, (size_t)L.d.B * a.bytes_per_slot);
+    if (rc) return rc;
+    HIPCHECK(e, hipStreamSynchronize(e->stream));
+    return AZ_OK;
+}
 // Blocking copies go through the engine's own (non-blocking) stream: nothing in the engine touches the legacy null
 // stream, whose implicit synchronisation would couple the engines of a process to each other and to PyTorch's work.
 static hipError_t az_memcpy(hipStream_t s, void *dst, const void *src, size_t bytes, hipMemcpyKind kind)
@@ -695,19 +715,17 @@ static int alloc_items(az_engine *e, Lane &L, int leaves)
 {
     const size_t NI = (size_t)L.d.B * leaves;
     int rc = AZ_OK;
-#define ALLOC(buf, bytes) if (!rc) rc = dev_alloc(e, L.buf, (bytes))
-    ALLOC(path, (NI * (size_t)e->PATH + 64) * 4);   // +64: k_step's speculative path[lane] read of the last slot
-    ALLOC(depth, NI * 4);
-    ALLOC(leaf_kind, NI * 4); ALLOC(leaf, NI * 8 * sizeof(u64)); ALLOC(leaf_last, NI * 4); ALLOC(leaf_sym, NI * 4);
-    ALLOC(logits, NI * (size_t)e->RW * 4); ALLOC(vhid, NI * 64 * 4);
-    ALLOC(pol_feat, NI * (size_t)((((e->cfg.model == AZ_MODEL_RESNET ? 3 : 6) * e->nn + 3) / 4) * 4) * 4);   // feature rows [NI][FROW], zero tail stays zero
+    ALLOC(L.path, (NI * (size_t)e->PATH + 64) * 4);   // +64: k_step's speculative path[lane] read of the last slot
+    ALLOC(L.depth, NI * 4);
+    ALLOC(L.leaf_kind, NI * 4); ALLOC(L.leaf, NI * 8 * sizeof(u64)); ALLOC(L.leaf_last, NI * 4); ALLOC(L.leaf_sym, NI * 4);
+    ALLOC(L.logits, NI * (size_t)e->RW * 4); ALLOC(L.vhid, NI * 64 * 4);
+    ALLOC(L.pol_feat, NI * (size_t)((((e->cfg.model == AZ_MODEL_RESNET ? 3 : 6) * e->nn + 3) / 4) * 4) * 4);   // feature rows [NI][FROW], zero tail stays zero
 #ifdef AZ_STAMPS
-    ALLOC(dbg, (NI * 16 + 4096 * 32 + NI * 32) * sizeof(unsigned long long));     // trunk stamps | k_fc stamps | conv3 per-wave stamps
+    ALLOC(L.dbg, (NI * 16 + 4096 * 32 + NI * 32) * sizeof(unsigned long long));     // trunk stamps | k_fc stamps | conv3 per-wave stamps
 #endif
     if (e->split_max > 0)    // zeroed once: the padding ring of the packed images is never written afterwards
-        ALLOC(scratch, (size_t)e->ops->split_scratch_floats((int)NI, e->cfg.model) * sizeof(float));
-    if (leaves > 1) { ALLOC(it_status, NI * 4); ALLOC(it_net, NI * 4); }
-#undef ALLOC
+        ALLOC(L.scratch, (size_t)e->ops->split_scratch_floats((int)NI, e->cfg.model) * sizeof(float));
+    if (leaves > 1) { ALLOC(L.it_status, NI * 4); ALLOC(L.it_net, NI * 4); }
     if (rc) return rc;
     DevState &d = L.d;
     d.L = leaves;
@@ -804,16 +822,14 @@ static int create_engine(const az_config *cfg, az_engine **out, bool deep)
     for (int i = 0; i < K && !rc; i++) {
         Lane &L = e->lanes[i];
         const size_t B = (size_t)std::min(per, cfg->slots - i * per);
-#define ALLOC(buf, bytes) if (!rc) rc = dev_alloc(e, L.buf, (bytes))
-        ALLOC(board, B * 8 * sizeof(u64));
-        ALLOC(s_game, B * 4); ALLOC(s_ply, B * 4); ALLOC(s_player, B * 4); ALLOC(s_last, B * 4);
-        ALLOC(s_status, B * 4); ALLOC(s_net, B * 4);
-        ALLOC(edges, B * (size_t)e->R * e->RW * sizeof(Edge));
-        ALLOC(rows_used, B * 4);
-        ALLOC(cnt, B * CNT_STRIDE * sizeof(unsigned long long)); ALLOC(active_dev, 16);
-        ALLOC(carried, B * 4);
-        ALLOC(budget, B * 4); ALLOC(cp_board, B * 8 * sizeof(u64)); ALLOC(cp_state, B * 4 * 4);
-#undef ALLOC
+        ALLOC(L.board, B * 8 * sizeof(u64));
+        ALLOC(L.s_game, B * 4); ALLOC(L.s_ply, B * 4); ALLOC(L.s_player, B * 4); ALLOC(L.s_last, B * 4);
+        ALLOC(L.s_status, B * 4); ALLOC(L.s_net, B * 4);
+        ALLOC(L.edges, B * (size_t)e->R * e->RW * sizeof(Edge));
+        ALLOC(L.rows_used, B * 4);
+        ALLOC(L.cnt, B * CNT_STRIDE * sizeof(unsigned long long)); ALLOC(L.active_dev, 16);
+        ALLOC(L.carried, B * 4);
+        ALLOC(L.budget, B * 4); ALLOC(L.cp_board, B * 8 * sizeof(u64)); ALLOC(L.cp_state, B * 4 * 4);
         DevState &d = L.d;
         d.B = (int)B; d.R = e->R; d.S = cfg->num_simulations; d.k = cfg->win_length; d.rule = WIN_RULE_FREESTYLE;
         d.c_puct = cfg->c_puct; d.w_noise = cfg->dirichlet_weight;
@@ -1073,18 +1089,16 @@ static int ensure_episode_buffers(az_engine *e, int games, bool need_noise)
     const size_t nn = e->nn, G = (size_t)games;
     int rc = AZ_OK;
     stop_tapes(e);            // a producer of an abandoned episode still writes into the buffers below
-#define ALLOC(buf, bytes, zero) if (!rc) rc = dev_alloc(e, e->buf, (bytes), zero)
-    ALLOC(rec_planes, G * nn * 8 * sizeof(u64), false);
-    ALLOC(rec_last, G * nn * 2, false); ALLOC(rec_action, G * nn * 2, false); ALLOC(rec_mover, G * nn, false);
-    ALLOC(rec_pi, G * nn * nn * 4, false); ALLOC(rec_visits, G * nn * nn * 2, false);
-    ALLOC(g_nply, G * 4, true); ALLOC(g_result, G * 4, true);
-    ALLOC(rec_value, G * nn * 4, false); ALLOC(g_cross, G * 4, false);
-    if (e->solver) ALLOC(rec_proof, G * nn, false);
-    if (e->threat_depth) ALLOC(rec_threat, G * nn, false);
+    ALLOC(e->rec_planes, G * nn * 8 * sizeof(u64), false);
+    ALLOC(e->rec_last, G * nn * 2, false); ALLOC(e->rec_action, G * nn * 2, false); ALLOC(e->rec_mover, G * nn, false);
+    ALLOC(e->rec_pi, G * nn * nn * 4, false); ALLOC(e->rec_visits, G * nn * nn * 2, false);
+    ALLOC(e->g_nply, G * 4, true); ALLOC(e->g_result, G * 4, true);
+    ALLOC(e->rec_value, G * nn * 4, false); ALLOC(e->g_cross, G * 4, false);
+    if (e->solver) ALLOC(e->rec_proof, G * nn, false);
+    if (e->threat_depth) ALLOC(e->rec_threat, G * nn, false);
     if (!rc) HIPCHECK(e, hipMemsetAsync(e->g_cross.p, 0xFF, G * 4, e->stream));      // -1: no game has crossed
-    ALLOC(u, G * nn * sizeof(double), false);
-    if (need_noise) ALLOC(noise, G * (size_t)e->tape_len * sizeof(double), false);
-#undef ALLOC
+    ALLOC(e->u, G * nn * sizeof(double), false);
+    if (need_noise) ALLOC(e->noise, G * (size_t)e->tape_len * sizeof(double), false);
     if (rc) return rc;
     each_state(e, [&](DevState &d) {
         d.rec_planes = (u64 *)e->rec_planes.p; d.rec_last = (short *)e->rec_last.p; d.rec_action = (short *)e->rec_action.p;
@@ -1148,19 +1162,9 @@ static void set_threat_state(DevState &d, const Lane *L, int max_depth, int budg
 
 static int ensure_threat_buffers(az_engine *e)
 {
-    int rc = AZ_OK;
-    for (Lane &L : e->lanes) {
-        const size_t B = (size_t)L.d.B;
-        if (!rc && !L.threat_edges.p) rc = dev_alloc(e, L.threat_edges, B * (size_t)e->RW);
-        if (!rc && !L.threat_root.p) rc = dev_alloc(e, L.threat_root, B);
-        if (!rc && !L.threat_depth.p) rc = dev_alloc(e, L.threat_depth, B);
-        if (!rc && !L.threat_move.p) rc = dev_alloc(e, L.threat_move, B * 2);
-        if (!rc && !L.threat_nodes.p) rc = dev_alloc(e, L.threat_nodes, B * 4);
-        if (!rc && !L.threat_stat.p) rc = dev_alloc(e, L.threat_stat, B * THREAT_STATS * sizeof(unsigned long long));
-    }
-    if (rc) return rc;
-    HIPCHECK(e, hipStreamSynchronize(e->stream));
-    return AZ_OK;
+    return ensure_lane_buffers(e, {{&Lane::threat_edges, (size_t)e->RW, false}, {&Lane::threat_root, 1, false}, {&Lane::threat_depth, 1, false},
+                                   {&Lane::threat_move, 2, false}, {&Lane::threat_nodes, 4, false},
+                                   {&Lane::threat_stat, THREAT_STATS * sizeof(unsigned long long), false}});
 }
 
 // Delta evaluation serves the lock-step path of the plain float32 trunk at the size that has the kernels (n = 15), one net, one
@@ -1173,16 +1177,9 @@ static bool delta_eligible(const az_engine *e, bool arena, bool ext, bool capped
 }
 static int ensure_delta_buffers(az_engine *e)
 {
-    int rc = AZ_OK;
-    for (Lane &L : e->lanes) {
-        const size_t B = (size_t)L.d.B;
-        if (!rc) rc = dev_alloc(e, L.delta_base, B * (size_t)e->ops->delta_floats_per_slot * sizeof(float), false);
-        if (!rc) rc = dev_alloc(e, L.delta_done, B, true);
-        if (!rc) rc = dev_alloc(e, L.delta_cnt, B * DELTA_CNT * sizeof(unsigned long long), true);
-    }
-    if (rc) return rc;
-    HIPCHECK(e, hipStreamSynchronize(e->stream));
-    return AZ_OK;
+    // every call starts from no base evaluation done and counters at zero; the activations themselves are written before they are read
+    return ensure_lane_buffers(e, {{&Lane::delta_base, (size_t)e->ops->delta_floats_per_slot * sizeof(float), false},
+                                   {&Lane::delta_done, 1, true}, {&Lane::delta_cnt, DELTA_CNT * sizeof(unsigned long long), true}});
 }
 
 static int episode_begin(az_engine *e, const EpisodeSpec &sp)
@@ -1390,6 +1387,28 @@ static int ply_graph(az_engine *e, Lane &L, const LaunchCtx &lc, bool use_split,
     return AZ_OK;
 }
 
+// few pending boards: the latency path, the tile-split trunk (the emulated trunk has one kernel, so that its results never
+// depend on the slot count)
+static bool use_split(const az_engine *e, const Lane &L, int pending_boards)
+{
+    return e->split_max > 0 && L.scratch.p && pending_boards <= e->split_max && e->trunk_mode == AZ_TRUNK_F32;
+}
+
+// The tapes of the ply a lane is about to play on stream s must be on the device (streamed a wave ahead of the games).  A wave
+// whose upload is still in flight would stall the play stream by the same amount: it is waited for here so that the stall
+// is counted (az_counters.tape_wait_seconds); normally the wave landed a ply or two ago.
+static hipError_t await_tapes(az_engine *e, Lane &L, hipStream_t s)
+{
+    if (!e->tapes) return hipSuccess;
+    hipEvent_t ev = nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    hipError_t rc = e->tapes->need(L.plies_played + e->tapes->ahead, &ev);
+    if (rc == hipSuccess && ev && hipEventQuery(ev) != hipSuccess) rc = hipEventSynchronize(ev);
+    L.tape_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (rc == hipSuccess && ev) rc = hipStreamWaitEvent(s, ev, 0);
+    return rc;
+}
+
 // one lane plays up to max_steps plies of its active slots in lock step (one "step" = MCTS.run for each active game);
 // runs on the lane's own host thread
 static int lane_plies(az_engine *e, Lane &L, int max_steps)
@@ -1414,19 +1433,9 @@ static int lane_plies(az_engine *e, Lane &L, int max_steps)
         lc.dv.B = L.cur * L.d.L;
         const DevState &d = lc.d;
         const bool full = L.cur == L.d.B;          // the captured graph holds the full grid; a shrunken ply is launched kernel by kernel
-        // few pending boards: latency path (the emulated trunk has one kernel, so that its results never depend on the slot count)
-        const bool use_split = e->split_max > 0 && L.scratch.p && L.active * e->vl <= e->split_max && e->trunk_mode == AZ_TRUNK_F32;
-        if (e->tapes) {       // the tapes of this ply must be on the device (streamed a wave ahead of the games)
-            hipEvent_t ev = nullptr;
-            const auto tw0 = std::chrono::steady_clock::now();
-            hipError_t trc = e->tapes->need(L.plies_played + e->tapes->ahead, &ev);
-            if (trc != hipSuccess) return lane_fail(L, AZ_ERR_HIP, "tape producer: %s", hipGetErrorString(trc));
-            // a wave whose upload is still in flight would stall the play stream by the same amount: wait for it here so
-            // that the stall is counted (az_counters.tape_wait_seconds); normally the wave landed a ply or two ago
-            if (ev && hipEventQuery(ev) != hipSuccess) HIPCHECK_L(L, hipEventSynchronize(ev));
-            L.tape_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count();
-            if (ev) HIPCHECK_L(L, hipStreamWaitEvent(L.stream, ev, 0));
-        }
+        const bool split = use_split(e, L, L.active * e->vl);
+        const hipError_t trc = await_tapes(e, L, L.stream);
+        if (trc != hipSuccess) return lane_fail(L, AZ_ERR_HIP, "tape producer: %s", hipGetErrorString(trc));
         // a deep search (S > DEFAULT_MAX_S) is launched kernel by kernel instead of as one graph of ~3 (S + 1) nodes per ply
         // (measured, DESIGN 7b: 5x5 / 1024 slots / S = 1000 runs as fast eagerly as from the graph; a 15x15 search costs 2.5 %)
         // a capped ply (az_set_playout_cap) is launched kernel by kernel as well: the width of its second phase changes from
@@ -1435,16 +1444,16 @@ static int lane_plies(az_engine *e, Lane &L, int max_steps)
         if (r.cap_fast) {
             cap.nb_a = sims_batches(e, r.cap_fast);
             cap.slots_b = L.n_full == 0 ? 0 : (e->compact ? L.n_full : L.cur);
-            cap.split_b = e->split_max > 0 && L.scratch.p && L.n_full * e->vl <= e->split_max && e->trunk_mode == AZ_TRUNK_F32;
+            cap.split_b = use_split(e, L, L.n_full * e->vl);
         }
         const int nrun = cap_batches(e, r.cap_fast ? &cap : nullptr);      // evaluation batches this ply launches
         if (e->use_graph && !prof && full && S <= DEFAULT_MAX_S && !r.cap_fast) {
             hipGraphExec_t exec = nullptr;
-            int rcg = ply_graph(e, L, lc, use_split, nnets, net, &exec);
+            int rcg = ply_graph(e, L, lc, split, nnets, net, &exec);
             if (rcg) return rcg;
             HIPCHECK_L(L, hipGraphLaunch(exec, L.stream));
         } else {
-            HIPCHECK_L(L, launch_ply(e, lc, use_split, nnets, net, prof ? L.ev.data() : nullptr, r.cap_fast ? &cap : nullptr));
+            HIPCHECK_L(L, launch_ply(e, lc, split, nnets, net, prof ? L.ev.data() : nullptr, r.cap_fast ? &cap : nullptr));
         }
         if (net) L.trunk_launches += e->persist_gp ? 1 : (int64_t)nnets * nrun;
         L.steps += nrun;
@@ -1490,21 +1499,45 @@ static void ext_restore(az_engine *e)
     each_state(e, [&](DevState &d) { d.ext_eval = 0; d.cache = (float *)e->cache.p; });
 }
 
+// an episode that failed is closed too: the engine stays usable
+static void abandon_episode(az_engine *e)
+{
+    e->run.open = false;
+    stop_tapes(e);
+    ext_restore(e);
+}
+
+// The first K lanes as a finished episode leaves them, for the code that fills slots by hand: every slot and evaluation item
+// idle, no pending leaf, the boards empty, no preset positions.  Enqueued on the engine's stream; IdleLanes also waits for it.
+static void idle_lanes(az_engine *e, int K)
+{
+    for (int l = 0; l < K; l++) {
+        Lane &L = e->lanes[l];
+        (void)hipMemsetAsync(L.s_status.p, 0, L.s_status.bytes, e->stream);
+        (void)hipMemsetAsync(L.leaf_kind.p, 0, L.leaf_kind.bytes, e->stream);
+        if (L.it_status.p) (void)hipMemsetAsync(L.it_status.p, 0, L.it_status.bytes, e->stream);
+        (void)hipMemsetAsync(L.board.p, 0, L.board.bytes, e->stream);
+        L.active = L.preset_m = 0;
+    }
+}
+struct IdleLanes {         // ... on every way out of the scope
+    az_engine *e;
+    int K;
+    ~IdleLanes()
+    {
+        idle_lanes(e, K);
+        (void)hipStreamSynchronize(e->stream);
+    }
+};
+
 // the evaluator gave up (or a HIP call failed) in the middle of a ply: the episode is closed and every slot left idle
 static void ext_abort(az_engine *e)
 {
     (void)hipStreamSynchronize(e->stream);
-    for (Lane &L : e->lanes) {
-        (void)hipMemsetAsync(L.s_status.p, 0, L.s_status.bytes, e->stream);
-        (void)hipMemsetAsync(L.leaf_kind.p, 0, L.leaf_kind.bytes, e->stream);
-        if (L.it_status.p) (void)hipMemsetAsync(L.it_status.p, 0, L.it_status.bytes, e->stream);
-        L.active = 0;
-    }
+    idle_lanes(e, (int)e->lanes.size());
     (void)hipStreamSynchronize(e->stream);
-    e->run.open = false;
     e->have_episode = false;
-    stop_tapes(e);
-    ext_restore(e);
+    abandon_episode(e);
 }
 
 // All lanes play up to max_steps plies TOGETHER from the calling thread, kernel by kernel on the engine's stream: every
@@ -1544,14 +1577,7 @@ static int ext_plies(az_engine *e, int max_steps)
         }
         for (Play &p : play) {
             Lane &L = *p.L;
-            if (e->tapes) {       // the tapes of this ply must be on the device, as in lane_plies
-                hipEvent_t tev = nullptr;
-                const auto tw0 = std::chrono::steady_clock::now();
-                EXTCHECK(e->tapes->need(L.plies_played + e->tapes->ahead, &tev));
-                if (tev && hipEventQuery(tev) != hipSuccess) EXTCHECK(hipEventSynchronize(tev));
-                L.tape_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count();
-                if (tev) EXTCHECK(hipStreamWaitEvent(s, tev, 0));
-            }
+            EXTCHECK(await_tapes(e, L, s));
             hipLaunchKernelGGL(k_begin, dim3((p.lc.d.B + 255) / 256), dim3(256), 0, s, p.lc.d);
         }
         for (int idx = 0; idx < nb; idx++) {
@@ -1656,51 +1682,37 @@ static int active_slots(const az_engine *e)
     return a;
 }
 
+// the column sums, over every slot of every lane, of a per-slot statistics buffer [B][K] of 64-bit counts
+static int sum_slot_stats(az_engine *e, DevBuf Lane::*buf, int K, int64_t *sums)
+{
+    std::fill(sums, sums + K, (int64_t)0);
+    std::vector<unsigned long long> h;
+    for (Lane &L : e->lanes) {
+        h.resize((size_t)L.d.B * K);
+        HIPCHECK(e, az_memcpy(L.stream, h.data(), (L.*buf).p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < h.size(); i++) sums[i % K] += (int64_t)h[i];
+    }
+    return AZ_OK;
+}
+
 static int read_counters(az_engine *e, az_counters &c)
 {
-    c.expansions = c.simulations = c.terminal_hits = c.depth_sum = 0;
+    int64_t cnt[CNT_STRIDE];
+    int rc = sum_slot_stats(e, &Lane::cnt, CNT_STRIDE, cnt);
+    e->solver_stops = 0;
+    if (!rc && e->episode_solver && e->lanes[0].proof_stops.p) rc = sum_slot_stats(e, &Lane::proof_stops, 1, &e->solver_stops);
+    if (!rc && e->run.delta) rc = sum_slot_stats(e, &Lane::delta_cnt, DELTA_CNT, e->delta_stats);
+    if (!rc && e->episode_threat) rc = sum_slot_stats(e, &Lane::threat_stat, THREAT_STATS, e->threat_stats);
+    if (rc) return rc;
+    c.expansions = cnt[0]; c.simulations = cnt[1]; c.terminal_hits = cnt[2]; c.depth_sum = cnt[3];
+    const int64_t reused = cnt[4];
+    c.duplicate_leaves = cnt[5]; c.cache_lookups = cnt[6]; c.cache_hits = cnt[7];
     c.steps = c.trunk_launches = c.plies = 0;
-    c.duplicate_leaves = c.cache_lookups = c.cache_hits = 0;
-    int64_t reused = 0, stops = 0;
     double trunk_ms = 0.0, nn_ms = 0.0, step_ms = 0.0, tape_wait = 0.0;
     for (Lane &L : e->lanes) {
-        std::vector<unsigned long long> hc((size_t)L.d.B * CNT_STRIDE);
-        HIPCHECK(e, az_memcpy(L.stream, hc.data(), L.cnt.p, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        for (int b = 0; b < L.d.B; b++) {
-            c.expansions += (int64_t)hc[(size_t)b * CNT_STRIDE + 0];
-            c.simulations += (int64_t)hc[(size_t)b * CNT_STRIDE + 1];
-            c.terminal_hits += (int64_t)hc[(size_t)b * CNT_STRIDE + 2];
-            c.depth_sum += (int64_t)hc[(size_t)b * CNT_STRIDE + 3];
-            reused += (int64_t)hc[(size_t)b * CNT_STRIDE + 4];
-            c.duplicate_leaves += (int64_t)hc[(size_t)b * CNT_STRIDE + 5];
-            c.cache_lookups += (int64_t)hc[(size_t)b * CNT_STRIDE + 6];
-            c.cache_hits += (int64_t)hc[(size_t)b * CNT_STRIDE + 7];
-        }
-        if (e->episode_solver && L.proof_stops.p) {
-            std::vector<unsigned long long> hs((size_t)L.d.B);
-            HIPCHECK(e, az_memcpy(L.stream, hs.data(), L.proof_stops.p, hs.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-            for (unsigned long long x : hs) stops += (int64_t)x;
-        }
         c.steps += L.steps; c.trunk_launches += L.trunk_launches; c.plies += L.plies;
         trunk_ms += L.trunk_ms; nn_ms += L.nn_ms; step_ms += L.step_ms;
         if (L.tape_wait_s > tape_wait) tape_wait = L.tape_wait_s;
-    }
-    e->solver_stops = stops;
-    if (e->run.delta) {
-        for (int64_t &x : e->delta_stats) x = 0;
-        for (Lane &L : e->lanes) {
-            std::vector<unsigned long long> hd((size_t)L.d.B * DELTA_CNT);
-            HIPCHECK(e, az_memcpy(L.stream, hd.data(), L.delta_cnt.p, hd.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < hd.size(); i++) e->delta_stats[i % DELTA_CNT] += (int64_t)hd[i];
-        }
-    }
-    if (e->episode_threat) {
-        for (int64_t &x : e->threat_stats) x = 0;
-        for (Lane &L : e->lanes) {
-            std::vector<unsigned long long> ht((size_t)L.d.B * THREAT_STATS);
-            HIPCHECK(e, az_memcpy(L.stream, ht.data(), L.threat_stat.p, ht.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < ht.size(); i++) e->threat_stats[i % THREAT_STATS] += (int64_t)ht[i];
-        }
     }
     c.tape_wait_seconds = tape_wait;
     c.tape_threads = e->tapes || e->stream_tapes ? e->tape_threads : 0;
@@ -1766,14 +1778,16 @@ static int episode_end(az_engine *e, az_counters *out)
     return AZ_OK;
 }
 
-static int run_episode(az_engine *e, const EpisodeSpec &sp, az_counters *out)
+// every ply of the episode that `begun` (the result of its begin call) opened, and its end
+static int play_episode(az_engine *e, int begun, az_counters *out)
 {
-    int rc = episode_begin(e, sp);
+    int rc = begun;
     if (!rc) rc = episode_plies(e, 1 << 30);
     if (!rc) rc = episode_end(e, out);
-    if (rc) { e->run.open = false; stop_tapes(e); ext_restore(e); }
+    if (rc) abandon_episode(e);
     return rc;
 }
+static int run_episode(az_engine *e, const EpisodeSpec &sp, az_counters *out) { return play_episode(e, episode_begin(e, sp), out); }
 
 static int upload_T(az_engine *e, const double *table, bool arena)
 {
@@ -1855,7 +1869,7 @@ extern "C" int az_selfplay_end(az_engine *e, az_counters *out)
     if (!e) return AZ_ERR_INVALID;
     DEVICE_GUARD(e);
     const int rc = episode_end(e, out);
-    if (rc) { e->run.open = false; stop_tapes(e); ext_restore(e); }      // a failed episode is closed too: the engine stays usable
+    if (rc) abandon_episode(e);
     return rc;
 }
 
@@ -1864,11 +1878,7 @@ extern "C" int az_selfplay(az_engine *e, const az_selfplay_args *a, az_counters 
     if (!e) return AZ_ERR_INVALID;
     if (e->run.open) return fail(e, AZ_ERR_STATE, "az_selfplay: an episode is already open (az_selfplay_end first)");
     DEVICE_GUARD(e);
-    int rc = az_selfplay_begin(e, a);
-    if (!rc) rc = episode_plies(e, 1 << 30);
-    if (!rc) rc = episode_end(e, out);
-    if (rc) { e->run.open = false; stop_tapes(e); ext_restore(e); }
-    return rc;
+    return play_episode(e, az_selfplay_begin(e, a), out);
 }
 
 extern "C" int az_selfplay_games(az_engine *e, int32_t *nply, int32_t *result)
@@ -1881,6 +1891,29 @@ extern "C" int az_selfplay_games(az_engine *e, int32_t *nply, int32_t *result)
     return AZ_OK;
 }
 
+// Every record of the last episode, game-major then ply: f(g, ply, src_index, r) with the game, the absolute ply (the device
+// counts plies from the empty board), the record's place g * nn + ply in the device's [G][nn] arrays and its running number.
+template <class F>
+static void for_each_record(const az_engine *e, F f)
+{
+    size_t r = 0;
+    for (int g = 0; g < e->episode_games; g++)
+        for (int m = 0; m < e->h_nply[g]; m++, r++) {
+            const int ply = e->h_start[g] + m;
+            f(g, ply, (size_t)g * e->nn + ply, r);
+        }
+}
+
+// one value per record, out of a device array [G][nn] of T
+template <class T>
+static int read_record_array(az_engine *e, const DevBuf &b, T *out)
+{
+    std::vector<T> h((size_t)e->episode_games * e->nn);
+    HIPCHECK(e, az_memcpy(e->stream, h.data(), b.p, h.size() * sizeof(T), hipMemcpyDeviceToHost));
+    for_each_record(e, [&](int, int, size_t si, size_t r) { out[r] = h[si]; });
+    return AZ_OK;
+}
+
 extern "C" int az_selfplay_records(az_engine *e, uint8_t *boards, uint8_t *movers, int16_t *lasts, int16_t *actions,
                                    float *pis, int32_t *visits, int8_t *z)
 {
@@ -1889,35 +1922,29 @@ extern "C" int az_selfplay_records(az_engine *e, uint8_t *boards, uint8_t *mover
     const int nn = e->nn, G = e->episode_games;
     const size_t tot = (size_t)G * nn;
     std::vector<u64> pl(tot * 8);
-    std::vector<short> la(tot), ac(tot);
     std::vector<unsigned char> mv(tot);
     std::vector<float> pi(tot * nn);
     std::vector<unsigned short> vis(tot * nn);
     HIPCHECK(e, az_memcpy(e->stream, pl.data(), e->rec_planes.p, pl.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHECK(e, az_memcpy(e->stream, la.data(), e->rec_last.p, la.size() * 2, hipMemcpyDeviceToHost));
-    HIPCHECK(e, az_memcpy(e->stream, ac.data(), e->rec_action.p, ac.size() * 2, hipMemcpyDeviceToHost));
     HIPCHECK(e, az_memcpy(e->stream, mv.data(), e->rec_mover.p, mv.size(), hipMemcpyDeviceToHost));
     HIPCHECK(e, az_memcpy(e->stream, pi.data(), e->rec_pi.p, pi.size() * 4, hipMemcpyDeviceToHost));
     HIPCHECK(e, az_memcpy(e->stream, vis.data(), e->rec_visits.p, vis.size() * 2, hipMemcpyDeviceToHost));
-    size_t r = 0;
-    for (int g = 0; g < G; g++) {
-        for (int m = 0; m < e->h_nply[g]; m++, r++) {
-            size_t si = (size_t)g * nn + e->h_start[g] + m;
-            int mover = mv[si];
-            if (boards)
-                for (int j = 0; j < nn; j++) {
-                    bool me = (pl[si * 8 + (j >> 6)] >> (j & 63)) & 1ull, op = (pl[si * 8 + 4 + (j >> 6)] >> (j & 63)) & 1ull;
-                    boards[r * nn + j] = (uint8_t)(me ? mover : (op ? 3 - mover : 0));
-                }
-            if (movers) movers[r] = (uint8_t)mover;
-            if (lasts) lasts[r] = la[si];
-            if (actions) actions[r] = ac[si];
-            if (pis) memcpy(pis + r * nn, pi.data() + si * nn, (size_t)nn * 4);
-            if (visits) for (int j = 0; j < nn; j++) visits[r * nn + j] = vis[si * nn + j];
-            int res = e->h_result[g];
-            if (z) z[r] = (int8_t)(res == 0 ? 99 : (res == 3 ? 0 : (mover == res ? 1 : -1)));
-        }
-    }
+    int rc = lasts ? read_record_array(e, e->rec_last, lasts) : AZ_OK;
+    if (!rc && actions) rc = read_record_array(e, e->rec_action, actions);
+    if (rc) return rc;
+    for_each_record(e, [&](int g, int, size_t si, size_t r) {
+        const int mover = mv[si];
+        if (boards)
+            for (int j = 0; j < nn; j++) {
+                bool me = (pl[si * 8 + (j >> 6)] >> (j & 63)) & 1ull, op = (pl[si * 8 + 4 + (j >> 6)] >> (j & 63)) & 1ull;
+                boards[r * nn + j] = (uint8_t)(me ? mover : (op ? 3 - mover : 0));
+            }
+        if (movers) movers[r] = (uint8_t)mover;
+        if (pis) memcpy(pis + r * nn, pi.data() + si * nn, (size_t)nn * 4);
+        if (visits) for (int j = 0; j < nn; j++) visits[r * nn + j] = vis[si * nn + j];
+        const int res = e->h_result[g];
+        if (z) z[r] = (int8_t)(res == 0 ? 99 : (res == 3 ? 0 : (mover == res ? 1 : -1)));
+    });
     return AZ_OK;
 }
 
@@ -1938,17 +1965,14 @@ static bool exported(const az_engine *e, int g, int ply)
 static int upload_src_index(az_engine *e, int64_t *records)
 {
     std::vector<int> src;
-    for (int g = 0; g < e->episode_games; g++)
-        for (int m = 0; m < e->h_nply[g]; m++)
-            if (exported(e, g, e->h_start[g] + m)) src.push_back(g * e->nn + e->h_start[g] + m);
+    for_each_record(e, [&](int g, int ply, size_t si, size_t) { if (exported(e, g, ply)) src.push_back((int)si); });
     *records = (int64_t)src.size();
     return src.empty() ? AZ_OK : upload(e, e->src_index, src.data(), src.size() * 4);
 }
 static int64_t export_records(const az_engine *e)
 {
     int64_t n = 0;
-    for (int g = 0; g < e->episode_games; g++)
-        for (int m = 0; m < e->h_nply[g]; m++) n += exported(e, g, e->h_start[g] + m) ? 1 : 0;
+    for_each_record(e, [&](int g, int ply, size_t, size_t) { n += exported(e, g, ply) ? 1 : 0; });
     return n;
 }
 
@@ -1975,13 +1999,7 @@ extern "C" int az_selfplay_values(az_engine *e, float *values)
     if (!e || !e->have_episode) return fail(e, AZ_ERR_STATE, "no episode has been run");
     if (!values) return fail(e, AZ_ERR_INVALID, "az_selfplay_values: null buffer");
     DEVICE_GUARD(e);
-    const int nn = e->nn, G = e->episode_games;
-    std::vector<float> val((size_t)G * nn);
-    HIPCHECK(e, az_memcpy(e->stream, val.data(), e->rec_value.p, val.size() * 4, hipMemcpyDeviceToHost));
-    size_t r = 0;
-    for (int g = 0; g < G; g++)
-        for (int m = 0; m < e->h_nply[g]; m++) values[r++] = val[(size_t)g * nn + e->h_start[g] + m];
-    return AZ_OK;
+    return read_record_array(e, e->rec_value, values);
 }
 
 extern "C" int az_selfplay_pack_values(az_engine *e, float *values_dev)
@@ -2243,11 +2261,9 @@ extern "C" int az_selfplay_sims(az_engine *e, int32_t *sims)
 {
     if (!e || !e->have_episode) return fail(e, AZ_ERR_STATE, "no episode has been run");
     if (!sims) return fail(e, AZ_ERR_INVALID, "az_selfplay_sims: null buffer");
-    size_t r = 0;
-    for (int g = 0; g < e->episode_games; g++)
-        for (int m = 0; m < e->h_nply[g]; m++)
-            sims[r++] = e->h_cap_fast && !az_playout_cap_full(e->h_key0 + (uint32_t)g, e->h_start[g] + m, e->h_cap_permille)
-                            ? e->h_cap_fast : e->cfg.num_simulations;
+    for_each_record(e, [&](int g, int ply, size_t, size_t r) {
+        sims[r] = e->h_cap_fast && !az_playout_cap_full(e->h_key0 + (uint32_t)g, ply, e->h_cap_permille) ? e->h_cap_fast : e->cfg.num_simulations;
+    });
     return AZ_OK;
 }
 
@@ -2296,6 +2312,81 @@ static void planes_from_cells(const uint8_t *cells, int nn, u64 *x, u64 *o)
     }
 }
 
+// az_net_eval_delta's part of eval_positions: the root every position is evaluated as a delta of, and where the path taken goes
+struct DeltaRoot {
+    const uint8_t *cells;
+    int player;
+    int32_t *path;
+};
+
+// The evaluation of `count` given positions on lane 0 (single-position and batch evaluation calls use lane 0), a pass at a time:
+// the planes as the mover sees them into the first items of the lane, launch(lc, cnt) for the trunk, then the FC layers and
+// the policy / value tail, and the rows copied back.  root: the delta call's extras, nullptr for the full evaluation.  The
+// lane is left idle and empty on every way out.
+template <class Launch>
+static int eval_positions(az_engine *e, const char *who, int slot, int count, const uint8_t *boards, const uint8_t *players,
+                          const int16_t *lasts, float *logits, float *policy, float *value, const DeltaRoot *root, Launch launch)
+{
+    Lane &L = e->lanes[0];
+    const int nn = e->nn;
+    // What the two calls differ in beyond their trunk kernels.  The full evaluation fills the lane's evaluation ITEMS, slots x
+    // leaves per batch (az_set_virtual_loss), and launches over all of them: a pass is an evaluation batch of the search.  A
+    // delta evaluation is of one leaf per SLOT, as the search's is (delta_eligible: no virtual-loss batching): base activations,
+    // root board and mover are per slot, so a pass holds the lane's slots, the kernels see the slots as their items
+    // (lc.dv = lc.d below) and run over the positions of the pass only.
+    const DevState &v = root ? L.d : L.dv;
+    const int B = v.B;
+    int *const d_status = v.s_status, *const d_net = v.s_net;
+    IdleLanes idle{e, 1};
+    DevBuf dpol, dval;
+    int rc = dev_alloc(e, dpol, (size_t)B * nn * 4);
+    if (!rc) rc = dev_alloc(e, dval, (size_t)B * 4);
+    u64 rx[4] = {}, ro[4] = {};
+    if (root) planes_from_cells(root->cells, nn, rx, ro);
+    for (int c0 = 0; !rc && c0 < count; c0 += B) {
+        const int cnt = std::min(B, count - c0);
+        std::vector<u64> lf((size_t)B * 8, 0), bd(root ? (size_t)B * 8 : 0, 0);
+        std::vector<int> kind(B, LEAF_NONE), st(B, SLOT_IDLE), nets(B, slot), ll(B, -1), pl(B, root ? root->player : 0);
+        for (int i = 0; i < cnt; i++) {
+            u64 x[4], o[4];
+            planes_from_cells(boards + (size_t)(c0 + i) * nn, nn, x, o);
+            const bool xm = players[c0 + i] == 1;
+            for (int q = 0; q < 4; q++) { lf[(size_t)i * 8 + q] = xm ? x[q] : o[q]; lf[(size_t)i * 8 + 4 + q] = xm ? o[q] : x[q]; }
+            for (int q = 0; root && q < 4; q++) { bd[(size_t)i * 8 + q] = rx[q]; bd[(size_t)i * 8 + 4 + q] = ro[q]; }
+            kind[i] = LEAF_ROOT; st[i] = SLOT_ACTIVE; ll[i] = lasts[c0 + i];
+        }
+        hipError_t hr = az_memcpy(e->stream, L.leaf.p, lf.data(), lf.size() * 8, hipMemcpyHostToDevice);
+        if (hr == hipSuccess && root) hr = az_memcpy(e->stream, L.board.p, bd.data(), bd.size() * 8, hipMemcpyHostToDevice);
+        if (hr == hipSuccess) hr = az_memcpy(e->stream, L.leaf_kind.p, kind.data(), (size_t)B * 4, hipMemcpyHostToDevice);
+        if (hr == hipSuccess) hr = az_memcpy(e->stream, d_status, st.data(), (size_t)B * 4, hipMemcpyHostToDevice);
+        if (hr == hipSuccess) hr = az_memcpy(e->stream, d_net, nets.data(), (size_t)B * 4, hipMemcpyHostToDevice);
+        if (hr == hipSuccess && root) hr = az_memcpy(e->stream, L.s_player.p, pl.data(), (size_t)B * 4, hipMemcpyHostToDevice);
+        if (hr == hipSuccess) hr = az_memcpy(e->stream, L.leaf_last.p, ll.data(), (size_t)B * 4, hipMemcpyHostToDevice);
+        if (hr != hipSuccess) { rc = fail(e, AZ_ERR_HIP, "%s upload: %s", who, hipGetErrorString(hr)); break; }
+        LaunchCtx lc = ctx_of_impl(e, L);
+        lc.d.leaf_sym = lc.dv.leaf_sym = nullptr;       // controller.py:39-53 evaluates the position as it is
+        if (root) { lc.d.B = cnt; lc.dv = lc.d; }
+        launch(lc, cnt);
+        e->ops->fc(lc, slot);
+        e->ops->eval_tail(lc, cnt, (float *)dpol.p, (float *)dval.p);
+        hr = hipStreamSynchronize(e->stream);
+        if (hr == hipSuccess) hr = hipGetLastError();
+        if (hr == hipSuccess && logits)
+            hr = az_memcpy2d(e->stream, logits + (size_t)c0 * nn, (size_t)nn * 4, L.logits.p, (size_t)e->RW * 4, (size_t)nn * 4, cnt, hipMemcpyDeviceToHost);
+        if (hr == hipSuccess && policy) hr = az_memcpy(e->stream, policy + (size_t)c0 * nn, dpol.p, (size_t)cnt * nn * 4, hipMemcpyDeviceToHost);
+        if (hr == hipSuccess && value) hr = az_memcpy(e->stream, value + c0, dval.p, (size_t)cnt * 4, hipMemcpyDeviceToHost);
+        if (hr == hipSuccess && root && root->path) {
+            std::vector<unsigned char> done(cnt, 0);
+            hr = az_memcpy(e->stream, done.data(), L.delta_done.p, (size_t)cnt, hipMemcpyDeviceToHost);
+            for (int i = 0; i < cnt; i++) root->path[c0 + i] = (int)done[i] - 1;      // conv3 tiles of a delta evaluation, -1 = evaluated in full
+        }
+        if (hr != hipSuccess) { rc = fail(e, AZ_ERR_HIP, "%s: %s", who, hipGetErrorString(hr)); break; }
+    }
+    dev_free(dpol);
+    dev_free(dval);
+    return rc;
+}
+
 extern "C" int az_net_eval(az_engine *e, int slot, int count, const uint8_t *boards, const uint8_t *players,
                            const int16_t *lasts, float *logits, float *policy, float *value)
 {
@@ -2303,50 +2394,9 @@ extern "C" int az_net_eval(az_engine *e, int slot, int count, const uint8_t *boa
     if (!e->net[slot].loaded) return fail(e, AZ_ERR_NO_WEIGHTS, "weights slot %d not loaded", slot);
     if (e->run.open) return fail(e, AZ_ERR_STATE, "az_net_eval: a self-play episode is open on this engine");
     DEVICE_GUARD(e);
-    Lane &L = e->lanes[0];            // single-position and batch evaluation calls use lane 0
-    const int nn = e->nn, B = L.dv.B;              // boards per pass = evaluation items of the lane
-    DevBuf dpol, dval;
-    int rc = dev_alloc(e, dpol, (size_t)B * nn * 4);
-    if (!rc) rc = dev_alloc(e, dval, (size_t)B * 4);
-    for (int c0 = 0; !rc && c0 < count; c0 += B) {
-        const int cnt = std::min(B, count - c0);
-        std::vector<u64> lf((size_t)B * 8, 0);
-        std::vector<int> kind(B, LEAF_NONE), st(B, SLOT_IDLE), nets(B, slot), ll(B, -1);
-        for (int i = 0; i < cnt; i++) {
-            u64 x[4], o[4];
-            planes_from_cells(boards + (size_t)(c0 + i) * nn, nn, x, o);
-            const bool xm = players[c0 + i] == 1;
-            for (int q = 0; q < 4; q++) { lf[(size_t)i * 8 + q] = xm ? x[q] : o[q]; lf[(size_t)i * 8 + 4 + q] = xm ? o[q] : x[q]; }
-            kind[i] = LEAF_ROOT; st[i] = SLOT_ACTIVE; ll[i] = lasts[c0 + i];
-        }
-        hipError_t hr = az_memcpy(e->stream, L.leaf.p, lf.data(), lf.size() * 8, hipMemcpyHostToDevice);
-        if (hr == hipSuccess) hr = az_memcpy(e->stream, L.leaf_kind.p, kind.data(), (size_t)B * 4, hipMemcpyHostToDevice);
-        if (hr == hipSuccess) hr = az_memcpy(e->stream, L.dv.s_status, st.data(), (size_t)B * 4, hipMemcpyHostToDevice);
-        if (hr == hipSuccess) hr = az_memcpy(e->stream, L.dv.s_net, nets.data(), (size_t)B * 4, hipMemcpyHostToDevice);
-        if (hr == hipSuccess) hr = az_memcpy(e->stream, L.leaf_last.p, ll.data(), (size_t)B * 4, hipMemcpyHostToDevice);
-        if (hr != hipSuccess) { rc = fail(e, AZ_ERR_HIP, "az_net_eval upload: %s", hipGetErrorString(hr)); break; }
-        {
-            LaunchCtx lc = ctx_of_impl(e, L);
-            lc.d.leaf_sym = lc.dv.leaf_sym = nullptr;       // controller.py:39-53 evaluates the position as it is
-            if (e->split_max > 0 && L.scratch.p && cnt <= e->split_max && e->trunk_mode == AZ_TRUNK_F32) e->ops->trunk_split(lc, slot); else e->ops->trunk(lc, slot);
-            e->ops->fc(lc, slot);
-            e->ops->eval_tail(lc, cnt, (float *)dpol.p, (float *)dval.p);
-        }
-        hr = hipStreamSynchronize(e->stream);
-        if (hr == hipSuccess) hr = hipGetLastError();
-        if (hr == hipSuccess && logits)
-            hr = az_memcpy2d(e->stream, logits + (size_t)c0 * nn, (size_t)nn * 4, L.logits.p, (size_t)e->RW * 4, (size_t)nn * 4, cnt, hipMemcpyDeviceToHost);
-        if (hr == hipSuccess && policy) hr = az_memcpy(e->stream, policy + (size_t)c0 * nn, dpol.p, (size_t)cnt * nn * 4, hipMemcpyDeviceToHost);
-        if (hr == hipSuccess && value) hr = az_memcpy(e->stream, value + c0, dval.p, (size_t)cnt * 4, hipMemcpyDeviceToHost);
-        if (hr != hipSuccess) { rc = fail(e, AZ_ERR_HIP, "az_net_eval: %s", hipGetErrorString(hr)); break; }
-    }
-    // leave the slots idle
-    (void)hipMemsetAsync(L.dv.s_status, 0, (size_t)B * 4, e->stream);
-    (void)hipMemsetAsync(L.leaf_kind.p, 0, L.leaf_kind.bytes, e->stream);
-    (void)hipStreamSynchronize(e->stream);
-    dev_free(dpol);
-    dev_free(dval);
-    return rc;
+    return eval_positions(e, "az_net_eval", slot, count, boards, players, lasts, logits, policy, value, nullptr, [&](LaunchCtx &lc, int cnt) {
+        if (use_split(e, e->lanes[0], cnt)) e->ops->trunk_split(lc, slot); else e->ops->trunk(lc, slot);
+    });
 }
 
 // ---- MCTS-Solver: proven wins, losses and draws in the search tree ----
@@ -2384,14 +2434,9 @@ extern "C" int az_set_solver(az_engine *e, int on)
         int rc = deep_memory_guard("the edge statuses of the solver", need, e);
         if (rc) return rc;
     }
-    int rc = AZ_OK;
-    for (Lane &L : e->lanes) {
-        if (!rc && !L.proof.p) rc = dev_alloc(e, L.proof, (size_t)L.d.B * (size_t)e->R * (size_t)e->RW);
-        if (!rc && !L.root_proof.p) rc = dev_alloc(e, L.root_proof, (size_t)L.d.B);
-        if (!rc && !L.proof_stops.p) rc = dev_alloc(e, L.proof_stops, (size_t)L.d.B * sizeof(unsigned long long));
-    }
+    const int rc = ensure_lane_buffers(e, {{&Lane::proof, (size_t)e->R * (size_t)e->RW, false}, {&Lane::root_proof, 1, false},
+                                           {&Lane::proof_stops, sizeof(unsigned long long), false}});
     if (rc) return rc;
-    HIPCHECK(e, hipStreamSynchronize(e->stream));
     for (Lane &L : e->lanes) {
         L.d.proof_buf = (unsigned char *)L.proof.p;
         L.d.root_proof = (signed char *)L.root_proof.p;
@@ -2485,71 +2530,16 @@ extern "C" int az_net_eval_delta(az_engine *e, int slot, const uint8_t *root, in
     DEVICE_GUARD(e);
     int rc = ensure_delta_buffers(e);
     if (rc) return rc;
-    Lane &L = e->lanes[0];
-    const int nn = e->nn, B = L.d.B;
-    DevBuf dpol, dval;
-    rc = dev_alloc(e, dpol, (size_t)B * nn * 4);
-    if (!rc) rc = dev_alloc(e, dval, (size_t)B * 4);
-    u64 rx[4], ro[4];
-    planes_from_cells(root, nn, rx, ro);
-    for (int c0 = 0; !rc && c0 < count; c0 += B) {
-        const int cnt = std::min(B, count - c0);
-        std::vector<u64> lf((size_t)B * 8, 0), bd((size_t)B * 8, 0);
-        std::vector<int> kind(B, LEAF_NONE), st(B, SLOT_IDLE), nets(B, slot), ll(B, -1), pl(B, root_player);
-        for (int i = 0; i < cnt; i++) {
-            u64 x[4], o[4];
-            planes_from_cells(boards + (size_t)(c0 + i) * nn, nn, x, o);
-            const bool xm = players[c0 + i] == 1;
-            for (int q = 0; q < 4; q++) {
-                lf[(size_t)i * 8 + q] = xm ? x[q] : o[q]; lf[(size_t)i * 8 + 4 + q] = xm ? o[q] : x[q];
-                bd[(size_t)i * 8 + q] = rx[q]; bd[(size_t)i * 8 + 4 + q] = ro[q];
-            }
-            kind[i] = LEAF_ROOT; st[i] = SLOT_ACTIVE; ll[i] = lasts[c0 + i];
-        }
-        hipError_t hr = az_memcpy(e->stream, L.leaf.p, lf.data(), lf.size() * 8, hipMemcpyHostToDevice);
-        if (hr == hipSuccess) hr = az_memcpy(e->stream, L.board.p, bd.data(), bd.size() * 8, hipMemcpyHostToDevice);
-        if (hr == hipSuccess) hr = az_memcpy(e->stream, L.leaf_kind.p, kind.data(), (size_t)B * 4, hipMemcpyHostToDevice);
-        if (hr == hipSuccess) hr = az_memcpy(e->stream, L.s_status.p, st.data(), (size_t)B * 4, hipMemcpyHostToDevice);
-        if (hr == hipSuccess) hr = az_memcpy(e->stream, L.s_net.p, nets.data(), (size_t)B * 4, hipMemcpyHostToDevice);
-        if (hr == hipSuccess) hr = az_memcpy(e->stream, L.s_player.p, pl.data(), (size_t)B * 4, hipMemcpyHostToDevice);
-        if (hr == hipSuccess) hr = az_memcpy(e->stream, L.leaf_last.p, ll.data(), (size_t)B * 4, hipMemcpyHostToDevice);
-        if (hr != hipSuccess) { rc = fail(e, AZ_ERR_HIP, "az_net_eval_delta upload: %s", hipGetErrorString(hr)); break; }
-        std::vector<unsigned char> done(B, 0);
-        {
-            LaunchCtx lc = ctx_of_impl(e, L);
-            lc.d.leaf_sym = lc.dv.leaf_sym = nullptr;
-            lc.d.B = lc.dv.B = cnt;
-            // one leaf per slot here, whatever az_set_virtual_loss says: the items are the slots
-            lc.dv = lc.d;
-            lc.delta_base = (float *)L.delta_base.p;
-            lc.delta_done = (unsigned char *)L.delta_done.p;
-            lc.delta_cnt = (unsigned long long *)L.delta_cnt.p;
-            lc.delta_tiles = e->delta_tiles;
-            e->ops->trunk_base(lc, slot);
-            e->ops->trunk_delta(lc, slot);
-            e->ops->fc(lc, slot);
-            e->ops->eval_tail(lc, cnt, (float *)dpol.p, (float *)dval.p);
-        }
-        hr = hipStreamSynchronize(e->stream);
-        if (hr == hipSuccess) hr = hipGetLastError();
-        if (hr == hipSuccess && logits)
-            hr = az_memcpy2d(e->stream, logits + (size_t)c0 * nn, (size_t)nn * 4, L.logits.p, (size_t)e->RW * 4, (size_t)nn * 4, cnt, hipMemcpyDeviceToHost);
-        if (hr == hipSuccess && policy) hr = az_memcpy(e->stream, policy + (size_t)c0 * nn, dpol.p, (size_t)cnt * nn * 4, hipMemcpyDeviceToHost);
-        if (hr == hipSuccess && value) hr = az_memcpy(e->stream, value + c0, dval.p, (size_t)cnt * 4, hipMemcpyDeviceToHost);
-        if (hr == hipSuccess && path) {
-            hr = az_memcpy(e->stream, done.data(), L.delta_done.p, (size_t)cnt, hipMemcpyDeviceToHost);
-            for (int i = 0; i < cnt; i++) path[c0 + i] = (int)done[i] - 1;      // conv3 tiles of a delta evaluation, -1 = evaluated in full
-        }
-        if (hr != hipSuccess) { rc = fail(e, AZ_ERR_HIP, "az_net_eval_delta: %s", hipGetErrorString(hr)); break; }
-    }
-    // leave the slots idle and empty
-    (void)hipMemsetAsync(L.s_status.p, 0, L.s_status.bytes, e->stream);
-    (void)hipMemsetAsync(L.leaf_kind.p, 0, L.leaf_kind.bytes, e->stream);
-    (void)hipMemsetAsync(L.board.p, 0, L.board.bytes, e->stream);
-    (void)hipStreamSynchronize(e->stream);
-    dev_free(dpol);
-    dev_free(dval);
-    return rc;
+    const Lane &L = e->lanes[0];
+    const DeltaRoot dr{root, root_player, path};
+    return eval_positions(e, "az_net_eval_delta", slot, count, boards, players, lasts, logits, policy, value, &dr, [&](LaunchCtx &lc, int) {
+        lc.delta_base = (float *)L.delta_base.p;
+        lc.delta_done = (unsigned char *)L.delta_done.p;
+        lc.delta_cnt = (unsigned long long *)L.delta_cnt.p;
+        lc.delta_tiles = e->delta_tiles;
+        e->ops->trunk_base(lc, slot);
+        e->ops->trunk_delta(lc, slot);
+    });
 }
 
 extern "C" int az_selfplay_proofs(az_engine *e, int8_t *roots)
@@ -2558,13 +2548,7 @@ extern "C" int az_selfplay_proofs(az_engine *e, int8_t *roots)
     if (!roots) return fail(e, AZ_ERR_INVALID, "az_selfplay_proofs: null buffer");
     if (!e->episode_solver || !e->rec_proof.p) return fail(e, AZ_ERR_STATE, "az_selfplay_proofs: the episode ran without the solver");
     DEVICE_GUARD(e);
-    const int nn = e->nn, G = e->episode_games;
-    std::vector<int8_t> val((size_t)G * nn);
-    HIPCHECK(e, az_memcpy(e->stream, val.data(), e->rec_proof.p, val.size(), hipMemcpyDeviceToHost));
-    size_t r = 0;
-    for (int g = 0; g < G; g++)
-        for (int m = 0; m < e->h_nply[g]; m++) roots[r++] = val[(size_t)g * nn + e->h_start[g] + m];
-    return AZ_OK;
+    return read_record_array(e, e->rec_proof, roots);
 }
 
 // k_move's count vector N' of one root row of `count` legal children, with the function the kernel uses (az_tree.h)
@@ -2611,6 +2595,35 @@ static void add_counters(az_counters &t, const az_counters &c)
     t.tape_threads = c.tape_threads; t.host_cpus = c.host_cpus;
 }
 
+// A wave's m positions over the first K lanes: an even share each, what a lane cannot hold goes to the lanes with room.  Sets
+// every Lane::preset_m; position i of the wave sits in slot i - first of its lane.
+static BatchLanes spread_wave(az_engine *e, int K, int m)
+{
+    BatchLanes bl{};
+    bl.K = K; bl.L = e->lanes[0].d.L;
+    int left = m;
+    for (int l = 0; l < K; l++) {
+        Lane &L = e->lanes[l];
+        L.preset_m = std::min(L.d.B, (left + (K - l) - 1) / (K - l));
+        left -= L.preset_m;
+    }
+    for (int l = 0; l < K && left > 0; l++) {
+        Lane &L = e->lanes[l];
+        const int add = std::min(L.d.B - L.preset_m, left);
+        L.preset_m += add; left -= add;
+    }
+    int first = 0;
+    for (int l = 0; l < K; l++) {
+        const Lane &L = e->lanes[l];
+        BatchLane &b = bl.lane[l];
+        b.board = L.d.board; b.s_game = L.d.s_game; b.s_ply = L.d.s_ply; b.s_player = L.d.s_player; b.s_last = L.d.s_last;
+        b.s_status = L.d.s_status; b.leaf_kind = L.d.leaf_kind; b.carried = L.d.carried; b.edges = L.d.edges;
+        b.B = L.d.B; b.first = first; b.m = L.preset_m;
+        first += L.preset_m;
+    }
+    return bl;
+}
+
 // The search of `count` checked positions, arguments as az_search_batch.  batch: the positions go over every lane, the ply
 // runs over the slots that hold one and the kernels are chosen for throughput, as in self-play (EpisodeSpec::batch); else
 // they sit in the first slots of lane 0, whose ply runs over its whole grid (the captured graph) on the latency choices.
@@ -2641,7 +2654,7 @@ static int preset_search(az_engine *e, bool batch, int slot, int count, const ui
     // The lanes' states for this call: per-position temperatures, key 0 for every position, and the compact noise rows.  The
     // baseline net (slot 1) searches as net 0 (the arena flag only selects the net through s_player) under its own cache
     // generation (the evaluation cache keys its entries by net id).  Everything is put back on every way out -- in the states
-    // AND their item views, which az_net_eval's tail reads -- so that no other entry point ever sees these values.
+    // AND their item views, which az_net_eval goes by -- so that no other entry point ever sees these values.
     const PackedNet saved0 = e->net[0];
     const float *sv2w = e->lanes[0].d.v2w[0], *sv2b = e->lanes[0].d.v2b[0];
     struct Restore {
@@ -2673,29 +2686,7 @@ static int preset_search(az_engine *e, bool batch, int slot, int count, const ui
     std::vector<double> hu(wn);
     for (int w0 = 0; w0 < count; w0 += Wv) {
         const int m = std::min(Wv, count - w0);
-        // the wave's positions over the lanes: an even share each, what a lane cannot hold goes to the lanes with room
-        BatchLanes bl{};
-        bl.K = K; bl.L = e->lanes[0].d.L;
-        int left = m;
-        for (int l = 0; l < K; l++) {
-            Lane &L = e->lanes[l];
-            L.preset_m = std::min(L.d.B, (left + (K - l) - 1) / (K - l));
-            left -= L.preset_m;
-        }
-        for (int l = 0; l < K && left > 0; l++) {
-            Lane &L = e->lanes[l];
-            const int add = std::min(L.d.B - L.preset_m, left);
-            L.preset_m += add; left -= add;
-        }
-        int first = 0;
-        for (int l = 0; l < K; l++) {
-            const Lane &L = e->lanes[l];
-            BatchLane &b = bl.lane[l];
-            b.board = L.d.board; b.s_game = L.d.s_game; b.s_ply = L.d.s_ply; b.s_player = L.d.s_player; b.s_last = L.d.s_last;
-            b.s_status = L.d.s_status; b.leaf_kind = L.d.leaf_kind; b.carried = L.d.carried; b.edges = L.d.edges;
-            b.B = L.d.B; b.first = first; b.m = L.preset_m;
-            first += L.preset_m;
-        }
+        const BatchLanes bl = spread_wave(e, K, m);
         // u is read at d.u[game * nn + ply]: scattered here, the other entries of the row are never read
         std::fill(hu.begin(), hu.begin() + (size_t)m * nn, 0.0);
         for (int i = 0; i < m; i++) {
@@ -2987,43 +2978,14 @@ extern "C" int az_threat_batch(az_engine *e, int count, const uint8_t *boards, c
     if (!rc) rc = dev_alloc(e, e->bt_players, (size_t)Wv, false);
     if (!rc) rc = dev_alloc(e, e->bt_lasts, (size_t)Wv * 2, false);
     if (rc) return rc;
-    struct Idle {          // the slots go back idle on every way out
-        az_engine *e;
-        ~Idle()
-        {
-            for (Lane &L : e->lanes) { (void)hipMemsetAsync(L.s_status.p, 0, L.s_status.bytes, e->stream); L.preset_m = 0; }
-            (void)hipStreamSynchronize(e->stream);
-        }
-    } idle{e};
+    IdleLanes idle{e, K};
     const std::vector<int16_t> no_last((size_t)Wv, (int16_t)-1);
     HIPCHECK(e, hipMemcpyAsync(e->bt_lasts.p, no_last.data(), (size_t)Wv * 2, hipMemcpyHostToDevice, e->stream));
     std::vector<int8_t> h8;
     std::vector<int16_t> h16;
     for (int w0 = 0; w0 < count; w0 += Wv) {
         const int m = std::min(Wv, count - w0);
-        // the wave's positions over the lanes, as az_search_batch spreads them
-        BatchLanes bl{};
-        bl.K = K; bl.L = e->lanes[0].d.L;
-        int left = m;
-        for (int l = 0; l < K; l++) {
-            Lane &L = e->lanes[l];
-            L.preset_m = std::min(L.d.B, (left + (K - l) - 1) / (K - l));
-            left -= L.preset_m;
-        }
-        for (int l = 0; l < K && left > 0; l++) {
-            Lane &L = e->lanes[l];
-            const int add = std::min(L.d.B - L.preset_m, left);
-            L.preset_m += add; left -= add;
-        }
-        int first = 0;
-        for (int l = 0; l < K; l++) {
-            const Lane &L = e->lanes[l];
-            BatchLane &b = bl.lane[l];
-            b.board = L.d.board; b.s_game = L.d.s_game; b.s_ply = L.d.s_ply; b.s_player = L.d.s_player; b.s_last = L.d.s_last;
-            b.s_status = L.d.s_status; b.leaf_kind = L.d.leaf_kind; b.carried = L.d.carried; b.edges = L.d.edges;
-            b.B = L.d.B; b.first = first; b.m = L.preset_m;
-            first += L.preset_m;
-        }
+        const BatchLanes bl = spread_wave(e, K, m);
         HIPCHECK(e, hipMemcpyAsync(e->bt_cells.p, boards + (size_t)w0 * nn, (size_t)m * nn, hipMemcpyHostToDevice, e->stream));
         HIPCHECK(e, hipMemcpyAsync(e->bt_players.p, players + w0, (size_t)m, hipMemcpyHostToDevice, e->stream));
         e->ops->set_positions(e->stream, bl, (const unsigned char *)e->bt_cells.p, (const unsigned char *)e->bt_players.p,
@@ -3039,7 +3001,7 @@ extern "C" int az_threat_batch(az_engine *e, int count, const uint8_t *boards, c
         }
         HIPCHECK(e, hipStreamSynchronize(e->stream));
         HIPCHECK(e, hipGetLastError());
-        first = 0;
+        int first = 0;
         for (Lane &L : e->lanes) {
             const size_t pm = (size_t)L.preset_m, at = (size_t)(w0 + first);
             first += L.preset_m;
@@ -3068,13 +3030,7 @@ extern "C" int az_selfplay_threats(az_engine *e, int8_t *depth)
     if (!depth) return fail(e, AZ_ERR_INVALID, "az_selfplay_threats: null buffer");
     if (!e->episode_threat || !e->rec_threat.p) return fail(e, AZ_ERR_STATE, "az_selfplay_threats: the episode ran without the threat search");
     DEVICE_GUARD(e);
-    const int nn = e->nn, G = e->episode_games;
-    std::vector<int8_t> val((size_t)G * nn);
-    HIPCHECK(e, az_memcpy(e->stream, val.data(), e->rec_threat.p, val.size(), hipMemcpyDeviceToHost));
-    size_t r = 0;
-    for (int g = 0; g < G; g++)
-        for (int m = 0; m < e->h_nply[g]; m++) depth[r++] = val[(size_t)g * nn + e->h_start[g] + m];
-    return AZ_OK;
+    return read_record_array(e, e->rec_threat, depth);
 }
 
 extern "C" int az_threat_stats(az_engine *e, int64_t *win_roots, int64_t *lost_roots, int64_t *block_roots, int64_t *exhausted, int64_t *nodes)
@@ -3121,8 +3077,8 @@ extern "C" int az_arena(az_engine *e, const az_arena_args *a, az_arena_result *o
     if (actions) {
         std::vector<short> ac((size_t)G * nn);
         HIPCHECK(e, az_memcpy(e->stream, ac.data(), e->rec_action.p, ac.size() * 2, hipMemcpyDeviceToHost));
-        for (int g = 0; g < G; g++)
-            for (int m = 0; m < nn; m++) actions[(size_t)g * nn + m] = m < e->h_nply[g] ? ac[(size_t)g * nn + e->h_start[g] + m] : (int16_t)-1;
+        std::fill(actions, actions + (size_t)G * nn, (int16_t)-1);     // a row per game, from the ply it started at
+        for_each_record(e, [&](int g, int, size_t si, size_t) { actions[si - e->h_start[g]] = ac[si]; });
     }
     if (out) {
         out->wins = w; out->losses = l; out->draws = dr; out->total = w + l + dr;

@@ -10,6 +10,7 @@ from . import parallel
 from ._capi import AZ_MAX_SIMULATIONS, Engine, check_threat_search, win_rule_name
 from .controller import device_index, make_batch_policy_value_fn, merge_batch_evaluators, model_kind
 from .mcts import check_solver, numpy_log_table
+from .options import apply_options
 from .self_play import check_resign
 
 
@@ -80,27 +81,13 @@ class ModelEvaluator:
         if self.seed is None:
             seed0 = parallel.broadcast_seed(seed0, dev)
         self.win_rule = win_rule_name(self.win_rule)
-        if eng.win_rule() != self.win_rule:
-            if eng.start_positions():
-                eng.clear_start_positions()                               # they were validated under the other rule
-            eng.set_win_rule(self.win_rule)
-        if self.start_positions is not None:
-            eng.set_start_positions(*self.start_positions, first=lo)      # lo is even (parallel.arena_block): no pair is torn apart
-        elif eng.start_positions():
-            eng.clear_start_positions()
         self.resign = check_resign(self.resign)
-        if self.resign is not None:
-            eng.set_resign(**self.resign)
-        elif eng.resign()["threshold"]:
-            eng.set_resign(0.0)
         self.solver = check_solver(self.solver, virtual_loss=self.virtual_loss, evaluator=self.evaluators)
         self.threat_search = check_threat_search(self.threat_search, self.solver)
-        if self.threat_search is None and eng.threat_search()[0]:
-            eng.set_threat_search(0)                      # before the solver it needs may go
-        if self.solver != eng.solver():
-            eng.set_solver(self.solver)
-        if self.threat_search is not None:
-            eng.set_threat_search(**self.threat_search)
+        # first=lo is even (parallel.arena_block): no pair of games from one start position is torn apart.  The arena has no
+        # playout cap, forced playouts or Gumbel root search: its roots are not noised.
+        apply_options(eng, win_rule=self.win_rule, start_positions=self.start_positions, first=lo, resign=self.resign,
+                      playout_cap=None, forced_playouts=None, gumbel=None, solver=self.solver, threat_search=self.threat_search)
         r = eng.arena(mine, seed0=seed0 + lo, temperature_table=T) if mine > 0 else {"wins": 0, "losses": 0, "draws": 0, "total": 0, "win_rate": 0.0}
         if world > 1:
             w, l, d = parallel.all_reduce_tally(r["wins"], r["losses"], r["draws"], dev, engine=eng)

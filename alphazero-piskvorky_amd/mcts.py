@@ -9,6 +9,7 @@ import numpy as np
 from . import constants as _c
 from ._capi import AZ_MAX_SIMULATIONS, FORCED_K_MAX, GUMBEL_DEFAULTS, GUMBEL_M_MAX, Engine, check_threat_search, win_rule_name
 from .controller import BatchPolicyValueFn, PolicyValueFn, device_index, model_kind, weights_version
+from .options import apply_options, check_combination, switched_on
 
 
 def numpy_log_table(S):
@@ -35,16 +36,8 @@ def check_solver(solver, subtree_reuse=False, virtual_loss=1, forced_playouts=No
     subtree reuse, virtual-loss batching, forced playouts, the Gumbel root search and evaluators outside the engine."""
     if not solver:
         return False
-    if subtree_reuse:
-        raise ValueError("the solver does not combine with subtree_reuse")
-    if virtual_loss != 1:
-        raise ValueError("the solver does not combine with virtual-loss batching")
-    if forced_playouts is not None:
-        raise ValueError("the solver does not combine with forced playouts")
-    if gumbel is not None:
-        raise ValueError("the solver does not combine with the Gumbel root search")
-    if evaluator is not None:
-        raise ValueError("the solver needs the engine's own net: it does not combine with an outside evaluator")
+    check_combination(switched_on(solver=True, subtree_reuse=subtree_reuse, virtual_loss=virtual_loss, forced_playouts=forced_playouts,
+                                  gumbel=gumbel, evaluator=evaluator), "solver")
     return True
 
 
@@ -63,14 +56,8 @@ def check_gumbel(gumbel, subtree_reuse=False, virtual_loss=1, forced_playouts=No
         raise ValueError(f"gumbel m must be in 1..{GUMBEL_M_MAX}, got {out['m']}")
     if not (0.0 <= out["c_visit"] < float("inf")) or not (0.0 < out["c_scale"] < float("inf")):
         raise ValueError(f"gumbel needs c_visit >= 0 and c_scale > 0, both finite, got {out['c_visit']} and {out['c_scale']}")
-    if subtree_reuse:
-        raise ValueError("the Gumbel root search does not combine with subtree_reuse")
-    if virtual_loss != 1:
-        raise ValueError("the Gumbel root search does not combine with virtual-loss batching")
-    if forced_playouts is not None:
-        raise ValueError("the Gumbel root search does not combine with forced playouts")
-    if evaluator is not None:
-        raise ValueError("the Gumbel root search needs the engine's own net: an outside evaluator returns priors, not logits")
+    check_combination(switched_on(gumbel=out, subtree_reuse=subtree_reuse, virtual_loss=virtual_loss, forced_playouts=forced_playouts,
+                                  evaluator=evaluator), "gumbel")
     return out
 
 
@@ -112,17 +99,16 @@ class MCTS:
         self._batch_engine = None             # run_many's own engine; run() and its one-slot engine are untouched by it
         self._batch_version = None
 
-    def _forced(self, eng):
-        """a new engine takes the searches' forced-playout setting"""
-        if self.forced_playouts is not None:
-            eng.set_forced_playouts(self.forced_playouts["k"], self.forced_playouts["prune"])
-        if self.gumbel is not None:
-            eng.set_gumbel(min(self.gumbel["m"], eng.nn), self.gumbel["c_visit"], self.gumbel["c_scale"])     # a board has n * n cells
-        if self.solver:
-            eng.set_solver(True)
-        if self.threat_search is not None:
-            eng.set_threat_search(**self.threat_search)
-        return eng
+    def _new_engine(self, n, k, slots, **evaluator):
+        """an engine of this object's own with the searches' options; evaluator: device and model of the net that evaluates"""
+        eng = Engine(n, k, self.num_simulations, slots, c_puct=self.c_puct, dirichlet_alpha=self.dirichlet_alpha,
+                     dirichlet_weight=self.dirichlet_weight, log_table=numpy_log_table(self.num_simulations),
+                     deep=self.num_simulations > AZ_MAX_SIMULATIONS, **evaluator)
+        if not self._external:
+            eng.set_virtual_loss(self.virtual_loss)
+        # the rule is the state's (_ruled); games, and with them start positions, resignation and the playout cap, are not played here
+        return apply_options(eng, win_rule="freestyle", start_positions=None, first=0, resign=None, playout_cap=None,
+                             forced_playouts=self.forced_playouts, gumbel=self.gumbel, solver=self.solver, threat_search=self.threat_search)
 
     @staticmethod
     def _state_rule(state):
@@ -145,10 +131,7 @@ class MCTS:
 
     def _eng_external(self, n, k):
         if self._engine is None or (self._engine.n, self._engine.k) != (n, k):
-            self._engine = Engine(n, k, self.num_simulations, 1, c_puct=self.c_puct, dirichlet_alpha=self.dirichlet_alpha,
-                                  dirichlet_weight=self.dirichlet_weight, log_table=numpy_log_table(self.num_simulations),
-                                  deep=self.num_simulations > AZ_MAX_SIMULATIONS)
-            self._forced(self._engine)
+            self._engine = self._new_engine(n, k, 1)
         return self._engine
 
     def _run_external(self, root_state, temperature, noise, u):
@@ -168,12 +151,7 @@ class MCTS:
     def _eng(self, n, k):
         ctrl = self.policy_value_fn.controller
         if self._engine is None or (self._engine.n, self._engine.k) != (n, k):
-            self._engine = Engine(n, k, self.num_simulations, 1, c_puct=self.c_puct,
-                                  dirichlet_alpha=self.dirichlet_alpha, dirichlet_weight=self.dirichlet_weight,
-                                  device=device_index(ctrl.device), log_table=numpy_log_table(self.num_simulations),
-                                  model=model_kind(ctrl.net), deep=self.num_simulations > AZ_MAX_SIMULATIONS)
-            self._engine.set_virtual_loss(self.virtual_loss)
-            self._forced(self._engine)
+            self._engine = self._new_engine(n, k, 1, device=device_index(ctrl.device), model=model_kind(ctrl.net))
             self._version = None
         ver = weights_version(ctrl.net)
         if ver != self._version:
@@ -217,13 +195,7 @@ class MCTS:
         if eng is None or (eng.n, eng.k) != (n, k) or eng.slots < slots:
             if eng is not None:
                 eng.close()
-            eng = self._batch_engine = Engine(n, k, self.num_simulations, slots, c_puct=self.c_puct,
-                                              dirichlet_alpha=self.dirichlet_alpha, dirichlet_weight=self.dirichlet_weight,
-                                              device=device_index(self.policy_value_fn.device),
-                                              log_table=numpy_log_table(self.num_simulations),
-                                              deep=self.num_simulations > AZ_MAX_SIMULATIONS)
-            eng.set_virtual_loss(self.virtual_loss)
-            self._forced(eng)
+            eng = self._batch_engine = self._new_engine(n, k, slots, device=device_index(self.policy_value_fn.device))
             self.policy_value_fn.attach(eng)
         return eng
 
@@ -239,12 +211,7 @@ class MCTS:
         if eng is None or (eng.n, eng.k) != (n, k) or eng.slots < slots:
             if eng is not None:
                 eng.close()
-            self._batch_engine = Engine(n, k, self.num_simulations, slots, c_puct=self.c_puct,
-                                        dirichlet_alpha=self.dirichlet_alpha, dirichlet_weight=self.dirichlet_weight,
-                                        device=device_index(ctrl.device), log_table=numpy_log_table(self.num_simulations),
-                                        model=model_kind(ctrl.net), deep=self.num_simulations > AZ_MAX_SIMULATIONS)
-            self._batch_engine.set_virtual_loss(self.virtual_loss)
-            self._forced(self._batch_engine)
+            self._batch_engine = self._new_engine(n, k, slots, device=device_index(ctrl.device), model=model_kind(ctrl.net))
             self._batch_version = None
         ver = weights_version(ctrl.net)
         if ver != self._batch_version:

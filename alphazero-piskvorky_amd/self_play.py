@@ -10,6 +10,7 @@ from . import parallel
 from ._capi import check_threat_search, AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine, playout_cap_permille, resign_permille, win_rule_name
 from .controller import BatchPolicyValueFn, device_index, model_kind
 from .mcts import check_forced_playouts, check_gumbel, check_solver, numpy_log_table
+from .options import apply_options, check_combination, switched_on
 
 
 def default_temperature_schedule(move: int) -> float:
@@ -126,40 +127,34 @@ class SelfPlayManager:
         # have no effect while it is set.
         if evaluator is not None and not isinstance(evaluator, BatchPolicyValueFn):
             raise TypeError("evaluator must be a controller.BatchPolicyValueFn (make_batch_policy_value_fn)")
-        if evaluator is not None and (subtree_reuse or leaf_symmetry):
-            raise ValueError("an external evaluator combines with neither subtree_reuse nor leaf_symmetry")
         self.evaluator = evaluator
         self.device = device
         self.mcts_params = mcts_params or {"num_simulations": 100}
         # opt-in playout cap randomisation: dict(fast_sims, full=0.25, train_on_fast=False); only the share `full` of the plies
         # gets num_simulations and root noise and becomes training examples, the rest is searched with fast_sims and moves
         # the game along (az_set_playout_cap).  Not with subtree_reuse or an external evaluator.
-        self.playout_cap = check_playout_cap(playout_cap, self.mcts_params.get("num_simulations", 100))
-        if self.playout_cap is not None and (subtree_reuse or evaluator is not None):
-            raise ValueError("a playout cap combines with neither subtree_reuse nor an external evaluator")
+        self.playout_cap = playout_cap
         self.last_playout_cap_stats = None    # playout_cap_stats() of this rank's games of the last episode (None while the cap is off)
         # opt-in forced playouts and policy target pruning: dict(k, prune=True); every noised root (with a playout cap: the full
         # plies') guarantees its children visits by the square root of their prior, and pi is made from the counts without
         # them (az_set_forced_playouts).  Not with subtree_reuse.  The records keep the raw visits and neither W nor the
         # priors, so the pruned share cannot be recomputed from them: the manager reports no statistics of it
         # (tools/forced_playouts_gain.py measures it on searched positions).
-        self.forced_playouts = check_forced_playouts(forced_playouts)
-        if self.forced_playouts is not None and subtree_reuse:
-            raise ValueError("forced playouts do not combine with subtree_reuse")
+        self.forced_playouts = forced_playouts
         # opt-in Gumbel root search: dict(m=16, c_visit=50.0, c_scale=1.0); every noised root (with a playout cap: the full plies')
         # samples m Gumbel-top candidates, searches them by sequential halving and records pi = softmax(logits + sigma(completed
         # Q)) (az_set_gumbel); the engine fills the game tapes with Gumbel draws.  Not with subtree_reuse, virtual_loss > 1,
         # forced_playouts or an external evaluator.
-        self.gumbel = check_gumbel(gumbel, subtree_reuse, virtual_loss, self.forced_playouts, evaluator)
+        self.gumbel = gumbel
         # opt-in MCTS-Solver: every search keeps proven wins, losses and draws in its tree; pi never spreads mass over refuted
         # moves while a better one is known, a proven root records an exact value (az_set_solver).  Not with subtree_reuse,
         # virtual_loss > 1, forced_playouts, gumbel or an external evaluator.  Whether it trains a stronger net per GPU hour
         # has not been measured.
-        self.solver = check_solver(solver, subtree_reuse, virtual_loss, self.forced_playouts, self.gumbel, evaluator)
+        self.solver = solver
         # opt-in root threat search, dict(max_depth=8, node_budget=256) or True: an exact forced-four search on every root before
         # the simulations, its proven wins and forced blocks premarked for the solver (az_set_threat_search).  Needs solver=True.
         # Whether it trains a stronger net per GPU hour has not been measured.
-        self.threat_search = check_threat_search(threat_search, self.solver)
+        self.threat_search = threat_search
         self.temperature_schedule = temperature_schedule
         self.concurrent_games = concurrent_games or _c.CONCURRENT_GAMES
         self.augmentation = augmentation      # 4 = the reference's rotations (self_play.py:94-108), 8 = full dihedral group, 1 = none
@@ -173,11 +168,26 @@ class SelfPlayManager:
         self.start_positions = start_positions    # opt-in: (boards, players, lasts); game g continues position g mod count instead of starting on the empty board
         # opt-in: dict(threshold, min_ply=0, playout=0.0); a game ends as a loss of the mover once the search value of a ply
         # falls below -threshold, except in the share `playout` of the games, which measure the false positives
-        self.resign = check_resign(resign)
+        self.resign = resign
         self.last_resign_stats = None         # resign_stats() of this rank's games of the last episode (None while resignation is off)
         self.gather_to = gather_to            # multi-rank: None = every rank receives all records (all-gather); r = only rank r does
         self.last_counters = None
         self._engine = None
+        self._check_options()
+
+    def _check_options(self):
+        """Every option in its checked form, and ValueError for a bad value or a combination the engine would refuse: at
+        construction, and again before every episode (the options are plain attributes)."""
+        self.win_rule = win_rule_name(self.win_rule)
+        self.resign = check_resign(self.resign)
+        self.playout_cap = check_playout_cap(self.playout_cap, self.mcts_params.get("num_simulations", 100))
+        self.forced_playouts = check_forced_playouts(self.forced_playouts)
+        self.gumbel = check_gumbel(self.gumbel)
+        self.solver = check_solver(self.solver)
+        self.threat_search = check_threat_search(self.threat_search)
+        check_combination(switched_on(subtree_reuse=self.subtree_reuse, virtual_loss=self.virtual_loss, leaf_symmetry=self.leaf_symmetry,
+                                      evaluator=self.evaluator, playout_cap=self.playout_cap, forced_playouts=self.forced_playouts,
+                                      gumbel=self.gumbel, solver=self.solver, threat_search=self.threat_search))
 
     def _eng(self, n, k, slots):
         p = self.mcts_params
@@ -234,6 +244,7 @@ class SelfPlayManager:
         device_replay.DeviceReplayBuffer.extend_packed to train without materialising Python tuples.
         Games are always played to the end here (max_plies is never passed), so no record carries the label of a cut
         game, z = 99 (include/az_engine.h), which the example kernels would hand on as a value target."""
+        self._check_options()
         n = self.controller.net.board_size
         k = min(_c.WIN_LENGTH, n)
         rank, world = parallel.rank_world()
@@ -255,47 +266,10 @@ class SelfPlayManager:
         if eng.trunk_mode() != self.trunk:
             eng.set_trunk_mode(self.trunk)
         T = np.array([float(self.temperature_schedule(m)) for m in range(n * n + 1)], dtype=np.float64)
-        self.win_rule = win_rule_name(self.win_rule)
-        if eng.win_rule() != self.win_rule:
-            if eng.start_positions():
-                eng.clear_start_positions()                               # they were validated under the other rule
-            eng.set_win_rule(self.win_rule)
-        if self.start_positions is not None:
-            eng.set_start_positions(*self.start_positions, first=lo)      # by global game id, like the seed
-        elif eng.start_positions():
-            eng.clear_start_positions()
-        self.resign = check_resign(self.resign)
-        if self.resign is not None:
-            eng.set_resign(**self.resign)
-        elif eng.resign()["threshold"]:
-            eng.set_resign(0.0)
-        self.last_resign_stats = None
-        self.playout_cap = check_playout_cap(self.playout_cap, sims)
-        if self.playout_cap is not None:
-            # the engine's export filter does the selection: the packed records below are the full plies' unless train_on_fast
-            eng.set_playout_cap(self.playout_cap["fast_sims"], self.playout_cap["full"],
-                                export_full_only=not self.playout_cap["train_on_fast"])
-        elif eng.playout_cap()["fast_sims"]:
-            eng.set_playout_cap(0)
-        self.last_playout_cap_stats = None
-        self.forced_playouts = check_forced_playouts(self.forced_playouts)
-        if self.forced_playouts is not None:
-            eng.set_forced_playouts(self.forced_playouts["k"], self.forced_playouts["prune"])
-        elif eng.forced_playouts()["k"]:
-            eng.set_forced_playouts(0.0)
-        self.gumbel = check_gumbel(self.gumbel, self.subtree_reuse, self.virtual_loss, self.forced_playouts, self.evaluator)
-        if self.gumbel is not None:
-            eng.set_gumbel(min(self.gumbel["m"], n * n), self.gumbel["c_visit"], self.gumbel["c_scale"])
-        elif eng.gumbel()["m"]:
-            eng.set_gumbel(0)
-        self.solver = check_solver(self.solver, self.subtree_reuse, self.virtual_loss, self.forced_playouts, self.gumbel, self.evaluator)
-        self.threat_search = check_threat_search(self.threat_search, self.solver)
-        if self.threat_search is None and eng.threat_search()[0]:
-            eng.set_threat_search(0)                      # before the solver it needs may go
-        if self.solver != eng.solver():
-            eng.set_solver(self.solver)
-        if self.threat_search is not None:
-            eng.set_threat_search(**self.threat_search)
+        apply_options(eng, win_rule=self.win_rule, start_positions=self.start_positions, first=lo, resign=self.resign,
+                      playout_cap=self.playout_cap, forced_playouts=self.forced_playouts, gumbel=self.gumbel, solver=self.solver,
+                      threat_search=self.threat_search)
+        self.last_resign_stats = self.last_playout_cap_stats = None
         if mine > 0:
             self.last_counters = eng.selfplay(mine, seed0=seed0 + lo, temperature_table=T)
             if self.resign is not None:

@@ -19,6 +19,7 @@ from .controller import NeuralNetworkController, make_batch_policy_value_fn
 from .evaluator import ModelEvaluator
 from .games import Gomoku
 from .net import GomokuNet
+from .options import option_from_flags
 from .promoter import ModelPromoter
 from .replay_buffer import ReplayBuffer
 from .self_play import SelfPlayManager
@@ -197,23 +198,12 @@ def main():
         forced_playouts = {"k": a.forced_playouts, "prune": not a.no_target_pruning}
     elif a.no_target_pruning:
         ap.error("--no-target-pruning needs --forced-playouts")
-    gumbel = None
-    if a.gumbel is not None:
-        gumbel = {"m": a.gumbel}
-        if a.gumbel_c_visit is not None:
-            gumbel["c_visit"] = a.gumbel_c_visit
-        if a.gumbel_c_scale is not None:
-            gumbel["c_scale"] = a.gumbel_c_scale
-    elif a.gumbel_c_visit is not None or a.gumbel_c_scale is not None:
-        ap.error("--gumbel-c-visit and --gumbel-c-scale need --gumbel")
-    threat_search = None
-    if a.threat_depth is not None:
-        threat_search = {"max_depth": a.threat_depth}
-        if a.threat_nodes is not None:
-            threat_search["node_budget"] = a.threat_nodes
+    gumbel = option_from_flags(ap.error, {"m": a.gumbel, "c_visit": a.gumbel_c_visit, "c_scale": a.gumbel_c_scale},
+                               "--gumbel-c-visit and --gumbel-c-scale need --gumbel")
+    threat_search = option_from_flags(ap.error, {"max_depth": a.threat_depth, "node_budget": a.threat_nodes},
+                                      "--threat-nodes needs --threat-depth")
+    if threat_search is not None:
         a.solver = True
-    elif a.threat_nodes is not None:
-        ap.error("--threat-nodes needs --threat-depth")
     start_positions = None
     if a.start_positions:
         with np.load(a.start_positions) as z:

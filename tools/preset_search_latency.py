@@ -2,13 +2,14 @@
 az_search_callback with a trivial evaluator, through the raw C-ABI, on a one-slot engine (MCTS.run's configuration).
 
   5x5 / S = 64     az_search runs the persistent search kernel; the callback never does
-  15x15 / S = 200  lock-step, the captured graph for az_search
+  15x15 / S = 200  lock-step, the captured graph for az_search; and Engine.net_eval (az_net_eval) of 1 and of 256 positions on
+                   a 256-slot engine: the tile-split trunk for the one, one full pass for the 256
 
     python tools/preset_search_latency.py --parent-lib <libaz_engine.so built from the parent commit>
 
 runs parent, this build, parent, this build per configuration (the parent twice: the spread between its two runs is what a
 difference is judged by), every leg a fresh process under `timeout -k 10` with the library selected through AZ_ENGINE_LIB, after
-20 warm-up calls; a host clock around each synchronising call.  Writes profiles/preset_search_path.json."""
+20 warm-up calls; a host clock around each synchronising call.  Writes --out (default profiles/preset_search_path.json)."""
 import argparse
 import ctypes as C
 import json
@@ -22,7 +23,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-CONFIGS = {"5x5": dict(n=5, k=4, S=64, calls=600, callback_calls=400), "15x15": dict(n=15, k=5, S=200, calls=400, callback_calls=300)}
+CONFIGS = {"5x5": dict(n=5, k=4, S=64, calls=600, callback_calls=400), "15x15": dict(n=15, k=5, S=200, calls=400, callback_calls=300, net_eval={1: 400, 256: 150})}
 LEGS = ("parent_1", "branch_1", "parent_2", "branch_2")
 WARMUP = 20
 
@@ -74,6 +75,22 @@ def run_leg(config, leg):
         if what == "az_search":
             row["az_search_persistent_kernel"] = e.persistent()
     e.close()
+    if "net_eval" in cfg:
+        e = az.Engine(n, k, S, 256)
+        e.load_weights(synthetic_state_dict(n), 0)
+        rs = np.random.RandomState(5)
+        boards = (rs.random_sample((256, nn)) < 0.2).astype(np.uint8) * rs.randint(1, 3, (256, nn)).astype(np.uint8)
+        players, lasts = np.ones(256, np.uint8), -np.ones(256, np.int16)
+        for count, calls in cfg["net_eval"].items():
+            ms = np.zeros(calls)
+            for i in range(-WARMUP, calls):
+                t = time.perf_counter()
+                out = e.net_eval(boards[:count], players[:count], lasts[:count])
+                if i >= 0:
+                    ms[i] = (time.perf_counter() - t) * 1e3
+            row[f"az_net_eval_{count}"] = dict(calls=calls, mean_ms=float(ms.mean()), median_ms=float(np.median(ms)), p10_ms=float(np.percentile(ms, 10)),
+                                               p90_ms=float(np.percentile(ms, 90)), value_bits=int(np.float32(out[2][0]).view(np.uint32)))
+        e.close()
     print(row, flush=True)
     return row
 
@@ -116,7 +133,7 @@ def main():
     for config in CONFIGS:
         if not all((config, leg) in by for leg in LEGS):
             continue
-        for what in ("az_search", "az_search_callback"):
+        for what in ["az_search", "az_search_callback"] + [f"az_net_eval_{c}" for c in CONFIGS[config].get("net_eval", ())]:
             par = [by[(config, leg)][what]["median_ms"] for leg in ("parent_1", "parent_2")]
             new = [by[(config, leg)][what]["median_ms"] for leg in ("branch_1", "branch_2")]
             summary[f"{config}/{what}"] = dict(parent_median_ms=par, this_build_median_ms=new, parent_spread_ms=abs(par[0] - par[1]),
