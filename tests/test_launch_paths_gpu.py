@@ -4,7 +4,10 @@ A. lanes wider than one k_refill chunk of 1024 slots (the second trip through it
 B. the three ways lane_plies launches a ply -- replayed graph, kernel by kernel (AZ_GRAPH=0), kernel by kernel with HIP
    events (az_set_profiling / AZ_PROFILE_EVENTS=1) -- on one episode, and the timing fields the events feed;
 C. one engine walked through every mode setter and back, against a fresh engine per mode: the graph cache (ply_graph keys
-   its graphs by the whole LaunchCtx) must never replay the previous mode's kernel sequence.
+   its graphs by the whole LaunchCtx) must never replay the previous mode's kernel sequence;
+E. one engine through the delta switch, its tile threshold, an option the delta path does not serve and a net_eval_delta call
+   (csrc/az_delta.h), against a fresh engine per configuration.  B and C hold a 15x15 entry too, whose plies launch
+   k_trunk_base / k_trunk_delta / k_trunk_rest, with delta_stats equal on every launch path and lane count.
 
 Records go by game id and games are seeded per id, so every layout, launch path and mode history must give identical
 episodes; every comparison is exact."""
@@ -212,6 +215,8 @@ B_CONFIGS = {
     "eval_cache_one_slot_persistent": dict(n=5, k=4, S=30, slots=1, engines=0, G=3, cut=0, cache=1024, oracle="B-persistent"),
     "persistent": dict(n=5, k=4, S=30, slots=7, engines=0, G=15, cut=0),
     "arena": dict(n=9, k=5, S=12, slots=6, engines=3, arena=6),
+    # 15x15, the plain net: the plies launch k_trunk_base once and k_trunk_delta / k_trunk_rest for every batch (csrc/az_delta.h)
+    "delta_15x15": dict(n=15, k=5, S=12, slots=6, engines=3, G=8, cut=3, delta=True),
 }
 B_SEED = 2024
 # cache_hits (and trunk_boards, which subtracts it) are a function of the episode only where one position is looked up or written
@@ -288,7 +293,7 @@ def _assert_b_same(ref, got, what, counters=LAUNCH_COUNTERS):
 def test_graph_eager_and_profiled_plies_give_one_episode(monkeypatch, name):
     cfg = B_CONFIGS[name]
     n, k, S = cfg["n"], cfg["k"], cfg["S"]
-    runs = {}
+    runs, delta = {}, {}
     for variant, env in (("graph", {}), ("eager", dict(AZ_GRAPH="0")), ("set_profiling", {}), ("env_profiled", dict(AZ_PROFILE_EVENTS="1"))):
         _clean_env(monkeypatch, **env)
         e = _b_engine(cfg)
@@ -296,6 +301,7 @@ def test_graph_eager_and_profiled_plies_give_one_episode(monkeypatch, name):
             e.set_profiling(True)
         profiled = variant in ("set_profiling", "env_profiled")
         runs[variant] = _b_play(e, cfg)
+        delta[variant] = e.delta_stats(by_tiles=True)
         _assert_b_path(cfg, e, runs[variant][2], profiled)
         if variant == "set_profiling":          # and off again: zeros, same records
             e.set_profiling(False)
@@ -322,6 +328,22 @@ def test_graph_eager_and_profiled_plies_give_one_episode(monkeypatch, name):
         tag = cfg.get("oracle") or ("B-9x9" if name in ("lockstep", "eval_cache") else "B-" + name)       # the cache and the slot count change no result
         ref = _oracle_games(tag, o, orc.Net(n, sd), n, B_SEED, range(cfg["G"]), cut=cfg["cut"])
         _assert_oracle_games(runs["graph"][0], ref, name)
+    if cfg.get("delta"):
+        # the same episode on one lane of six slots: every lane count owns its base activations, flags and counters
+        _clean_env(monkeypatch)
+        e = _b_engine(dict(cfg, engines=1))
+        assert e.lanes() == 1
+        runs["one lane"] = _b_play(e, cfg)
+        delta["one lane"] = e.delta_stats(by_tiles=True)
+        e.close()
+        _assert_b_same(runs["graph"], runs["one lane"], f"{name}: three lanes vs one", counters=WORK + ("trunk_boards",))
+        c = runs["graph"][2]
+        assert delta["graph"]["delta"] > 0 and delta["graph"]["delta"] + delta["graph"]["full"] == c["trunk_boards"]
+        assert delta["graph"]["base"] == 2 * c["plies"]
+        for variant, st in delta.items():
+            assert st == delta["graph"], f"{name}: delta_stats: graph vs {variant}"
+    else:
+        assert all(st == dict(delta=0, full=0, tiles=0, base=0, by_tiles=[0] * 16) for st in delta.values())
 
 
 def test_stream_priority_and_host_thread_switches_keep_the_records(monkeypatch):
@@ -348,6 +370,9 @@ def test_stream_priority_and_host_thread_switches_keep_the_records(monkeypatch):
 C_CONFIGS = {
     "9x9": dict(n=9, k=5, S=16, slots=8, engines=2, G=8, cut=5),
     "5x5": dict(n=5, k=4, S=24, slots=6, engines=0, G=6, cut=0),
+    # 15x15, the plain net: the default mode and every mode switched off again evaluate leaves as deltas (csrc/az_delta.h); one
+    # arena game, which runs to its end on a board of 225 cells
+    "15x15": dict(n=15, k=5, S=12, slots=6, engines=3, G=6, cut=3, arena=1, delta=True),
 }
 C_SEED = 7300
 DEFAULT_MODE = dict(w0="first", w1=None, cache=0, vl=1, leaf_sym=False, trunk="f32", reuse=False)
@@ -426,8 +451,18 @@ def test_one_engine_through_the_modes_and_back(monkeypatch, name):
         assert (kept.persistent() == 0) == lockstep, step
         fresh = _c_fresh(cfg, mode, weights)
         want = _episode(fresh, G, C_SEED, cut)
+        want_delta = fresh.delta_stats(by_tiles=True)
         fresh.close()
         _assert_same_episode(want, ep, f"{name}: {step}: fresh engine vs kept engine", counters=WORK + ("trunk_launches", "steps", "duplicate_leaves"))
+        # delta evaluation: in the modes it serves, counted from zero in every episode; nothing of it in the others
+        st = kept.delta_stats(by_tiles=True)
+        if cfg.get("delta") and mode["vl"] == 1 and not mode["leaf_sym"] and mode["trunk"] == "f32" and not mode["reuse"]:
+            assert st["delta"] > 0 and st["base"] == 2 * ep["c"]["plies"] and st["delta"] + st["full"] == ep["c"]["trunk_boards"], step
+            assert sum(st["by_tiles"]) == st["delta"] and sum(t * x for t, x in enumerate(st["by_tiles"])) == st["tiles"], step
+            if not mode["cache"]:              # (with the cache the evaluations left over depend on the order of its writes: CACHE_ORDER_COUNTERS)
+                assert st == want_delta, f"{name}: {step}: delta_stats: fresh engine vs kept engine"
+        else:
+            assert st == want_delta == dict(delta=0, full=0, tiles=0, base=0, by_tiles=[0] * 16), step
         if mode["trunk"] == "f32":
             tag = ("C", name, mode["w0"], mode["vl"], mode["leaf_sym"], mode["reuse"])
             ref = _oracle_games(tag, _c_oracle(cfg, mode), onets[mode["w0"]], n, C_SEED, range(G), cut=cut)
@@ -465,9 +500,10 @@ def test_one_engine_through_the_modes_and_back(monkeypatch, name):
     fresh = _c_fresh(cfg, mode, weights)
     o = _c_oracle(cfg, mode)
     T = orc.arena_T_table(n * n)
-    a, fa = kept.arena(4, seed0=C_SEED, temperature_table=T), fresh.arena(4, seed0=C_SEED, temperature_table=T)
+    A = cfg.get("arena", 4)
+    a, fa = kept.arena(A, seed0=C_SEED, temperature_table=T), fresh.arena(A, seed0=C_SEED, temperature_table=T)
     _assert_same_arena(fa, a, f"{name}: arena")
-    _assert_oracle_arena(a, _oracle_arena(("C-arena", name), o, onets["second"], onets["first"], n, C_SEED, range(4)), f"{name}: arena")
+    _assert_oracle_arena(a, _oracle_arena(("C-arena", name), o, onets["second"], onets["first"], n, C_SEED, range(A)), f"{name}: arena")
     board, pl, last, temp, noise, u = _c_position(cfg)
     for slot, tag in ((0, "second"), (1, "first")):
         r, fr = kept.search(board, pl, last, temp, noise, u, slot=slot), fresh.search(board, pl, last, temp, noise, u, slot=slot)
@@ -561,3 +597,78 @@ def test_searches_on_a_used_engine_equal_a_fresh_engine(monkeypatch):
                 assert np.array_equal(one[key], batch[key][0]), f"search vs search_batch of one: position {i}, slot {slot}: {key}"
             assert one["action"] == int(batch["action"][0])
             assert int(one["N"].sum()) == S
+
+
+# ------------------------------------------------------------------------------------------------
+# E. one engine through the delta switch
+# ------------------------------------------------------------------------------------------------
+def _e_leaves(n):
+    """a root and four of its leaves for net_eval_delta: one stone in a corner, two stones, three, and nine (evaluated in full)"""
+    root = np.zeros(n * n, np.uint8)
+    root[[7 * n + 7, 3 * n + 3]] = 1; root[[7 * n + 8, 11 * n + 2]] = 2
+    boards, players, lasts = [], [], []
+    for cells in ([0], [6 * n + 6, n * n - 1], [8 * n + 8, 14 * n, 2 * n + 9], [4 * n + j for j in range(9)]):
+        b, pl = root.copy(), 1
+        for c in cells:
+            b[c] = pl
+            pl = 3 - pl
+        boards.append(b); players.append(pl); lasts.append(cells[-1])
+    return root, 1, np.stack(boards), np.array(players, np.uint8), np.array(lasts, np.int16)
+
+
+def test_one_engine_through_the_delta_switch_and_back(monkeypatch):
+    """Consecutive episodes of the same seeds on one engine, the delta switch, its tile threshold and an option it does not serve
+    changed in between (set_delta_eval and delta_max_tiles are rows of the graph key).  Every episode is the one a fresh engine
+    plays in that configuration, records as bytes and delta_stats alike: the counters restart, the graph is captured again,
+    and a net_eval_delta call leaves nothing behind in the lane's base activations, flags and counters."""
+    _clean_env(monkeypatch)
+    cfg = B_CONFIGS["delta_15x15"]
+    n, k, S, G, cut = cfg["n"], cfg["k"], cfg["S"], cfg["G"], cfg["cut"]
+    zero = dict(delta=0, full=0, tiles=0, base=0, by_tiles=[0] * 16)
+
+    def configure(e, on, tiles, vl):
+        e.set_delta_eval(on)
+        assert e.delta_max_tiles(tiles) == tiles
+        e.set_virtual_loss(vl)
+
+    def fresh(on, tiles, vl):
+        e = _b_engine(cfg)
+        configure(e, on, tiles, vl)
+        ep = _episode(e, G, B_SEED, cut)
+        st = e.delta_stats(by_tiles=True)
+        e.close()
+        return ep, st
+
+    kept = _b_engine(cfg)
+    assert kept.lanes() == cfg["engines"] and kept.delta_eval() and kept.delta_max_tiles() == 12
+    ref = _oracle_games("B-delta_15x15", orc.Oracle(n, k, S), orc.Net(n, _b_weights(cfg)[0]), n, B_SEED, range(G), cut=cut)
+    stats = []
+    steps = (("switch on", True, 12, 1, False), ("switch off", False, 12, 1, False), ("threshold 3", True, 3, 1, False),
+             ("threshold 12 again", True, 12, 1, False), ("virtual loss 4", True, 12, 4, False), ("virtual loss 1 again", True, 12, 1, False),
+             ("after a net_eval_delta call", True, 12, 1, True))
+    for step, on, tiles, vl, call in steps:
+        configure(kept, on, tiles, vl)
+        if call:
+            root, pl, boards, players, lasts = _e_leaves(n)
+            got = kept.net_eval_delta(root, pl, boards, players, lasts)
+            want = kept.net_eval(boards, players, lasts)
+            for x, y in zip(got[:3], want):
+                assert np.array_equal(x.view(np.uint32), y.view(np.uint32)), f"{step}: net_eval_delta vs net_eval"
+            assert (got[3][:3] > 0).all() and got[3][3] == -1
+        ep = _episode(kept, G, B_SEED, cut)
+        st = kept.delta_stats(by_tiles=True)
+        want_ep, want_st = fresh(on, tiles, vl)
+        _assert_same_episode(want_ep, ep, f"{step}: fresh engine vs kept engine", counters=LAUNCH_COUNTERS)
+        for key in ep["rec"]:
+            assert ep["rec"][key].tobytes() == want_ep["rec"][key].tobytes(), f"{step}: {key}"
+        assert st == want_st, f"{step}: delta_stats: kept engine {st}, fresh engine {want_st}"
+        if vl == 1:
+            _assert_oracle_games(ep, ref, step)
+        stats.append(st)
+    on12, off, on3, back12, vl4, vl1, called = stats
+    assert off == vl4 == zero                                    # the switch off, and an option the path does not serve
+    assert on12 == back12 == vl1 == called and on12["delta"] > 0 and on12["base"] == 2 * ep["c"]["plies"]
+    # threshold 3: the same evaluations, those above 3 tiles in full (an interior depth-1 leaf has 4)
+    assert on3["delta"] + on3["full"] == on12["delta"] + on12["full"] and on3["full"] > on12["full"] and on3["delta"] > 0
+    assert on3["by_tiles"][:4] == on12["by_tiles"][:4] and not any(on3["by_tiles"][4:])
+    kept.close()
