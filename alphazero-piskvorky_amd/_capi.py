@@ -37,6 +37,7 @@ EXPORTS = [
     "az_resign_mix", "az_resign_exempt",
     "az_set_playout_cap", "az_get_playout_cap", "az_playout_cap_full", "az_selfplay_sims", "az_selfplay_export_count",
     "az_set_forced_playouts", "az_get_forced_playouts", "az_forced_prune",
+    "az_set_selection", "az_get_selection", "az_selection_tables",
     "az_set_gumbel", "az_get_gumbel", "az_gumbel_schedule", "az_gumbel_target", "az_gumbel_vmix", "az_rng_selfplay_tape_gumbel",
     "az_set_external_evaluator", "az_get_external_evaluator", "az_ext_capacity", "az_ext_stats",
     "az_set_solver", "az_get_solver", "az_last_proof", "az_selfplay_proofs", "az_solver_counts", "az_solver_stops",
@@ -167,6 +168,10 @@ def lib():
             L.az_get_forced_playouts.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
             L.az_forced_prune.argtypes = [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.az_forced_prune.restype = C.c_int64
+        if hasattr(L, "az_set_selection"):
+            L.az_set_selection.argtypes = [C.c_void_p, C.c_int] + [C.c_double] * 4
+            L.az_get_selection.argtypes = [C.c_void_p, C.POINTER(C.c_int)] + [C.POINTER(C.c_double)] * 4
+            L.az_selection_tables.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
         if hasattr(L, "az_set_gumbel"):
             L.az_set_gumbel.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
             L.az_get_gumbel.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -296,6 +301,41 @@ def forced_prune(k, c_puct, visits, W, prior):
     if removed < 0:
         raise ValueError(f"az_forced_prune refused its arguments (k {k} in (0, {FORCED_K_MAX:g}], counts 0..65534 with at least one visit)")
     return out, removed
+
+
+# az_set_selection: the keys of the option with their defaults, and the closed range of each (None = no upper bound)
+SELECTION_DEFAULTS = dict(fpu=0.2, fpu_root=0.0, cpuct_base=19652.0, cpuct_factor=0.0)
+SELECTION_RANGES = dict(fpu=(0.0, 2.0), fpu_root=(0.0, 2.0), cpuct_base=(1.0, None), cpuct_factor=(0.0, 16.0))
+SELECTION_MASS_STEPS = 4096
+
+
+def check_selection(selection):
+    """The option as the seams keep it: None (off), or a dict over fpu, fpu_root, cpuct_base and cpuct_factor completed with
+    the defaults, every value a finite float inside its range (ValueError otherwise; no engine is touched)."""
+    if selection is None or selection is False:
+        return None
+    if selection is True:
+        selection = {}
+    if not isinstance(selection, dict) or set(selection) - set(SELECTION_DEFAULTS):
+        raise ValueError(f"selection takes a dict over {sorted(SELECTION_DEFAULTS)}, got {selection!r}")
+    out = dict(SELECTION_DEFAULTS)
+    out.update({k: float(v) for k, v in selection.items()})
+    for k, (lo, hi) in SELECTION_RANGES.items():
+        if not (np.isfinite(out[k]) and out[k] >= lo and (hi is None or out[k] <= hi)):
+            raise ValueError(f"selection {k} must be finite and in [{lo:g}, {'inf' if hi is None else format(hi, 'g')}], got {out[k]}")
+    return out
+
+
+def selection_tables(c_puct, cpuct_base, cpuct_factor, S):
+    """The two tables of the selection rule exactly as an engine with S simulations uploads them (az_selection_tables; needs no
+    GPU): (cpuct float64[S + 2], mass float64[4097])."""
+    cp = np.zeros(int(S) + 2, np.float64)
+    mass = np.zeros(SELECTION_MASS_STEPS + 1, np.float64)
+    rc = lib().az_selection_tables(float(c_puct), float(cpuct_base), float(cpuct_factor), int(S), _p(cp), _p(mass))
+    if rc:
+        raise ValueError(f"az_selection_tables refused its arguments (c_puct {c_puct}, cpuct_base {cpuct_base} >= 1, "
+                         f"cpuct_factor {cpuct_factor} in [0, 16], S {S} in 1..{AZ_DEEP_MAX_SIMULATIONS})")
+    return cp, mass
 
 
 WIN_RULES = {"freestyle": 0, "exact": 1}                       # az_set_win_rule: AZ_RULE_*
@@ -933,6 +973,22 @@ class Engine:
         k, p = C.c_double(0.0), C.c_int(0)
         self._check(lib().az_get_forced_playouts(self.h, C.byref(k), C.byref(p)), "az_get_forced_playouts")
         return dict(k=float(k.value), prune=bool(p.value))
+
+    # ---- selection rule ----
+    def set_selection(self, fpu=0.2, fpu_root=0.0, cpuct_base=19652.0, cpuct_factor=0.0, on=True):
+        """Opt-in: an unvisited child is worth its parent's value less fpu * sqrt(visited prior mass) (fpu_root at the root)
+        instead of 0, and c_puct grows with the parent's count, c_puct + cpuct_factor * log((N + cpuct_base + 1) / cpuct_base).
+        on=False switches it off.  While it is on every board size runs the lock-step kernels.  See include/az_engine.h."""
+        self._check(lib().az_set_selection(self.h, 1 if on else 0, float(fpu), float(fpu_root), float(cpuct_base), float(cpuct_factor)),
+                    "az_set_selection")
+
+    def selection(self):
+        """The setting: dict(on, fpu, fpu_root, cpuct_base, cpuct_factor); the parameters are the last ones set (az_get_selection)."""
+        on = C.c_int(0)
+        v = [C.c_double(0.0) for _ in range(4)]
+        self._check(lib().az_get_selection(self.h, C.byref(on), *[C.byref(x) for x in v]), "az_get_selection")
+        return dict(on=bool(on.value), fpu=float(v[0].value), fpu_root=float(v[1].value), cpuct_base=float(v[2].value),
+                    cpuct_factor=float(v[3].value))
 
     # ---- win rule ----
     def set_win_rule(self, rule):

@@ -148,6 +148,10 @@ struct az_engine {
     int gumbel_m = 0;
     double gumbel_cv = 50.0, gumbel_cs = 1.0;
     DevBuf gumbel_seq;
+    // az_set_selection: 0 = off; the parameters stay as last set; the two tables live on the device while it is on
+    int sel_on = 0;
+    double sel_fpu = 0.0, sel_fpu_root = 0.0, sel_base = 19652.0, sel_factor = 0.0;
+    DevBuf sel_cpuct, sel_mass;
     // az_set_solver: 0 = off; the root status of every record, and what az_last_proof hands out (the root rows and root
     // statuses of the last az_search / az_search_batch, occupied cells 0)
     int solver = 0;
@@ -325,7 +329,7 @@ static int upload(az_engine *e, DevBuf &b, const void *src, size_t bytes)
 // its setting ON calls refuse_conflicts; the first row with an active partner names the error.
 // ------------------------------------------------------------------------------------------------
 enum Setting {
-    SET_REUSE, SET_VL, SET_VL_KERNEL, SET_SYMMETRY, SET_EXT, SET_CAP, SET_FORCED, SET_GUMBEL, SET_SOLVER,
+    SET_REUSE, SET_VL, SET_VL_KERNEL, SET_SYMMETRY, SET_EXT, SET_CAP, SET_FORCED, SET_GUMBEL, SET_SOLVER, SET_SELECTION,
     SET_SYNTHETIC, SET_NO_NET          // facts of az_config: the synthetic evaluator; any evaluator but the net
 };
 static const struct { Setting a, b; const char *message; } g_conflicts[] = {
@@ -347,6 +351,9 @@ static const struct { Setting a, b; const char *message; } g_conflicts[] = {
     {SET_SOLVER, SET_GUMBEL, "the solver and the Gumbel root search cannot be combined"},
     {SET_SOLVER, SET_EXT, "the solver and the external evaluator cannot be combined"},
     {SET_SOLVER, SET_SYNTHETIC, "the solver and the synthetic evaluator cannot be combined"},
+    {SET_SELECTION, SET_REUSE, "the selection rule and subtree reuse cannot be combined (a retained root has no fresh value)"},
+    {SET_SELECTION, SET_SOLVER, "the selection rule and the solver cannot be combined"},
+    {SET_SELECTION, SET_GUMBEL, "the selection rule and the Gumbel root search cannot be combined"},
 };
 
 // bit s = setting s is on.  Virtual-loss batching has two: more than one leaf per batch, and the batched tree kernel being in
@@ -354,7 +361,7 @@ static const struct { Setting a, b; const char *message; } g_conflicts[] = {
 static unsigned active_settings(const az_engine *e)
 {
     const bool on[] = {e->reuse != 0, e->vl > 1, e->vl > 1 || e->vl_kernel, e->leaf_symmetry != 0, e->ext.on, e->cap_fast != 0,
-                       e->forced_k > 0.0, e->gumbel_m > 0, e->solver != 0,
+                       e->forced_k > 0.0, e->gumbel_m > 0, e->solver != 0, e->sel_on != 0,
                        e->cfg.eval_kind == AZ_EVAL_SYNTHETIC, e->cfg.eval_kind != AZ_EVAL_NET};
     unsigned m = 0;
     for (int s = 0; s <= SET_NO_NET; s++) m |= on[s] ? 1u << s : 0u;
@@ -849,6 +856,7 @@ static int create_engine(const az_config *cfg, az_engine **out, bool deep)
         d.forced_k = 0.0; d.forced_prune = 0;
         d.gumbel_m = 0; d.gumbel_cv = 0.0; d.gumbel_cs = 0.0; d.gumbel_seq = nullptr; d.root_logits = nullptr; d.root_v = nullptr;
         d.proof = nullptr; d.proof_buf = nullptr; d.root_proof = nullptr; d.rec_proof = nullptr; d.proof_stops = nullptr;
+        d.sel_cpuct = nullptr; d.sel_mass = nullptr; d.sel_fpu = 0.0; d.sel_fpu_root = 0.0;
         d.s_budget = (int *)L.budget.p; d.cp_board = (u64 *)L.cp_board.p; d.cp_state = (int *)L.cp_state.p;
         if (!rc) rc = alloc_items(e, L, 1);
     }
@@ -938,7 +946,7 @@ extern "C" void az_destroy(az_engine *e)
                         &e->rec_planes, &e->rec_last, &e->rec_action, &e->rec_mover, &e->rec_pi, &e->rec_visits, &e->g_nply,
                         &e->g_result, &e->src_index, &e->rec_value, &e->g_cross, &e->cache, &e->start_tab, &e->bt_cells, &e->bt_players, &e->bt_lasts, &e->bt_T,
                         &e->bt_zero_off, &e->bt_visits, &e->bt_W, &e->bt_prior, &e->bt_pi, &e->bt_action, &e->ext.map, &e->ext.count, &e->gumbel_seq, &e->rec_proof, &e->rec_threat,
-                        &e->cb_planes, &e->cb_policy, &e->cb_value};
+                        &e->cb_planes, &e->cb_policy, &e->cb_value, &e->sel_cpuct, &e->sel_mass};
     for (DevBuf *b : shared) dev_free(*b);
     for (int s = 0; s < 2; s++) {
         PackedNet &p = e->net[s];
@@ -1230,6 +1238,11 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
         // the solver is for every search; the slot's status arrays were put into the state by az_set_solver
         d.proof = e->solver ? d.proof_buf : nullptr;
         d.rec_proof = e->solver ? (signed char *)e->rec_proof.p : nullptr;
+        // the selection rule is for every search as well; its tables and root_v were put up by az_set_selection
+        d.sel_cpuct = e->sel_on ? (const double *)e->sel_cpuct.p : nullptr;
+        d.sel_mass = e->sel_on ? (const double *)e->sel_mass.p : nullptr;
+        d.sel_fpu = e->sel_on ? e->sel_fpu : 0.0;
+        d.sel_fpu_root = e->sel_on ? e->sel_fpu_root : 0.0;
     });
     e->episode_solver = e->solver;
     e->solver_stops = 0;
@@ -1239,7 +1252,7 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
     const bool capped = !sp.preset && !sp.arena && e->cap_fast > 0;
     // persistent search kernel: plain net or synthetic evaluator, the reference's sequential search, trees that fit into LDS
     e->persist_gp = 0;
-    if (e->persist_allowed && !ext && !e->vl_kernel && !capped && !e->threat_depth && e->trunk_mode == AZ_TRUNK_F32) {
+    if (e->persist_allowed && !ext && !e->vl_kernel && !capped && !e->threat_depth && !e->sel_on && e->trunk_mode == AZ_TRUNK_F32) {
         const int synth = e->cfg.eval_kind == AZ_EVAL_SYNTHETIC ? 1 : 0;
         const int S = e->cfg.num_simulations;
         if (!sp.arena && (!sp.preset || sp.batch) && e->ops->search_prepare(S, 2, synth, e->cfg.model, e->solver)) e->persist_gp = 2;
@@ -2125,6 +2138,70 @@ extern "C" int64_t az_forced_prune(double k, double c_puct, int count, const int
         removed += visits[c] - out[c];
     }
     return removed;
+}
+
+// ---- selection rule: first-play urgency and visit-dependent c_puct ----
+// the two tables as the engine uploads them: cpuct[i] = c(i) for i = 0..S+1, mass[i] = sqrt(i / 4096) for i = 0..4096
+static void selection_tables(double c_puct, double base, double factor, int count, double *cpuct, double *mass)
+{
+    // factor = 0 gives c_puct exactly: 0 * log(x) is +0 for every finite log
+    for (int i = 0; i < count; i++) cpuct[i] = c_puct + factor * std::log(((double)i + base + 1.0) / base);
+    for (int i = 0; i <= SEL_MASS_STEPS; i++) mass[i] = std::sqrt((double)i / (double)SEL_MASS_STEPS);
+}
+
+static bool selection_args_ok(double fpu, double fpu_root, double base, double factor)
+{
+    return std::isfinite(fpu) && fpu >= 0.0 && fpu <= 2.0 && std::isfinite(fpu_root) && fpu_root >= 0.0 && fpu_root <= 2.0 &&
+           std::isfinite(factor) && factor >= 0.0 && factor <= 16.0 && std::isfinite(base) && base >= 1.0;
+}
+
+extern "C" int az_selection_tables(double c_puct, double cpuct_base, double cpuct_factor, int S, double *cpuct, double *mass)
+{
+    if (!std::isfinite(c_puct) || !selection_args_ok(0.0, 0.0, cpuct_base, cpuct_factor) || S < 1 || S > AZ_DEEP_MAX_SIMULATIONS ||
+        !cpuct || !mass)
+        return AZ_ERR_INVALID;
+    selection_tables(c_puct, cpuct_base, cpuct_factor, S + 2, cpuct, mass);
+    return AZ_OK;
+}
+
+extern "C" int az_set_selection(az_engine *e, int on, double fpu, double fpu_root, double cpuct_base, double cpuct_factor)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_selection: an episode is open (az_selfplay_end first)");
+    if (!on) {
+        e->sel_on = 0;
+        return AZ_OK;
+    }
+    if (on != 1 || !selection_args_ok(fpu, fpu_root, cpuct_base, cpuct_factor))
+        return fail(e, AZ_ERR_INVALID, "az_set_selection: on %d (0 / 1), fpu %g and fpu_root %g (in [0, 2]), cpuct_base %g (>= 1), cpuct_factor %g (in [0, 16])",
+                    on, fpu, fpu_root, cpuct_base, cpuct_factor);
+    if (refuse_conflicts(e, SET_SELECTION)) return AZ_ERR_INVALID;
+    DEVICE_GUARD(e);
+    // sized like sqrt_table (S + 3 entries, the last one never read) so that every index the sqrt takes is good for c(count) too
+    const int S = e->cfg.num_simulations;
+    std::vector<double> ct((size_t)S + 3), mt((size_t)SEL_MASS_STEPS + 1);
+    selection_tables(e->cfg.c_puct, cpuct_base, cpuct_factor, S + 3, ct.data(), mt.data());
+    int rc = upload(e, e->sel_cpuct, ct.data(), ct.size() * sizeof(double));
+    if (!rc) rc = upload(e, e->sel_mass, mt.data(), mt.size() * sizeof(double));
+    for (Lane &L : e->lanes)
+        if (!rc) rc = dev_alloc(e, L.root_v, (size_t)L.d.B * sizeof(float));
+    if (rc) return rc;
+    HIPCHECK(e, hipStreamSynchronize(e->stream));
+    for (Lane &L : e->lanes) L.d.root_v = (float *)L.root_v.p;
+    each_state(e, [&](DevState &d) { (void)d; });        // refresh the item views
+    e->sel_on = 1; e->sel_fpu = fpu; e->sel_fpu_root = fpu_root; e->sel_base = cpuct_base; e->sel_factor = cpuct_factor;
+    return AZ_OK;
+}
+
+extern "C" int az_get_selection(const az_engine *e, int *on, double *fpu, double *fpu_root, double *cpuct_base, double *cpuct_factor)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (on) *on = e->sel_on;
+    if (fpu) *fpu = e->sel_fpu;
+    if (fpu_root) *fpu_root = e->sel_fpu_root;
+    if (cpuct_base) *cpuct_base = e->sel_base;
+    if (cpuct_factor) *cpuct_factor = e->sel_factor;
+    return AZ_OK;
 }
 
 // ---- Gumbel root search: sequential halving and completed-Q policy targets ----

@@ -87,6 +87,17 @@ void step(const LaunchCtx &c, int rootN, int do_select)
         else hipLaunchKernelGGL((k_step<N, false, false, true>), g, b, (size_t)(c.d.S + 2) * sizeof(double), c.stream, c.d, rootN, do_select);
         return;
     }
+    if (c.d.sel_cpuct) {                                       // az_set_selection (never with the solver): the SEL kernels
+        const size_t lds = c.d.S > DEFAULT_MAX_S ? 0 : (size_t)(c.d.S + 2) * sizeof(double);
+        if (c.d.S > DEFAULT_MAX_S) {
+            if (c.synthetic) hipLaunchKernelGGL((k_step<N, true, true, false, true, SelLevel>), g, b, lds, c.stream, c.d, rootN, do_select, SelLevel{});
+            else hipLaunchKernelGGL((k_step<N, false, true, false, true, SelLevel>), g, b, lds, c.stream, c.d, rootN, do_select, SelLevel{});
+        } else {
+            if (c.synthetic) hipLaunchKernelGGL((k_step<N, true, false, false, true, SelLevel>), g, b, lds, c.stream, c.d, rootN, do_select, SelLevel{});
+            else hipLaunchKernelGGL((k_step<N, false, false, false, true, SelLevel>), g, b, lds, c.stream, c.d, rootN, do_select, SelLevel{});
+        }
+        return;
+    }
     if (c.d.S > DEFAULT_MAX_S) {
         if (c.synthetic) hipLaunchKernelGGL((k_step<N, true, true>), g, b, 0, c.stream, c.d, rootN, do_select);
         else hipLaunchKernelGGL((k_step<N, false, true>), g, b, 0, c.stream, c.d, rootN, do_select);
@@ -102,9 +113,20 @@ void step(const LaunchCtx &c, int rootN, int do_select)
 void step_vl(const LaunchCtx &c, int sims_done, int nb_next)
 {
     dim3 g((c.d.B + 3) / 4), b(256);
+    if (c.d.sel_cpuct) {                                       // az_set_selection: the SEL kernels
+        if (c.d.S > DEFAULT_MAX_S) {
+            if (c.synthetic) hipLaunchKernelGGL((k_step_vl<N, true, true, true, SelLevel, unsigned char *>), g, b, 0, c.stream, c.d, sims_done, nb_next, SelLevel{}, c.inflight);
+            else hipLaunchKernelGGL((k_step_vl<N, false, true, true, SelLevel, unsigned char *>), g, b, 0, c.stream, c.d, sims_done, nb_next, SelLevel{}, c.inflight);
+            return;
+        }
+        const size_t lds = (size_t)(c.d.S + 2) * sizeof(double);
+        if (c.synthetic) hipLaunchKernelGGL((k_step_vl<N, true, false, true, SelLevel>), g, b, lds, c.stream, c.d, sims_done, nb_next, SelLevel{});
+        else hipLaunchKernelGGL((k_step_vl<N, false, false, true, SelLevel>), g, b, lds, c.stream, c.d, sims_done, nb_next, SelLevel{});
+        return;
+    }
     if (c.d.S > DEFAULT_MAX_S) {
-        if (c.synthetic) hipLaunchKernelGGL((k_step_vl<N, true, true, unsigned char *>), g, b, 0, c.stream, c.d, sims_done, nb_next, c.inflight);
-        else hipLaunchKernelGGL((k_step_vl<N, false, true, unsigned char *>), g, b, 0, c.stream, c.d, sims_done, nb_next, c.inflight);
+        if (c.synthetic) hipLaunchKernelGGL((k_step_vl<N, true, true, false, unsigned char *>), g, b, 0, c.stream, c.d, sims_done, nb_next, c.inflight);
+        else hipLaunchKernelGGL((k_step_vl<N, false, true, false, unsigned char *>), g, b, 0, c.stream, c.d, sims_done, nb_next, c.inflight);
         return;
     }
     const size_t lds = (size_t)(c.d.S + 2) * sizeof(double);   // sqrt table

@@ -144,7 +144,33 @@ struct DevState {
     unsigned long long *threat_stat;   // [B][THREAT_STATS] roots proven WIN / LOSS, block-only roots, exhausted searches, nodes
     signed char *rec_threat;       // [G*nn] threat_depth of every record's root, written by k_move
     int threat_max_depth, threat_budget;
+    // --- opt-in selection rule (az_set_selection): sel_cpuct = nullptr with the option off, nothing below is read then.  The SEL
+    // tree kernels score an unvisited child V_X - r_X mass_table[visited prior mass] and use c(count) = sel_cpuct[count]; they
+    // keep the root's value in root_v (above).  k_move reads sel_cpuct in the pruning pass only ---
+    const double *sel_cpuct;       // [S+3] c_puct + factor * log((i + base + 1) / base), beside sqrt_table and indexed like it
+    const double *sel_mass;        // [SEL_MASS_STEPS + 1] sqrt(i / SEL_MASS_STEPS)
+    double sel_fpu, sel_fpu_root;  // r_X below the root / at the root
 };
+constexpr int SEL_MASS_STEPS = 4096, SEL_MASS_SHIFT = 12;      // mass is a sum of floor(P * 2^24): 2^24 >> 12 = 4096 steps for a mass of 1
+// the visited prior mass of one child, an integer so that the wave sum has no order
+__host__ __device__ __forceinline__ unsigned sel_mass_of(float P) { return (unsigned)((double)P * 16777216.0); }
+__host__ __device__ __forceinline__ int sel_mass_index(unsigned mass)
+{
+    const unsigned i = mass >> SEL_MASS_SHIFT;
+    return i > (unsigned)SEL_MASS_STEPS ? SEL_MASS_STEPS : (int)i;
+}
+// what a SEL descent carries from level to level: c(count) of the level, V_X of its node, and this lane's Q of its best child.
+// The SEL kernels take one as a last argument of their own (its value is ignored), so that a kernel without the rule declares
+// nothing for it and keeps its code instruction for instruction.
+struct SelLevel { double cp, vx, bQ; };
+template <class... Rest>
+__device__ __forceinline__ SelLevel &sel_level(SelLevel &s, Rest &...) { return s; }
+// Q of an unvisited child: the node's own value less the reduction (two separate float64 operations)
+__host__ __device__ __forceinline__ double sel_unvisited(double vx, double r, double m)
+{
+    const double red = r * m;
+    return vx - red;
+}
 __device__ __forceinline__ int game_key(const DevState &d, int game) { return (int)(d.game_key0 + d.key_stride * (unsigned)game); }
 // az_set_playout_cap's rule, a function of the game's global name and the absolute ply only (the host's az_playout_cap_full)
 __device__ __forceinline__ bool cap_full_ply(const DevState &d, int game, int ply)
@@ -500,9 +526,13 @@ __device__ __forceinline__ int proof_mark(unsigned char *prf, const unsigned *pa
     return PROOF_UNKNOWN;
 }
 
-template <int N, bool SYNTH, bool DEEP = false, bool SOLVER = false>
-__global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN, int do_select)
+// SEL (az_set_selection): instantiations of their own as well, never together with SOLVER.  Per level one 32-bit wave sum (the
+// visited prior mass), two uniform table reads from HBM (c(count) beside the sqrt, issued with it; the mass table once the
+// sum is known) and the chosen edge's Q carried down as the next node's value; the root's value stays in d.root_v for the ply.
+template <int N, bool SYNTH, bool DEEP = false, bool SOLVER = false, bool SEL = false, class... Sel>
+__global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN, int do_select, Sel... sel)
 {
+    static_assert(sizeof...(Sel) == (SEL ? 1 : 0) && !(SEL && SOLVER), "the SEL kernels take a SelLevel; never with SOLVER");
     typedef TreeGeo<N> G;
     extern __shared__ double sq_lds[];                 // np.sqrt(N + 1e-8), N = 0..S+1 (mcts.py:73)
     const int lane = threadIdx.x & 63;
@@ -667,6 +697,10 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
                     }
                 }
             }
+            if constexpr (SEL) {
+                // az_set_selection: the value the root's evaluation gave (net, cache hit, synthetic or external alike)
+                if (kind == LEAF_ROOT && lane == 0) d.root_v[b] = v;
+            }
             // mcts.py:50-64 expand: one edge per cell (occupied cells are never selected)
             const int row = kind == LEAF_ROOT ? 0 : rows0;
 #pragma unroll
@@ -739,6 +773,11 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
     Plane opp = pl == 1 ? bO : bX;
     int row = 0, npar = rootN, depth = 0, last = slast, out_kind = LEAF_NONE;
     double sq_next = DEEP ? d.sqrt_table[rootN] : 0.0;
+    if constexpr (SEL) {                                      // c(count) of the level, read like DEEP's sqrt; V_X of its node
+        SelLevel &sl = sel_level(sel...);
+        sl.cp = d.sel_cpuct[rootN];
+        sl.vx = (double)d.root_v[b];                          // after stage 1's wave_mem_sync: this launch may have written it
+    }
     const bool forced = d.forced_k > 0.0 && root_noise;       // forced playouts (kernel-argument test, uniform): the noised root only
     for (;;) {
         Plane occ;
@@ -747,7 +786,34 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
         const double sq = DEEP ? sq_next : sq_lds[npar];      // np.sqrt(self.N + 1e-8), mcts.py:73
         double best = 0.0;
         int bi = -1, bN = 0, bC = 0, bS = 0;
-        if (gumbel && row == 0) {
+        if constexpr (SEL) {
+            // az_set_selection: an unvisited child is worth the node's own value less r sqrt(visited prior mass)
+            SelLevel &sl = sel_level(sel...);
+            Edge er[G::CPL];
+            unsigned ms = 0u;
+#pragma unroll
+            for (int i = 0; i < G::CPL; i++) {
+                const int j = lane + 64 * i;
+                if (j < G::nn && !pl_get(occ, j)) {
+                    er[i] = rows[(size_t)row * G::RW + j];
+                    ms += er[i].N ? sel_mass_of(er[i].P) : 0u;
+                }
+            }
+            ms = (unsigned)wave_sum_i((int)ms);
+            const double unv = sel_unvisited(sl.vx, row == 0 ? d.sel_fpu_root : d.sel_fpu, d.sel_mass[sel_mass_index(ms)]);
+            sl.bQ = 0.0;
+#pragma unroll
+            for (int i = 0; i < G::CPL; i++) {
+                const int j = lane + 64 * i;
+                if (j < G::nn && !pl_get(occ, j)) {
+                    const Edge e = er[i];
+                    const double Q = e.N ? e.W / (double)e.N : unv;
+                    double sc = Q + ((sl.cp * (double)e.P) * sq) / (double)(1 + (int)e.N);
+                    if (forced && row == 0 && forced_child((double)(int)e.N, d.forced_k, e.P, rootN)) sc = INFINITY;
+                    if (bi < 0 || sc > best) { best = sc; bi = j; bN = e.N; bC = e.child; sl.bQ = Q; }
+                }
+            }
+        } else if (gumbel && row == 0) {
             // az_set_gumbel: sequential halving at the root.  Among the legal children whose visit count is the schedule's entry
             // for this simulation, the first maximum of (g + logit) + sigma q; they all have equal N, so the choice is exact.
             Edge er[G::CPL];
@@ -816,6 +882,11 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
         const int an = __builtin_amdgcn_readlane(bN, a & 63);
         const int ast = SOLVER ? __builtin_amdgcn_readlane(bS, a & 63) : PROOF_UNKNOWN;
         if (DEEP) sq_next = d.sqrt_table[an];                 // the next level's parent visits: issued before the win test
+        if constexpr (SEL) {
+            SelLevel &sl = sel_level(sel...);
+            sl.cp = d.sel_cpuct[an];
+            sl.vx = -lane_d(sl.bQ, a & 63);                   // the node below, for its side to move (the edge has a visit when a row hangs on it)
+        }
         if (lane == 0) path[depth] = ((unsigned)row << 16) | (unsigned)a;
         depth++;
         pl_set(me, a);                                        // games.py:79-81 place, flip player, remember action
@@ -979,8 +1050,12 @@ __device__ __forceinline__ void vl_leaf_eval(const DevState &d, size_t it, const
 
 __device__ __forceinline__ unsigned char *inflight_arg() { return nullptr; }
 __device__ __forceinline__ unsigned char *inflight_arg(unsigned char *p) { return p; }
+__device__ __forceinline__ unsigned char *inflight_arg(SelLevel &) { return nullptr; }
+__device__ __forceinline__ unsigned char *inflight_arg(SelLevel &, unsigned char *p) { return p; }
 // InFlight is empty for the default kernel (its arguments stay those of the narrow kernel) and `unsigned char *` for DEEP
-template <int N, bool SYNTH, bool DEEP = false, class... InFlight>
+// SEL (az_set_selection): k_step's rule on the counts and totals this kernel scores with, N + in-flight and W - in-flight; a
+// SelLevel goes in front of the extra arguments
+template <int N, bool SYNTH, bool DEEP = false, bool SEL = false, class... InFlight>
 __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int nb_next, InFlight... inflight)
 {
     typedef TreeGeo<N> G;
@@ -1023,6 +1098,9 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
             const int leaf_last = d.leaf_last[it];
             float P[G::CPL];
             vl_leaf_eval<N, SYNTH>(d, it, lme, lopp, leaf_last, netid, kind_raw == kind, lane, P, v);
+            if constexpr (SEL) {
+                if (kind == LEAF_ROOT && lane == 0) d.root_v[b] = v;      // az_set_selection: the root's value for the ply
+            }
             if (kind == LEAF_ROOT && root_noise) {
                 // mcts.py:113-116; float32 multiply, float64 add, float32 store
                 Plane occ;
@@ -1096,6 +1174,11 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
         unsigned *path = d.path + it * G::PATH;
         unsigned leaf_edge = 0xFFFFFFFFu;
         double sq_next = DEEP ? d.sqrt_table[npar] : 0.0;
+        if constexpr (SEL) {                                  // as in k_step
+            SelLevel &sl = sel_level(inflight...);
+            sl.cp = d.sel_cpuct[npar];
+            sl.vx = (double)d.root_v[b];                          // after stage 1's wave_mem_sync: this launch may have written it
+        }
         for (;;) {
             Plane occ;
 #pragma unroll
@@ -1103,6 +1186,40 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
             const double sq = DEEP ? sq_next : sq_lds[npar];      // np.sqrt(self.N + 1e-8), mcts.py:73
             double best = 0.0;
             int bi = -1, bN = 0, bC = 0;
+            if constexpr (SEL) {
+                SelLevel &sl = sel_level(inflight...);
+                Edge er[G::CPL];
+                int nvs[G::CPL];
+                unsigned ms = 0u;
+#pragma unroll
+                for (int i = 0; i < G::CPL; i++) {
+                    const int c = lane + 64 * i;
+                    nvs[i] = 0;
+                    if (c < G::nn && !pl_get(occ, c)) {
+                        er[i] = rows[(size_t)row * G::RW + c];
+                        const int fl = DEEP ? (infl ? (int)infl[(size_t)row * G::RW + c] : 0) : (int)er[i].N >> EDGE_N_BITS;
+                        nvs[i] = (DEEP ? (int)er[i].N : ((int)er[i].N & EDGE_N_MASK)) + fl;
+                        ms += nvs[i] ? sel_mass_of(er[i].P) : 0u;
+                    }
+                }
+                ms = (unsigned)wave_sum_i((int)ms);
+                const double unv = sel_unvisited(sl.vx, row == 0 ? d.sel_fpu_root : d.sel_fpu, d.sel_mass[sel_mass_index(ms)]);
+                sl.bQ = 0.0;
+#pragma unroll
+                for (int i = 0; i < G::CPL; i++) {
+                    const int c = lane + 64 * i;
+                    if (c < G::nn && !pl_get(occ, c)) {
+                        const Edge e = er[i];
+                        const int nv = nvs[i];
+                        const int fl = nv - (DEEP ? (int)e.N : ((int)e.N & EDGE_N_MASK));
+                        const double wvv = e.W - (double)fl;
+                        const double Q = nv ? wvv / (double)nv : unv;
+                        double sc = Q + ((sl.cp * (double)e.P) * sq) / (double)(1 + nv);
+                        if (forced && row == 0 && forced_child((double)nv, d.forced_k, e.P, sims_done + j)) sc = INFINITY;
+                        if (bi < 0 || sc > best) { best = sc; bi = c; bN = nv; bC = e.child; sl.bQ = Q; }
+                    }
+                }
+            } else {
 #pragma unroll
             for (int i = 0; i < G::CPL; i++) {
                 int c = lane + 64 * i;
@@ -1118,12 +1235,18 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
                     if (bi < 0 || sc > best) { best = sc; bi = c; bN = nv; bC = e.child; }
                 }
             }
+            }
             wave_argmax(best, bi);
             const int a = __builtin_amdgcn_readfirstlane(bi);
             if (a < 0) { out_kind = LEAF_NONE; break; }
             const int child = __builtin_amdgcn_readlane(bC, a & 63);
             const int an = __builtin_amdgcn_readlane(bN, a & 63);
             if (DEEP) sq_next = d.sqrt_table[an];                 // the next level's parent visits: issued before the win test
+            if constexpr (SEL) {
+                SelLevel &sl = sel_level(inflight...);
+                sl.cp = d.sel_cpuct[an];
+                sl.vx = -lane_d(sl.bQ, a & 63);
+            }
             if (lane == (a & 63)) {
                 if (DEEP) {
                     if (infl) { unsigned char *f = infl + (size_t)row * G::RW + a; *f = (unsigned char)(*f + 1); }
@@ -1292,13 +1415,14 @@ __global__ __launch_bounds__(256) void k_move(DevState d)
         tot = wave_sum_i(tot);
         const double sq = d.sqrt_table[tot];
         const Edge es = root[astar];
-        const double target = forced_score(es.W / (double)(int)(best >> 16), d.c_puct, es.P, sq, (int)(best >> 16));
+        const double cp = d.sel_cpuct ? d.sel_cpuct[tot] : d.c_puct;     // az_set_selection: c(count), the count the sqrt takes
+        const double target = forced_score(es.W / (double)(int)(best >> 16), cp, es.P, sq, (int)(best >> 16));
 #pragma unroll
         for (int i = 0; i < G::CPL; i++) {
             const int j = lane + 64 * i;
             if (legal[i] && Nj[i] > 0 && j != astar) {
                 const Edge ec = root[j];
-                Np[i] = forced_pruned(d.forced_k, d.c_puct, ec.W / (double)Nj[i], ec.P, Nj[i], tot, sq, target);
+                Np[i] = forced_pruned(d.forced_k, cp, ec.W / (double)Nj[i], ec.P, Nj[i], tot, sq, target);
             }
         }
     }

@@ -1,5 +1,7 @@
 """The search options of the seams (MCTS, SelfPlayManager, ModelEvaluator, train.py): which of them combine, and how an engine
-is brought to a set of them.  A new option is wired into the seams here: its row(s) in CONFLICTS, its set / clear in apply_options."""
+is brought to a set of them.  A new option is wired into the seams here: its row(s) in CONFLICTS, its set / clear in apply_options.
+The selection rule has a table and a function of its own (SELECTION_CONFLICTS, bring_selection): the seams call that function
+on either side of apply_options."""
 
 # Pairs of options that cannot be combined, with the text a seam refuses them with: the engine's table (g_conflicts in
 # csrc/az_engine.hip) for the options the seams expose.  The first row whose two options are both on names the error.
@@ -24,6 +26,12 @@ CONFLICTS = (
 NEEDS = (
     ("threat_search", "solver", "threat_search needs solver=True: it hands its results to the solver"),
 )
+# ... and the pairs the selection rule (az_set_selection) adds to the engine's table
+SELECTION_CONFLICTS = (
+    ("selection", "subtree_reuse", "the selection rule does not combine with subtree_reuse: a retained root has no fresh value"),
+    ("selection", "solver", "the selection rule does not combine with the solver (and so not with the threat search)"),
+    ("selection", "gumbel", "the selection rule does not combine with the Gumbel root search"),
+)
 
 
 def switched_on(**options):
@@ -32,13 +40,16 @@ def switched_on(**options):
 
 
 def check_combination(on, of=None):
-    """ValueError for the first rule of CONFLICTS / NEEDS that the set `on` of option names breaks; of: only the rules that
-    speak of this option."""
+    """ValueError for the first rule of CONFLICTS / NEEDS / SELECTION_CONFLICTS that the set `on` of option names breaks; of: only
+    the rules that speak of this option."""
     for a, b, message in CONFLICTS:
         if a in on and b in on and of in (None, a, b):
             raise ValueError(message)
     for a, b, message in NEEDS:
         if a in on and b not in on and of in (None, a, b):
+            raise ValueError(message)
+    for a, b, message in SELECTION_CONFLICTS:
+        if a in on and b in on and of in (None, a, b):
             raise ValueError(message)
 
 
@@ -79,6 +90,21 @@ def apply_options(eng, *, win_rule, start_positions, first, resign, playout_cap,
         eng.set_solver(True)                              # before the threat search that needs it
     if threat_search is not None:
         eng.set_threat_search(**threat_search)
+    return eng
+
+
+def bring_selection(eng, selection, before):
+    """The selection rule of a new or cached engine (selection: the checked dict, None = off), in two steps round apply_options
+    and whatever else may switch one of its refused partners on: before=True takes it off unless the engine already has
+    exactly this one, so that the solver, the Gumbel root search or subtree reuse never meet the last configuration's; before=
+    False sets it once apply_options has switched those off."""
+    have = eng.selection()
+    same = selection is not None and have == dict(selection, on=True)
+    if before:
+        if have["on"] and not same:
+            eng.set_selection(on=False)
+    elif selection is not None and not same:
+        eng.set_selection(**selection)
     return eng
 
 

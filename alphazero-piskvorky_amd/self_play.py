@@ -7,10 +7,10 @@ import torch
 
 from . import constants as _c
 from . import parallel
-from ._capi import check_threat_search, AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine, playout_cap_permille, resign_permille, win_rule_name
+from ._capi import check_selection, check_threat_search, AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine, playout_cap_permille, resign_permille, win_rule_name
 from .controller import BatchPolicyValueFn, device_index, model_kind
 from .mcts import check_forced_playouts, check_gumbel, check_solver, numpy_log_table
-from .options import apply_options, check_combination, switched_on
+from .options import apply_options, bring_selection, check_combination, switched_on
 
 
 def default_temperature_schedule(move: int) -> float:
@@ -116,7 +116,7 @@ class SelfPlayManager:
                  eval_cache: int = 0, virtual_loss: int = 1, trunk: str = "f32", leaf_symmetry: bool = False,
                  start_positions=None, resign: dict = None, evaluator: BatchPolicyValueFn = None,
                  playout_cap: dict = None, forced_playouts: dict = None, gumbel: dict = None, solver: bool = False,
-                 win_rule: str = None, threat_search: dict = None):
+                 win_rule: str = None, threat_search: dict = None, selection: dict = None):
         self.controller = controller
         # which game is played: "freestyle" (constants.WIN_RULE's default, the reference's: a run of WIN_LENGTH or more wins) or
         # "exact" (standard Gomoku: exactly WIN_LENGTH, an overline wins nothing; az_set_win_rule).  Combines with every option.
@@ -155,6 +155,11 @@ class SelfPlayManager:
         # the simulations, its proven wins and forced blocks premarked for the solver (az_set_threat_search).  Needs solver=True.
         # Whether it trains a stronger net per GPU hour has not been measured.
         self.threat_search = threat_search
+        # opt-in selection rule: dict(fpu=0.2, fpu_root=0.0, cpuct_base=19652.0, cpuct_factor=0.0); an unvisited child is worth its
+        # parent's value less fpu * sqrt(visited prior mass) instead of 0, and c_puct grows with the parent's count
+        # (az_set_selection).  Not with subtree_reuse, gumbel or solver.  Whether it trains a stronger net per GPU hour has not
+        # been measured (tools/selection_gain.py measures throughput, game length and how wide the roots get).
+        self.selection = selection
         self.temperature_schedule = temperature_schedule
         self.concurrent_games = concurrent_games or _c.CONCURRENT_GAMES
         self.augmentation = augmentation      # 4 = the reference's rotations (self_play.py:94-108), 8 = full dihedral group, 1 = none
@@ -185,9 +190,10 @@ class SelfPlayManager:
         self.gumbel = check_gumbel(self.gumbel)
         self.solver = check_solver(self.solver)
         self.threat_search = check_threat_search(self.threat_search)
+        self.selection = check_selection(self.selection)
         check_combination(switched_on(subtree_reuse=self.subtree_reuse, virtual_loss=self.virtual_loss, leaf_symmetry=self.leaf_symmetry,
                                       evaluator=self.evaluator, playout_cap=self.playout_cap, forced_playouts=self.forced_playouts,
-                                      gumbel=self.gumbel, solver=self.solver, threat_search=self.threat_search))
+                                      gumbel=self.gumbel, solver=self.solver, threat_search=self.threat_search, selection=self.selection))
 
     def _eng(self, n, k, slots):
         p = self.mcts_params
@@ -262,6 +268,7 @@ class SelfPlayManager:
         eng = self._eng(n, k, max(1, min(self.concurrent_games, max(mine, 1))))
         if self.evaluator is None:
             eng.load_weights(self.controller.net.state_dict(), 0)
+        bring_selection(eng, self.selection, before=True)      # before subtree reuse, the solver or the Gumbel root may come on
         eng.set_subtree_reuse(self.subtree_reuse)
         if eng.trunk_mode() != self.trunk:
             eng.set_trunk_mode(self.trunk)
@@ -269,6 +276,7 @@ class SelfPlayManager:
         apply_options(eng, win_rule=self.win_rule, start_positions=self.start_positions, first=lo, resign=self.resign,
                       playout_cap=self.playout_cap, forced_playouts=self.forced_playouts, gumbel=self.gumbel, solver=self.solver,
                       threat_search=self.threat_search)
+        bring_selection(eng, self.selection, before=False)
         self.last_resign_stats = self.last_playout_cap_stats = None
         if mine > 0:
             self.last_counters = eng.selfplay(mine, seed0=seed0 + lo, temperature_table=T)

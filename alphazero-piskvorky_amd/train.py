@@ -29,7 +29,7 @@ PROMOTION_THRESHOLD = 0.55          # promoter.py:19, strict ">" with draws coun
 
 def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=None, log=print, device_replay=False,
         subtree_reuse=False, trunk="f32", eval_sims=None, start_positions=None, resign=None, torch_eval=False,
-        playout_cap=None, forced_playouts=None, gumbel=None, solver=False, win_rule=None, threat_search=None):
+        playout_cap=None, forced_playouts=None, gumbel=None, solver=False, win_rule=None, threat_search=None, selection=None):
     """eval_sims: simulations per move in the arena (evaluator.py:53-62 takes NUM_EVAL_SIMULATIONS = 200 whatever the
     self-play count is; main() passes that constant); None = as many as self-play, which keeps small test runs short.
     device_replay=True keeps the examples on the GPU from the episode-end gather to the optimizer step (packed records
@@ -54,6 +54,9 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
     threat_search: dict(max_depth, node_budget) for the self-play searches (Engine.set_threat_search): an exact forced-four search
     on every root before the simulations; its proven wins and forced blocks reach the solver as premarked root statuses.  Needs
     solver=True.  The arena is untouched.  Whether it trains a stronger net per GPU hour is not measured.
+    selection: dict(fpu, fpu_root, cpuct_base, cpuct_factor) for the self-play searches (Engine.set_selection): an unvisited child is
+    worth its parent's value less fpu * sqrt(visited prior mass) instead of 0, and c_puct grows with the parent's count.  Not with
+    subtree_reuse, gumbel or solver.  The arena is untouched.  Whether it trains a stronger net per GPU hour is not measured.
     win_rule: "freestyle" (constants.WIN_RULE's default: a run of WIN_LENGTH or more wins) or "exact" (standard Gomoku: exactly
     WIN_LENGTH, overlines win nothing; Engine.set_win_rule).  It is the game itself, so self-play AND the arena play it, and it
     combines with every option.  Whether exact-rule self-play trains a stronger standard-rule net is not measured.
@@ -72,7 +75,7 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
                               seed=seed, subtree_reuse=subtree_reuse, gather_to=0 if world > 1 else None, trunk=trunk,
                               start_positions=start_positions, resign=resign, playout_cap=playout_cap,
                               forced_playouts=forced_playouts, gumbel=gumbel, solver=solver, win_rule=win_rule, threat_search=threat_search,
-                              evaluator=make_batch_policy_value_fn(candidate.net, device) if torch_eval else None)
+                              selection=selection, evaluator=make_batch_policy_value_fn(candidate.net, device) if torch_eval else None)
     evaluator = ModelEvaluator(game_class=Gomoku, print_games=False, device=device, seed=seed,
                                evaluators=True if torch_eval else None, win_rule=win_rule)
     promoter = ModelPromoter(model_dir, evaluator, lambda: GomokuNet(board_size=n), device, threshold=PROMOTION_THRESHOLD)
@@ -131,6 +134,16 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
     return history
 
 
+def selection_from_flags(error, fpu, fpu_root, cpuct_base, cpuct_factor):
+    """--fpu / --fpu-root / --cpuct-base / --cpuct-factor as the dict the seams take, None when none is given.  --fpu or
+    --cpuct-factor switches the option on; the other two without one of them are an error."""
+    message = "--fpu-root and --cpuct-base need --fpu or --cpuct-factor"
+    flags = {"fpu": fpu, "fpu_root": fpu_root, "cpuct_base": cpuct_base, "cpuct_factor": cpuct_factor}
+    if fpu is None and cpuct_factor is not None:
+        flags = {"cpuct_factor": flags.pop("cpuct_factor"), **flags}       # the option's own flag goes first
+    return option_from_flags(error, flags, message)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--episodes", type=int, default=C.NUM_EPISODES)
@@ -175,6 +188,14 @@ def main():
                     help="root threat search in the self-play searches: an exact forced-four search of depth D (1..16) on every root "
                          "before the simulations, handed to the solver; implies --solver")
     ap.add_argument("--threat-nodes", type=int, default=None, metavar="N", help="with --threat-depth: fours tried per root at most (default 256)")
+    ap.add_argument("--fpu", type=float, default=None, metavar="R",
+                    help="selection rule in the self-play searches: an unvisited child is worth its parent's value less "
+                         "R x sqrt(prior mass already visited) instead of 0 (0 <= R <= 2; Leela Zero and KataGo use about 0.2)")
+    ap.add_argument("--fpu-root", type=float, default=None, metavar="R0", help="with --fpu or --cpuct-factor: the reduction at the root (default 0)")
+    ap.add_argument("--cpuct-base", type=float, default=None, metavar="B", help="with --fpu or --cpuct-factor: c_base of the c_puct growth (default 19652)")
+    ap.add_argument("--cpuct-factor", type=float, default=None, metavar="F",
+                    help="selection rule in the self-play searches: c_puct + F x log((N + B + 1) / B) at a parent with N visits "
+                         "(0 <= F <= 16; AlphaZero's rule is F = 1); unvisited children are scored as under --fpu (default R 0.2)")
     ap.add_argument("--win-rule", choices=("freestyle", "exact"), default=None,
                     help="the game that self-play and the arena play: freestyle (default; a run of WIN_LENGTH or more wins) or "
                          "exact (standard Gomoku: exactly WIN_LENGTH, an overline wins nothing)")
@@ -204,6 +225,7 @@ def main():
                                       "--threat-nodes needs --threat-depth")
     if threat_search is not None:
         a.solver = True
+    selection = selection_from_flags(ap.error, a.fpu, a.fpu_root, a.cpuct_base, a.cpuct_factor)
     start_positions = None
     if a.start_positions:
         with np.load(a.start_positions) as z:
@@ -220,7 +242,7 @@ def main():
     run(a.episodes, a.games, a.sims, a.eval_games, a.device, model_dir=a.model_dir, device_replay=a.device_replay,
         subtree_reuse=a.subtree_reuse, trunk=a.trunk, eval_sims=C.NUM_EVAL_SIMULATIONS, start_positions=start_positions,
         resign=resign, torch_eval=a.torch_eval, playout_cap=playout_cap, forced_playouts=forced_playouts,
-        gumbel=gumbel, solver=a.solver, win_rule=a.win_rule, threat_search=threat_search)
+        gumbel=gumbel, solver=a.solver, win_rule=a.win_rule, threat_search=threat_search, selection=selection)
     if world > 1:
         td.barrier()
         td.destroy_process_group()

@@ -641,6 +641,43 @@ int az_set_forced_playouts(az_engine *e, double k, int prune);
 int az_get_forced_playouts(const az_engine *e, double *k, int *prune);
 int64_t az_forced_prune(double k, double c_puct, int count, const int32_t *visits, const double *W, const float *prior, int32_t *out);
 
+/* Opt-in selection rule: first-play urgency (Leela Zero, KataGo) and AlphaZero's visit-dependent c_puct.  The reference scores
+ * a child Q + ((c_puct P) sqrt(Np + 1e-8)) / (1 + N) with Q = 0 while the child is unvisited and one constant c_puct; with
+ * the option on an unvisited child is worth its parent's value less a reduction that grows with the prior mass already
+ * visited, and c_puct grows with the parent's count.  Whether this trains a stronger net per GPU hour has not been measured.
+ *
+ * Rule.  az_set_selection(on, fpu, fpu_root, cpuct_base, cpuct_factor).  on = 0 switches the option off, which is the default
+ * (the other arguments are then ignored and the stored ones kept); every search is then the reference's, executed by the
+ * kernels that run it without this option.  With on = 1, at a node X whose children are scored:
+ *   nv_c, wv_c = the child's count and total as the selection uses them: N and W, or N + in-flight and W - in-flight under
+ *   virtual-loss batching.  A child is visited when nv_c > 0.
+ *   mass = the sum over the visited legal children of (uint32) floor((double)P_c * 2^24), P_c the edge's float32 prior as stored
+ *   (noised at a noised root): an integer, so the sum has no order.  idx = min(mass >> 12, 4096).
+ *   red = r_X * mass_table[idx], mass_table[i] = sqrt(i / 4096.0) for i = 0..4096; r_X = fpu_root at the root, fpu elsewhere.
+ *   V_X = the node's value for its side to move: at the root (double) of the float32 value the root's evaluation gave (the net,
+ *   a cache hit, the synthetic or an external evaluator); elsewhere -Q_sel, Q_sel = the Q the level above computed for the
+ *   edge it chose (always a visited one: a row exists only after a backup).
+ *   Q_c = nv_c > 0 ? wv_c / nv_c : V_X - red       (the product and the difference are two float64 operations)
+ *   score = Q_c + ((c(Np) * P_c) * sqrt(Np + 1e-8)) / (1 + nv_c), c(Np) = cpuct_table[Np] with the count the sqrt takes,
+ *   cpuct_table[i] = c_puct + cpuct_factor * log((i + cpuct_base + 1.0) / cpuct_base) for i = 0..S+1 (std::log on the host);
+ *   cpuct_factor = 0 gives c_puct exactly in every entry.
+ *   Forced playouts: the pruning's score(c, m) and target take c(total) for c_puct, total the count its sqrt takes; the forced
+ *   test n^2 < (k P) total, pi, the sampled move and the search value keep their definitions.
+ * az_selection_tables(c_puct, cpuct_base, cpuct_factor, S, cpuct, mass) writes the two tables exactly as the engine uploads
+ * them, cpuct[0 .. S+1] and mass[0 .. 4096] (host only, no engine needed); AZ_ERR_INVALID for a bad argument.
+ * While the option is on every board size runs the lock-step kernels (az_get_persistent reports 0); switching it off brings
+ * the persistent search kernel back.
+ * Combines with virtual-loss batching, the evaluation cache, leaf symmetry, both nets, the synthetic evaluator, deep engines,
+ * the external evaluator, start positions, resignation, the playout cap (a FAST ply's un-noised root uses fpu_root like any
+ * root), forced playouts, the exact win rule and delta evaluation.  Refused with AZ_ERR_INVALID, whichever is set first:
+ * subtree reuse (a retained root has no fresh value), the solver and with it the threat search (their kernels do not carry
+ * the rule), the Gumbel root search.
+ * AZ_ERR_INVALID unless fpu and fpu_root are finite and in [0, 2], cpuct_factor finite and in [0, 16], cpuct_base finite and
+ * >= 1 (the previous setting is kept); AZ_ERR_STATE while an episode is open. */
+int az_set_selection(az_engine *e, int on, double fpu, double fpu_root, double cpuct_base, double cpuct_factor);
+int az_get_selection(const az_engine *e, int *on, double *fpu, double *fpu_root, double *cpuct_base, double *cpuct_factor);
+int az_selection_tables(double c_puct, double cpuct_base, double cpuct_factor, int S, double *cpuct, double *mass);
+
 /* Opt-in Gumbel root search ("Policy improvement by planning with Gumbel", Danihelka et al., ICLR 2022): instead of Dirichlet
  * noise, PUCT at the root and the visit-count target, the root samples Gumbel-top-m candidates without replacement, spends a
  * fixed sequential-halving schedule on them and trains on softmax(logits + sigma(completed Q)).  Made for 16 to 64 simulations
