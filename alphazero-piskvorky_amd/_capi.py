@@ -38,6 +38,7 @@ EXPORTS = [
     "az_set_playout_cap", "az_get_playout_cap", "az_playout_cap_full", "az_selfplay_sims", "az_selfplay_export_count",
     "az_set_forced_playouts", "az_get_forced_playouts", "az_forced_prune",
     "az_set_selection", "az_get_selection", "az_selection_tables",
+    "az_set_candidates", "az_get_candidates", "az_candidate_mask",
     "az_set_gumbel", "az_get_gumbel", "az_gumbel_schedule", "az_gumbel_target", "az_gumbel_vmix", "az_rng_selfplay_tape_gumbel",
     "az_set_external_evaluator", "az_get_external_evaluator", "az_ext_capacity", "az_ext_stats",
     "az_set_solver", "az_get_solver", "az_last_proof", "az_selfplay_proofs", "az_solver_counts", "az_solver_stops",
@@ -172,6 +173,10 @@ def lib():
             L.az_set_selection.argtypes = [C.c_void_p, C.c_int] + [C.c_double] * 4
             L.az_get_selection.argtypes = [C.c_void_p, C.POINTER(C.c_int)] + [C.POINTER(C.c_double)] * 4
             L.az_selection_tables.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
+        if hasattr(L, "az_set_candidates"):
+            L.az_set_candidates.argtypes = [C.c_void_p, C.c_int]
+            L.az_get_candidates.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+            L.az_candidate_mask.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         if hasattr(L, "az_set_gumbel"):
             L.az_set_gumbel.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
             L.az_get_gumbel.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -338,7 +343,32 @@ def selection_tables(c_puct, cpuct_base, cpuct_factor, S):
     return cp, mass
 
 
-WIN_RULES = {"freestyle": 0, "exact": 1}                       # az_set_win_rule: AZ_RULE_*
+def check_candidates(candidates):
+    """The option as the seams keep it: None (off), or dict(radius=r) with r an int >= 1 (ValueError otherwise; no engine is
+    touched -- the upper bound n - 1 is the engine's, which knows the board)."""
+    if candidates is None or candidates is False:
+        return None
+    if not isinstance(candidates, dict) or set(candidates) != {"radius"}:
+        raise ValueError(f"candidates takes dict(radius=r), got {candidates!r}")
+    r = candidates["radius"]
+    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 1 <= int(r) <= 14:
+        raise ValueError(f"candidates radius must be an int in 1 .. n-1 (at most 14), got {r!r}")
+    return dict(radius=int(r))
+
+
+def candidate_mask(board, n, radius):
+    """The candidate set of a position as az_set_candidates defines it (az_candidate_mask; needs no GPU): board uint8[n*n]
+    (0 empty, 1 / 2 stones) -> uint8[n*n], 1 for the cells of C.  radius 0 gives the empty cells."""
+    b = np.ascontiguousarray(np.asarray(board).reshape(-1), np.uint8)
+    if b.size != int(n) * int(n):
+        raise ValueError(f"board has {b.size} cells, n*n = {int(n) * int(n)}")
+    mask = np.zeros(b.size, np.uint8)
+    if lib().az_candidate_mask(int(n), _p(b), int(radius), _p(mask)):
+        raise ValueError(f"az_candidate_mask refused its arguments (n {n} in 3..15, radius {radius} in 0..n-1, cells in 0..2)")
+    return mask
+
+
+WIN_RULES = {"freestyle": 0, "exact": 1}                     # az_set_win_rule: AZ_RULE_*
 
 
 def win_rule_id(rule):
@@ -989,6 +1019,19 @@ class Engine:
         self._check(lib().az_get_selection(self.h, C.byref(on), *[C.byref(x) for x in v]), "az_get_selection")
         return dict(on=bool(on.value), fpu=float(v[0].value), fpu_root=float(v[1].value), cpuct_base=float(v[2].value),
                     cpuct_factor=float(v[3].value))
+
+    # ---- candidate moves ----
+    def set_candidates(self, radius):
+        """Opt-in: every search expands, noises and selects only the empty cells within Chebyshev distance `radius` (1 .. n-1) of
+        a stone, every cell on an empty board, with the priors normalised over them; 0 switches it off.  While it is on every
+        board size runs the lock-step kernels.  See include/az_engine.h."""
+        self._check(lib().az_set_candidates(self.h, int(radius)), "az_set_candidates")
+
+    def candidates(self):
+        """The radius set, 0 = off (az_get_candidates)."""
+        r = C.c_int(0)
+        self._check(lib().az_get_candidates(self.h, C.byref(r)), "az_get_candidates")
+        return int(r.value)
 
     # ---- win rule ----
     def set_win_rule(self, rule):

@@ -96,6 +96,13 @@ __device__ __forceinline__ float wave_sum_butterfly(float v)
     for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
     return v;
 }
+// the same butterfly in float64 (az_set_candidates: the noise of the candidate cells is renormalised by its sum)
+__device__ __forceinline__ double wave_sum_butterfly_d(double v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
+    return v;
+}
 // Cross-lane moves on the DPP path (no LDS round trip, unlike __shfl's ds_bpermute).  Only patterns whose meaning leaves no
 // room for a direction convention: the two quad permutes that are xor 1 / xor 2, and the two mirrors.  After the four steps
 // below every lane of a 16-lane row holds the row's result of an idempotent, commutative reduction (max, min); the four rows

@@ -5,6 +5,7 @@
 #include <dlfcn.h>
 #include <sched.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -152,6 +153,8 @@ struct az_engine {
     int sel_on = 0;
     double sel_fpu = 0.0, sel_fpu_root = 0.0, sel_base = 19652.0, sel_factor = 0.0;
     DevBuf sel_cpuct, sel_mass;
+    // az_set_candidates: the Chebyshev radius, 0 = off
+    int cand_radius = 0;
     // az_set_solver: 0 = off; the root status of every record, and what az_last_proof hands out (the root rows and root
     // statuses of the last az_search / az_search_batch, occupied cells 0)
     int solver = 0;
@@ -329,7 +332,7 @@ static int upload(az_engine *e, DevBuf &b, const void *src, size_t bytes)
 // its setting ON calls refuse_conflicts; the first row with an active partner names the error.
 // ------------------------------------------------------------------------------------------------
 enum Setting {
-    SET_REUSE, SET_VL, SET_VL_KERNEL, SET_SYMMETRY, SET_EXT, SET_CAP, SET_FORCED, SET_GUMBEL, SET_SOLVER, SET_SELECTION,
+    SET_REUSE, SET_VL, SET_VL_KERNEL, SET_SYMMETRY, SET_EXT, SET_CAP, SET_FORCED, SET_GUMBEL, SET_SOLVER, SET_SELECTION, SET_CANDIDATES,
     SET_SYNTHETIC, SET_NO_NET          // facts of az_config: the synthetic evaluator; any evaluator but the net
 };
 static const struct { Setting a, b; const char *message; } g_conflicts[] = {
@@ -354,6 +357,11 @@ static const struct { Setting a, b; const char *message; } g_conflicts[] = {
     {SET_SELECTION, SET_REUSE, "the selection rule and subtree reuse cannot be combined (a retained root has no fresh value)"},
     {SET_SELECTION, SET_SOLVER, "the selection rule and the solver cannot be combined"},
     {SET_SELECTION, SET_GUMBEL, "the selection rule and the Gumbel root search cannot be combined"},
+    {SET_CANDIDATES, SET_REUSE, "candidate moves and subtree reuse cannot be combined (a retained root's priors and noise were not made under the rule)"},
+    {SET_CANDIDATES, SET_GUMBEL, "candidate moves and the Gumbel root search cannot be combined (its top-m and target are defined over the legal cells)"},
+    {SET_CANDIDATES, SET_SOLVER, "candidate moves and the solver cannot be combined (every move loses is no proof when moves were left out)"},
+    {SET_CANDIDATES, SET_SELECTION, "candidate moves and the selection rule cannot be combined yet"},
+    {SET_CANDIDATES, SET_EXT, "candidate moves and the external evaluator cannot be combined (it returns priors, not logits)"},
 };
 
 // bit s = setting s is on.  Virtual-loss batching has two: more than one leaf per batch, and the batched tree kernel being in
@@ -361,7 +369,7 @@ static const struct { Setting a, b; const char *message; } g_conflicts[] = {
 static unsigned active_settings(const az_engine *e)
 {
     const bool on[] = {e->reuse != 0, e->vl > 1, e->vl > 1 || e->vl_kernel, e->leaf_symmetry != 0, e->ext.on, e->cap_fast != 0,
-                       e->forced_k > 0.0, e->gumbel_m > 0, e->solver != 0, e->sel_on != 0,
+                       e->forced_k > 0.0, e->gumbel_m > 0, e->solver != 0, e->sel_on != 0, e->cand_radius != 0,
                        e->cfg.eval_kind == AZ_EVAL_SYNTHETIC, e->cfg.eval_kind != AZ_EVAL_NET};
     unsigned m = 0;
     for (int s = 0; s <= SET_NO_NET; s++) m |= on[s] ? 1u << s : 0u;
@@ -857,6 +865,7 @@ static int create_engine(const az_config *cfg, az_engine **out, bool deep)
         d.gumbel_m = 0; d.gumbel_cv = 0.0; d.gumbel_cs = 0.0; d.gumbel_seq = nullptr; d.root_logits = nullptr; d.root_v = nullptr;
         d.proof = nullptr; d.proof_buf = nullptr; d.root_proof = nullptr; d.rec_proof = nullptr; d.proof_stops = nullptr;
         d.sel_cpuct = nullptr; d.sel_mass = nullptr; d.sel_fpu = 0.0; d.sel_fpu_root = 0.0;
+        d.cand_radius = 0;
         d.s_budget = (int *)L.budget.p; d.cp_board = (u64 *)L.cp_board.p; d.cp_state = (int *)L.cp_state.p;
         if (!rc) rc = alloc_items(e, L, 1);
     }
@@ -1243,6 +1252,8 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
         d.sel_mass = e->sel_on ? (const double *)e->sel_mass.p : nullptr;
         d.sel_fpu = e->sel_on ? e->sel_fpu : 0.0;
         d.sel_fpu_root = e->sel_on ? e->sel_fpu_root : 0.0;
+        // ... and so are candidate moves: self-play, the arena and the preset searches alike
+        d.cand_radius = e->cand_radius;
     });
     e->episode_solver = e->solver;
     e->solver_stops = 0;
@@ -1252,7 +1263,7 @@ static int episode_begin(az_engine *e, const EpisodeSpec &sp)
     const bool capped = !sp.preset && !sp.arena && e->cap_fast > 0;
     // persistent search kernel: plain net or synthetic evaluator, the reference's sequential search, trees that fit into LDS
     e->persist_gp = 0;
-    if (e->persist_allowed && !ext && !e->vl_kernel && !capped && !e->threat_depth && !e->sel_on && e->trunk_mode == AZ_TRUNK_F32) {
+    if (e->persist_allowed && !ext && !e->vl_kernel && !capped && !e->threat_depth && !e->sel_on && !e->cand_radius && e->trunk_mode == AZ_TRUNK_F32) {
         const int synth = e->cfg.eval_kind == AZ_EVAL_SYNTHETIC ? 1 : 0;
         const int S = e->cfg.num_simulations;
         if (!sp.arena && (!sp.preset || sp.batch) && e->ops->search_prepare(S, 2, synth, e->cfg.model, e->solver)) e->persist_gp = 2;
@@ -2201,6 +2212,46 @@ extern "C" int az_get_selection(const az_engine *e, int *on, double *fpu, double
     if (fpu_root) *fpu_root = e->sel_fpu_root;
     if (cpuct_base) *cpuct_base = e->sel_base;
     if (cpuct_factor) *cpuct_factor = e->sel_factor;
+    return AZ_OK;
+}
+
+// ---- candidate moves: expansion, noise and selection over the empty cells near the stones ----
+// the rule on the host: mask[j] = 1 for the cells of C(X); radius 0 = the option off, every empty cell
+extern "C" int az_candidate_mask(int n, const uint8_t *board, int radius, uint8_t *mask)
+{
+    if (n < 3 || n > 15 || !board || !mask || radius < 0 || radius > n - 1) return AZ_ERR_INVALID;
+    const int nn = n * n;
+    int stones = 0;
+    for (int j = 0; j < nn; j++) {
+        if (board[j] > 2) return AZ_ERR_INVALID;
+        stones += board[j] != 0;
+    }
+    for (int j = 0; j < nn; j++) {
+        bool in = board[j] == 0 && (stones == 0 || radius == 0);
+        if (board[j] == 0 && !in) {
+            const int r = j / n, c = j % n;
+            for (int rr = std::max(0, r - radius); rr <= std::min(n - 1, r + radius) && !in; rr++)
+                for (int cc = std::max(0, c - radius); cc <= std::min(n - 1, c + radius) && !in; cc++) in = board[rr * n + cc] != 0;
+        }
+        mask[j] = in ? 1 : 0;
+    }
+    return AZ_OK;
+}
+
+extern "C" int az_set_candidates(az_engine *e, int radius)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_candidates: an episode is open (az_selfplay_end first)");
+    if (radius < 0 || radius > e->n - 1) return fail(e, AZ_ERR_INVALID, "az_set_candidates: radius %d (0 = off, or 1 .. %d)", radius, e->n - 1);
+    if (radius && refuse_conflicts(e, SET_CANDIDATES)) return AZ_ERR_INVALID;
+    e->cand_radius = radius;
+    return AZ_OK;
+}
+
+extern "C" int az_get_candidates(const az_engine *e, int *radius)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (radius) *radius = e->cand_radius;
     return AZ_OK;
 }
 
@@ -3446,6 +3497,7 @@ extern "C" int az_search_callback(az_engine *e, const uint8_t *board, int player
     if (e->vl > 1 || e->reuse || e->leaf_symmetry)
         return fail(e, AZ_ERR_INVALID, "az_search_callback: not combinable with virtual-loss batching, subtree reuse or random-symmetry leaf evaluation");
     if (e->solver) return fail(e, AZ_ERR_INVALID, "az_search_callback: not combinable with the solver");
+    if (e->cand_radius) return fail(e, AZ_ERR_INVALID, "az_search_callback: not combinable with candidate moves (the callback returns priors, not logits)");
     if (noise && e->gumbel_m > 0)
         return fail(e, AZ_ERR_INVALID, "az_search_callback: a noised search under the Gumbel root search needs logits, the callback returns priors");
     int stones = 0;

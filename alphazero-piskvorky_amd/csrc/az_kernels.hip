@@ -90,12 +90,23 @@ void step(const LaunchCtx &c, int rootN, int do_select)
     if (c.d.sel_cpuct) {                                       // az_set_selection (never with the solver): the SEL kernels
         const size_t lds = c.d.S > DEFAULT_MAX_S ? 0 : (size_t)(c.d.S + 2) * sizeof(double);
         if (c.d.S > DEFAULT_MAX_S) {
-            if (c.synthetic) hipLaunchKernelGGL((k_step<N, true, true, false, true, SelLevel>), g, b, lds, c.stream, c.d, rootN, do_select, SelLevel{});
-            else hipLaunchKernelGGL((k_step<N, false, true, false, true, SelLevel>), g, b, lds, c.stream, c.d, rootN, do_select, SelLevel{});
+            if (c.synthetic) hipLaunchKernelGGL((k_step<N, true, true, false, true, false, SelLevel>), g, b, lds, c.stream, c.d, rootN, do_select, SelLevel{});
+            else hipLaunchKernelGGL((k_step<N, false, true, false, true, false, SelLevel>), g, b, lds, c.stream, c.d, rootN, do_select, SelLevel{});
         } else {
-            if (c.synthetic) hipLaunchKernelGGL((k_step<N, true, false, false, true, SelLevel>), g, b, lds, c.stream, c.d, rootN, do_select, SelLevel{});
-            else hipLaunchKernelGGL((k_step<N, false, false, false, true, SelLevel>), g, b, lds, c.stream, c.d, rootN, do_select, SelLevel{});
+            if (c.synthetic) hipLaunchKernelGGL((k_step<N, true, false, false, true, false, SelLevel>), g, b, lds, c.stream, c.d, rootN, do_select, SelLevel{});
+            else hipLaunchKernelGGL((k_step<N, false, false, false, true, false, SelLevel>), g, b, lds, c.stream, c.d, rootN, do_select, SelLevel{});
         }
+        return;
+    }
+    if (c.d.cand_radius) {                                     // az_set_candidates (never with the solver or the selection rule): the CAND kernels
+        if (c.d.S > DEFAULT_MAX_S) {
+            if (c.synthetic) hipLaunchKernelGGL((k_step<N, true, true, false, false, true, CandLevel>), g, b, 0, c.stream, c.d, rootN, do_select, CandLevel{});
+            else hipLaunchKernelGGL((k_step<N, false, true, false, false, true, CandLevel>), g, b, 0, c.stream, c.d, rootN, do_select, CandLevel{});
+            return;
+        }
+        const size_t lds = (size_t)(c.d.S + 2) * sizeof(double);
+        if (c.synthetic) hipLaunchKernelGGL((k_step<N, true, false, false, false, true, CandLevel>), g, b, lds, c.stream, c.d, rootN, do_select, CandLevel{});
+        else hipLaunchKernelGGL((k_step<N, false, false, false, false, true, CandLevel>), g, b, lds, c.stream, c.d, rootN, do_select, CandLevel{});
         return;
     }
     if (c.d.S > DEFAULT_MAX_S) {
@@ -115,18 +126,29 @@ void step_vl(const LaunchCtx &c, int sims_done, int nb_next)
     dim3 g((c.d.B + 3) / 4), b(256);
     if (c.d.sel_cpuct) {                                       // az_set_selection: the SEL kernels
         if (c.d.S > DEFAULT_MAX_S) {
-            if (c.synthetic) hipLaunchKernelGGL((k_step_vl<N, true, true, true, SelLevel, unsigned char *>), g, b, 0, c.stream, c.d, sims_done, nb_next, SelLevel{}, c.inflight);
-            else hipLaunchKernelGGL((k_step_vl<N, false, true, true, SelLevel, unsigned char *>), g, b, 0, c.stream, c.d, sims_done, nb_next, SelLevel{}, c.inflight);
+            if (c.synthetic) hipLaunchKernelGGL((k_step_vl<N, true, true, true, false, SelLevel, unsigned char *>), g, b, 0, c.stream, c.d, sims_done, nb_next, SelLevel{}, c.inflight);
+            else hipLaunchKernelGGL((k_step_vl<N, false, true, true, false, SelLevel, unsigned char *>), g, b, 0, c.stream, c.d, sims_done, nb_next, SelLevel{}, c.inflight);
             return;
         }
         const size_t lds = (size_t)(c.d.S + 2) * sizeof(double);
-        if (c.synthetic) hipLaunchKernelGGL((k_step_vl<N, true, false, true, SelLevel>), g, b, lds, c.stream, c.d, sims_done, nb_next, SelLevel{});
-        else hipLaunchKernelGGL((k_step_vl<N, false, false, true, SelLevel>), g, b, lds, c.stream, c.d, sims_done, nb_next, SelLevel{});
+        if (c.synthetic) hipLaunchKernelGGL((k_step_vl<N, true, false, true, false, SelLevel>), g, b, lds, c.stream, c.d, sims_done, nb_next, SelLevel{});
+        else hipLaunchKernelGGL((k_step_vl<N, false, false, true, false, SelLevel>), g, b, lds, c.stream, c.d, sims_done, nb_next, SelLevel{});
+        return;
+    }
+    if (c.d.cand_radius) {                                     // az_set_candidates: the CAND kernels
+        if (c.d.S > DEFAULT_MAX_S) {
+            if (c.synthetic) hipLaunchKernelGGL((k_step_vl<N, true, true, false, true, CandLevel, unsigned char *>), g, b, 0, c.stream, c.d, sims_done, nb_next, CandLevel{}, c.inflight);
+            else hipLaunchKernelGGL((k_step_vl<N, false, true, false, true, CandLevel, unsigned char *>), g, b, 0, c.stream, c.d, sims_done, nb_next, CandLevel{}, c.inflight);
+            return;
+        }
+        const size_t lds = (size_t)(c.d.S + 2) * sizeof(double);
+        if (c.synthetic) hipLaunchKernelGGL((k_step_vl<N, true, false, false, true, CandLevel>), g, b, lds, c.stream, c.d, sims_done, nb_next, CandLevel{});
+        else hipLaunchKernelGGL((k_step_vl<N, false, false, false, true, CandLevel>), g, b, lds, c.stream, c.d, sims_done, nb_next, CandLevel{});
         return;
     }
     if (c.d.S > DEFAULT_MAX_S) {
-        if (c.synthetic) hipLaunchKernelGGL((k_step_vl<N, true, true, false, unsigned char *>), g, b, 0, c.stream, c.d, sims_done, nb_next, c.inflight);
-        else hipLaunchKernelGGL((k_step_vl<N, false, true, false, unsigned char *>), g, b, 0, c.stream, c.d, sims_done, nb_next, c.inflight);
+        if (c.synthetic) hipLaunchKernelGGL((k_step_vl<N, true, true, false, false, unsigned char *>), g, b, 0, c.stream, c.d, sims_done, nb_next, c.inflight);
+        else hipLaunchKernelGGL((k_step_vl<N, false, true, false, false, unsigned char *>), g, b, 0, c.stream, c.d, sims_done, nb_next, c.inflight);
         return;
     }
     const size_t lds = (size_t)(c.d.S + 2) * sizeof(double);   // sqrt table

@@ -150,6 +150,9 @@ struct DevState {
     const double *sel_cpuct;       // [S+3] c_puct + factor * log((i + base + 1) / base), beside sqrt_table and indexed like it
     const double *sel_mass;        // [SEL_MASS_STEPS + 1] sqrt(i / SEL_MASS_STEPS)
     double sel_fpu, sel_fpu_root;  // r_X below the root / at the root
+    // --- opt-in candidate moves (az_set_candidates): 0 = off, nothing reads it then.  The CAND tree kernels expand, noise and
+    // select over the empty cells within this Chebyshev distance of a stone (cand_plane below) ---
+    int cand_radius;
 };
 constexpr int SEL_MASS_STEPS = 4096, SEL_MASS_SHIFT = 12;      // mass is a sum of floor(P * 2^24): 2^24 >> 12 = 4096 steps for a mass of 1
 // the visited prior mass of one child, an integer so that the wave sum has no order
@@ -239,6 +242,95 @@ __device__ __forceinline__ void wave_mem_sync()
     // orders this wave's global/LDS writes before its later reads (cross-lane hand-off inside one wave)
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __builtin_amdgcn_wave_barrier();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Candidate moves (az_set_candidates, the rule is in include/az_engine.h): C(X) = the empty cells within Chebyshev distance
+// `radius` of a stone, every cell of an empty board.  A separable dilation of the occupancy on the 4 x u64 plane: `radius`
+// steps of one column to either side (the column masks keep a row's end out of its neighbour row), then `radius` steps of
+// one row up and down (256-bit shifts by N), every step clipped to the n*n bits of the board; less the stones.  The plane
+// and the loop count are wave-uniform, the words are named (no run-time index), so all of it is scalar work.
+// ------------------------------------------------------------------------------------------------
+template <int N>
+struct CandGeo {
+    // word q of: the board's n*n bits less column `skip` (-1: less nothing)
+    static constexpr u64 keep(int q, int skip)
+    {
+        u64 m = 0ull;
+        for (int b = 0; b < 64; b++) {
+            const int j = 64 * q + b;
+            if (j < N * N && j % N != skip) m |= 1ull << b;
+        }
+        return m;
+    }
+    static constexpr u64 B0 = keep(0, -1), B1 = keep(1, -1), B2 = keep(2, -1), B3 = keep(3, -1);                  // the board
+    static constexpr u64 L0 = keep(0, 0), L1 = keep(1, 0), L2 = keep(2, 0), L3 = keep(3, 0);                      // ... less column 0
+    static constexpr u64 R0 = keep(0, N - 1), R1 = keep(1, N - 1), R2 = keep(2, N - 1), R3 = keep(3, N - 1);      // ... less the last column
+};
+template <int N>
+__device__ __forceinline__ Plane cand_plane(const Plane &occ, int radius)
+{
+    typedef CandGeo<N> C;
+    Plane h = occ;
+    if ((occ.w[0] | occ.w[1] | occ.w[2] | occ.w[3]) == 0ull) {
+        h.w[0] = C::B0; h.w[1] = C::B1; h.w[2] = C::B2; h.w[3] = C::B3;
+        return h;
+    }
+    for (int s = 0; s < radius; s++) {                        // one column to the right (<< 1) and to the left (>> 1)
+        Plane t;
+        t.w[0] = ((h.w[0] << 1) & C::L0) | (((h.w[0] >> 1) | (h.w[1] << 63)) & C::R0);
+        t.w[1] = (((h.w[1] << 1) | (h.w[0] >> 63)) & C::L1) | (((h.w[1] >> 1) | (h.w[2] << 63)) & C::R1);
+        t.w[2] = (((h.w[2] << 1) | (h.w[1] >> 63)) & C::L2) | (((h.w[2] >> 1) | (h.w[3] << 63)) & C::R2);
+        t.w[3] = (((h.w[3] << 1) | (h.w[2] >> 63)) & C::L3) | ((h.w[3] >> 1) & C::R3);
+        h.w[0] |= t.w[0]; h.w[1] |= t.w[1]; h.w[2] |= t.w[2]; h.w[3] |= t.w[3];
+    }
+    for (int s = 0; s < radius; s++) {                        // one row down (<< N) and up (>> N)
+        Plane t;
+        t.w[0] = ((h.w[0] << N) | (h.w[0] >> N) | (h.w[1] << (64 - N))) & C::B0;
+        t.w[1] = ((h.w[1] << N) | (h.w[0] >> (64 - N)) | (h.w[1] >> N) | (h.w[2] << (64 - N))) & C::B1;
+        t.w[2] = ((h.w[2] << N) | (h.w[1] >> (64 - N)) | (h.w[2] >> N) | (h.w[3] << (64 - N))) & C::B2;
+        t.w[3] = ((h.w[3] << N) | (h.w[2] >> (64 - N)) | (h.w[3] >> N)) & C::B3;
+        h.w[0] |= t.w[0]; h.w[1] |= t.w[1]; h.w[2] |= t.w[2]; h.w[3] |= t.w[3];
+    }
+    h.w[0] &= ~occ.w[0]; h.w[1] &= ~occ.w[1]; h.w[2] &= ~occ.w[2]; h.w[3] &= ~occ.w[3];
+    return h;
+}
+// What a CAND kernel keeps beside the shared body: C(X) of the level being selected, and of the node being expanded.  Like
+// SelLevel it is a last kernel argument of the CAND kernels only (its value is ignored), so that a kernel without the option
+// declares nothing for it and keeps its code.
+struct CandLevel { Plane lvl, exp; };
+template <class... Rest>
+__device__ __forceinline__ CandLevel &cand_level(CandLevel &c, Rest &...) { return c; }
+// cell j is in the level's / the expanded node's plane; the overloads without a CandLevel are never called for their value
+template <class... A> __device__ __forceinline__ bool cand_lvl(int, A &...) { return false; }
+template <class... A> __device__ __forceinline__ bool cand_lvl(int j, CandLevel &c, A &...) { return pl_get(c.lvl, j); }
+template <class... A> __device__ __forceinline__ bool cand_exp(int, A &...) { return false; }
+template <class... A> __device__ __forceinline__ bool cand_exp(int j, CandLevel &c, A &...) { return pl_get(c.exp, j); }
+// The root's Dirichlet mix under CAND: the tape and legal_rank stay, the sample is cut down to the candidates and renormalised
+// by its float64 canonical wave sum (lane partials over its cells in ascending order, then the butterfly); nothing is fused.
+template <int CPL>
+__device__ __forceinline__ void cand_mix_noise(const DevState &d, const Plane &occ, const Plane &cand, const double *nz, int lane,
+                                               float (&P)[CPL])
+{
+    double nc[CPL], part = 0.0;
+#pragma unroll
+    for (int i = 0; i < CPL; i++) {
+        const int j = lane + 64 * i;
+        nc[i] = 0.0;
+        if (pl_get(cand, j)) {
+            nc[i] = nz[j - pl_rank(occ, j)];
+            part = part + nc[i];
+        }
+    }
+    const double t = wave_sum_butterfly_d(part);
+#pragma unroll
+    for (int i = 0; i < CPL; i++) {
+        if (pl_get(cand, lane + 64 * i)) {
+            const float scaled = d.one_minus_w * P[i];
+            const double share = nc[i] / t;
+            P[i] = (float)((double)scaled + d.w_noise * share);
+        }
+    }
 }
 
 
@@ -529,10 +621,14 @@ __device__ __forceinline__ int proof_mark(unsigned char *prf, const unsigned *pa
 // SEL (az_set_selection): instantiations of their own as well, never together with SOLVER.  Per level one 32-bit wave sum (the
 // visited prior mass), two uniform table reads from HBM (c(count) beside the sqrt, issued with it; the mass table once the
 // sum is known) and the chosen edge's Q carried down as the next node's value; the root's value stays in d.root_v for the ply.
-template <int N, bool SYNTH, bool DEEP = false, bool SOLVER = false, bool SEL = false, class... Sel>
+// CAND (az_set_candidates): instantiations of their own again, never together with SOLVER or SEL.  The root's and every leaf's
+// softmax, the root's noise and every level's argmax run over the node's candidate plane (cand_plane) instead of the board /
+// the empty cells; the plane is formed from the position where it is needed, per expansion and per level of the descent.
+template <int N, bool SYNTH, bool DEEP = false, bool SOLVER = false, bool SEL = false, bool CAND = false, class... Sel>
 __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN, int do_select, Sel... sel)
 {
-    static_assert(sizeof...(Sel) == (SEL ? 1 : 0) && !(SEL && SOLVER), "the SEL kernels take a SelLevel; never with SOLVER");
+    static_assert(sizeof...(Sel) == (SEL || CAND ? 1 : 0) && !(SEL && SOLVER), "the SEL kernels take a SelLevel; never with SOLVER");
+    static_assert(!(CAND && (SEL || SOLVER)), "the CAND kernels take a CandLevel; they carry neither the solver nor the selection rule");
     typedef TreeGeo<N> G;
     extern __shared__ double sq_lds[];                 // np.sqrt(N + 1e-8), N = 0..S+1 (mcts.py:73)
     const int lane = threadIdx.x & 63;
@@ -586,7 +682,7 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
     Edge *rows = d.edges + (size_t)b * d.R * G::RW;
     const int budget = budget_raw < 0 ? -budget_raw : budget_raw;     // simulations of this slot's ply: S unless the cap says less
     const bool root_noise = d.add_noise && budget_raw > 0;            // a FAST ply uses the priors as they are
-    const bool gumbel = !SYNTH && d.gumbel_m > 0 && root_noise;       // Gumbel root search (kernel-argument test, uniform): the noised root only
+    const bool gumbel = !SYNTH && !CAND && d.gumbel_m > 0 && root_noise;      // Gumbel root search (kernel-argument test, uniform): the noised root only
 
     // ---------------- stage 1: evaluation -> expand -> backup ----------------
     if (kind == LEAF_REUSE) {
@@ -614,6 +710,12 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
         float v = 0.0f;
         if (kind == LEAF_ROOT || kind == LEAF_EXPAND) {
             float P[G::CPL];
+            if constexpr (CAND) {                             // C(X) of the node being expanded
+                Plane occx;
+#pragma unroll
+                for (int q = 0; q < 4; q++) occx.w[q] = lme.w[q] | lopp.w[q];
+                cand_level(sel...).exp = cand_plane<N>(occx, d.cand_radius);
+            }
             if (SYNTH) {
                 // build-owned deterministic evaluator (test hook behind the policy_value_fn seam, mcts.py:87-93)
                 unsigned hx = 0;
@@ -635,6 +737,10 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
                 }
                 int vv = (int)(az_fmix32(hs ^ 0x7F4A7C15u) & 0x1FFu);
                 v = (float)(vv - 256) / 256.0f;
+                if constexpr (CAND) {                         // not normalised: candidates keep their prior, every other cell gets 0
+#pragma unroll
+                    for (int i = 0; i < G::CPL; i++) P[i] = cand_exp(lane + 64 * i, sel...) ? P[i] : 0.0f;
+                }
             } else {
                 if (d.cache && kind_raw == kind) {            // a fresh evaluation: remember it
                     float xc[G::CPL];
@@ -649,11 +755,11 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
                     for (int i = 0; i < G::CPL; i++) P[i] = lane + 64 * i < G::nn ? x[i] : 0.0f;
                     v = __shfl(h_l, 0, 64);
                 } else {
-                // controller.py:49 softmax over all n^2 logits (no legality mask), canonical wave order
+                // controller.py:49 softmax over all n^2 logits (no legality mask), canonical wave order; CAND: over C(X)
                 float mx = -INFINITY;
 #pragma unroll
                 for (int i = 0; i < G::CPL; i++) {
-                    if (lane + 64 * i >= G::nn) x[i] = -INFINITY;
+                    if (CAND ? !cand_exp(lane + 64 * i, sel...) : lane + 64 * i >= G::nn) x[i] = -INFINITY;
                     mx = fmaxf(mx, x[i]);
                 }
                 mx = wave_max_f(mx);
@@ -661,7 +767,7 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
 #pragma unroll
                 for (int i = 0; i < G::CPL; i++) {
                     P[i] = 0.0f;
-                    if (lane + 64 * i < G::nn) {
+                    if (CAND ? cand_exp(lane + 64 * i, sel...) : lane + 64 * i < G::nn) {
                         P[i] = az_expf(x[i] - mx);
                         part = part + P[i];
                     }
@@ -687,6 +793,9 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
 #pragma unroll
                 for (int q = 0; q < 4; q++) occ.w[q] = lme.w[q] | lopp.w[q];
                 const double *nz = d.noise + (size_t)game * d.noise_stride + d.noise_off[ply];
+                if constexpr (CAND) {
+                    cand_mix_noise<G::CPL>(d, occ, cand_level(sel...).exp, nz, lane, P);
+                } else {
 #pragma unroll
                 for (int i = 0; i < G::CPL; i++) {
                     int j = lane + 64 * i;
@@ -695,6 +804,7 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
                         float scaled = d.one_minus_w * P[i];
                         P[i] = (float)((double)scaled + d.w_noise * nz[rank]);
                     }
+                }
                 }
             }
             if constexpr (SEL) {
@@ -784,6 +894,7 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
 #pragma unroll
         for (int q = 0; q < 4; q++) occ.w[q] = me.w[q] | opp.w[q];
         const double sq = DEEP ? sq_next : sq_lds[npar];      // np.sqrt(self.N + 1e-8), mcts.py:73
+        if constexpr (CAND) cand_level(sel...).lvl = cand_plane<N>(occ, d.cand_radius);     // C(X) of this level's node, from its position
         double best = 0.0;
         int bi = -1, bN = 0, bC = 0, bS = 0;
         if constexpr (SEL) {
@@ -859,7 +970,7 @@ __global__ __launch_bounds__(STEP_WAVES * 64) void k_step(DevState d, int rootN,
 #pragma unroll
         for (int i = 0; i < G::CPL; i++) {
             int j = lane + 64 * i;
-            if (j < G::nn && !pl_get(occ, j)) {
+            if (CAND ? cand_lvl(j, sel...) : (j < G::nn && !pl_get(occ, j))) {
                 Edge e = rows[(size_t)row * G::RW + j];
                 double Q = e.N ? e.W / (double)e.N : 0.0;     // mcts.py:80 Q = W/N (0.0 while unvisited)
                 double sc = Q + ((d.c_puct * (double)e.P) * sq) / (double)(1 + (int)e.N);
@@ -972,11 +1083,18 @@ __global__ __launch_bounds__(256) void k_root_cache(DevState d)
 // narrow kernel adds 1 << EDGE_N_BITS, lowered at backup, zeroed with every new row; the sqrt table is read from HBM as in
 // k_step<.., DEEP>.  Mechanically the same rule: bit-identical to the oracle at any S.
 // ------------------------------------------------------------------------------------------------
-template <int N, bool SYNTH>
+// CAND: the caller's CandLevel (and whatever follows it) comes last; its exp plane is formed here, as in k_step
+template <int N, bool SYNTH, bool CAND = false, class... Cand>
 __device__ __forceinline__ void vl_leaf_eval(const DevState &d, size_t it, const Plane &lme, const Plane &lopp, int leaf_last,
-                                             int netid, bool fresh, int lane, float (&P)[TreeGeo<N>::CPL], float &v)
+                                             int netid, bool fresh, int lane, float (&P)[TreeGeo<N>::CPL], float &v, Cand &... cand)
 {
     typedef TreeGeo<N> G;
+    if constexpr (CAND) {
+        Plane occx;
+#pragma unroll
+        for (int q = 0; q < 4; q++) occx.w[q] = lme.w[q] | lopp.w[q];
+        cand_level(cand...).exp = cand_plane<N>(occx, d.cand_radius);
+    }
     if (SYNTH) {
         unsigned hx = 0;
 #pragma unroll
@@ -997,6 +1115,10 @@ __device__ __forceinline__ void vl_leaf_eval(const DevState &d, size_t it, const
         }
         int vv = (int)(az_fmix32(hs ^ 0x7F4A7C15u) & 0x1FFu);
         v = (float)(vv - 256) / 256.0f;
+        if constexpr (CAND) {
+#pragma unroll
+            for (int i = 0; i < G::CPL; i++) P[i] = cand_exp(lane + 64 * i, cand...) ? P[i] : 0.0f;
+        }
         return;
     }
     float x[G::CPL];
@@ -1028,7 +1150,7 @@ __device__ __forceinline__ void vl_leaf_eval(const DevState &d, size_t it, const
     float mx = -INFINITY;
 #pragma unroll
     for (int i = 0; i < G::CPL; i++) {
-        if (lane + 64 * i >= G::nn) x[i] = -INFINITY;
+        if (CAND ? !cand_exp(lane + 64 * i, cand...) : lane + 64 * i >= G::nn) x[i] = -INFINITY;
         mx = fmaxf(mx, x[i]);
     }
     mx = wave_max_f(mx);
@@ -1036,7 +1158,7 @@ __device__ __forceinline__ void vl_leaf_eval(const DevState &d, size_t it, const
 #pragma unroll
     for (int i = 0; i < G::CPL; i++) {
         P[i] = 0.0f;
-        if (lane + 64 * i < G::nn) {
+        if (CAND ? cand_exp(lane + 64 * i, cand...) : lane + 64 * i < G::nn) {
             P[i] = az_expf(x[i] - mx);
             part = part + P[i];
         }
@@ -1052,12 +1174,16 @@ __device__ __forceinline__ unsigned char *inflight_arg() { return nullptr; }
 __device__ __forceinline__ unsigned char *inflight_arg(unsigned char *p) { return p; }
 __device__ __forceinline__ unsigned char *inflight_arg(SelLevel &) { return nullptr; }
 __device__ __forceinline__ unsigned char *inflight_arg(SelLevel &, unsigned char *p) { return p; }
+__device__ __forceinline__ unsigned char *inflight_arg(CandLevel &) { return nullptr; }
+__device__ __forceinline__ unsigned char *inflight_arg(CandLevel &, unsigned char *p) { return p; }
 // InFlight is empty for the default kernel (its arguments stay those of the narrow kernel) and `unsigned char *` for DEEP
 // SEL (az_set_selection): k_step's rule on the counts and totals this kernel scores with, N + in-flight and W - in-flight; a
 // SelLevel goes in front of the extra arguments
-template <int N, bool SYNTH, bool DEEP = false, bool SEL = false, class... InFlight>
+// CAND (az_set_candidates): as in k_step, never with SEL; a CandLevel goes in front of the extra arguments
+template <int N, bool SYNTH, bool DEEP = false, bool SEL = false, bool CAND = false, class... InFlight>
 __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int nb_next, InFlight... inflight)
 {
+    static_assert(!(CAND && SEL), "the CAND kernels do not carry the selection rule");
     typedef TreeGeo<N> G;
     extern __shared__ double sq_lds[];                 // np.sqrt(N + 1e-8), N = 0..S+1 (mcts.py:73)
     __shared__ float vals_lds[4][VL_MAX];              // leaf values of the batch being finished (duplicates read them)
@@ -1097,7 +1223,8 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
             const Plane lme = pl_load(d.leaf + it * 8), lopp = pl_load(d.leaf + it * 8 + 4);
             const int leaf_last = d.leaf_last[it];
             float P[G::CPL];
-            vl_leaf_eval<N, SYNTH>(d, it, lme, lopp, leaf_last, netid, kind_raw == kind, lane, P, v);
+            if constexpr (CAND) vl_leaf_eval<N, SYNTH, true>(d, it, lme, lopp, leaf_last, netid, kind_raw == kind, lane, P, v, inflight...);
+            else vl_leaf_eval<N, SYNTH>(d, it, lme, lopp, leaf_last, netid, kind_raw == kind, lane, P, v);
             if constexpr (SEL) {
                 if (kind == LEAF_ROOT && lane == 0) d.root_v[b] = v;      // az_set_selection: the root's value for the ply
             }
@@ -1107,6 +1234,9 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
 #pragma unroll
                 for (int q = 0; q < 4; q++) occ.w[q] = lme.w[q] | lopp.w[q];
                 const double *nz = d.noise + (size_t)game * d.noise_stride + d.noise_off[ply];
+                if constexpr (CAND) {
+                    cand_mix_noise<G::CPL>(d, occ, cand_level(inflight...).exp, nz, lane, P);
+                } else {
 #pragma unroll
                 for (int i = 0; i < G::CPL; i++) {
                     int c = lane + 64 * i;
@@ -1115,6 +1245,7 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
                         float scaled = d.one_minus_w * P[i];
                         P[i] = (float)((double)scaled + d.w_noise * nz[rank]);
                     }
+                }
                 }
             }
             // mcts.py:50-64 expand: one edge per cell (occupied cells are never selected)
@@ -1184,6 +1315,7 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
 #pragma unroll
             for (int q = 0; q < 4; q++) occ.w[q] = me.w[q] | opp.w[q];
             const double sq = DEEP ? sq_next : sq_lds[npar];      // np.sqrt(self.N + 1e-8), mcts.py:73
+            if constexpr (CAND) cand_level(inflight...).lvl = cand_plane<N>(occ, d.cand_radius);     // C(X) of this level's node
             double best = 0.0;
             int bi = -1, bN = 0, bC = 0;
             if constexpr (SEL) {
@@ -1223,7 +1355,7 @@ __global__ __launch_bounds__(256) void k_step_vl(DevState d, int sims_done, int 
 #pragma unroll
             for (int i = 0; i < G::CPL; i++) {
                 int c = lane + 64 * i;
-                if (c < G::nn && !pl_get(occ, c)) {
+                if (CAND ? cand_lvl(c, inflight...) : (c < G::nn && !pl_get(occ, c))) {
                     Edge e = rows[(size_t)row * G::RW + c];
                     // simulations of this batch in flight through the edge
                     const int fl = DEEP ? (infl ? (int)infl[(size_t)row * G::RW + c] : 0) : (int)e.N >> EDGE_N_BITS;

@@ -7,10 +7,10 @@ them to the engine, so np.random.seed(s) reproduces the reference's choices."""
 import numpy as np
 
 from . import constants as _c
-from ._capi import (AZ_MAX_SIMULATIONS, FORCED_K_MAX, GUMBEL_DEFAULTS, GUMBEL_M_MAX, Engine, check_selection, check_threat_search,
+from ._capi import (AZ_MAX_SIMULATIONS, FORCED_K_MAX, GUMBEL_DEFAULTS, GUMBEL_M_MAX, Engine, check_candidates, check_selection, check_threat_search,
                     win_rule_name)
 from .controller import BatchPolicyValueFn, PolicyValueFn, device_index, model_kind, weights_version
-from .options import apply_options, bring_selection, check_combination, switched_on
+from .options import apply_options, bring_candidates, bring_selection, check_combination, switched_on
 
 
 def numpy_log_table(S):
@@ -64,7 +64,7 @@ def check_gumbel(gumbel, subtree_reuse=False, virtual_loss=1, forced_playouts=No
 
 class MCTS:
     def __init__(self, policy_value_fn, num_simulations, c_puct, dirichlet_alpha=0.3, dirichlet_weight=0.25, virtual_loss=1,
-                 forced_playouts=None, gumbel=None, solver=False, threat_search=None, selection=None):
+                 forced_playouts=None, gumbel=None, solver=False, threat_search=None, selection=None, candidates=None):
         if not callable(policy_value_fn):
             raise TypeError("policy_value_fn must be callable: state -> (policy [n, n], value)")
         # make_policy_value_fn(controller): the leaves are evaluated inside the HIP engine.  Any other callable keeps the
@@ -98,6 +98,11 @@ class MCTS:
         # in every search (az_set_selection).  Not with gumbel or solver.
         self.selection = check_selection(selection)
         check_combination(switched_on(selection=self.selection, gumbel=self.gumbel, solver=self.solver), "selection")
+        # opt-in: dict(radius=r), every search expands, noises and selects only the empty cells within r of a stone, the priors
+        # normalised over them (az_set_candidates).  Controller-backed evaluators only; not with gumbel, solver or selection.
+        self.candidates = check_candidates(candidates)
+        check_combination(switched_on(candidates=self.candidates, gumbel=self.gumbel, solver=self.solver, selection=self.selection,
+                                      evaluator=policy_value_fn if (self._external or self._batched) else None), "candidates")
         self.last_proof = None
         self._engine = None
         self._version = None
@@ -112,10 +117,12 @@ class MCTS:
         if not self._external:
             eng.set_virtual_loss(self.virtual_loss)
         # the rule is the state's (_ruled); games, and with them start positions, resignation and the playout cap, are not played here
+        bring_candidates(eng, self.candidates, before=True)
         bring_selection(eng, self.selection, before=True)
         apply_options(eng, win_rule="freestyle", start_positions=None, first=0, resign=None, playout_cap=None,
                       forced_playouts=self.forced_playouts, gumbel=self.gumbel, solver=self.solver, threat_search=self.threat_search)
-        return bring_selection(eng, self.selection, before=False)
+        bring_selection(eng, self.selection, before=False)
+        return bring_candidates(eng, self.candidates, before=False)
 
     @staticmethod
     def _state_rule(state):

@@ -1,7 +1,8 @@
 """The search options of the seams (MCTS, SelfPlayManager, ModelEvaluator, train.py): which of them combine, and how an engine
 is brought to a set of them.  A new option is wired into the seams here: its row(s) in CONFLICTS, its set / clear in apply_options.
 The selection rule has a table and a function of its own (SELECTION_CONFLICTS, bring_selection): the seams call that function
-on either side of apply_options."""
+on either side of apply_options.  So do candidate moves (CANDIDATE_CONFLICTS, bring_candidates), outermost: off before the
+selection rule may come on, on after it has gone off."""
 
 # Pairs of options that cannot be combined, with the text a seam refuses them with: the engine's table (g_conflicts in
 # csrc/az_engine.hip) for the options the seams expose.  The first row whose two options are both on names the error.
@@ -32,6 +33,14 @@ SELECTION_CONFLICTS = (
     ("selection", "solver", "the selection rule does not combine with the solver (and so not with the threat search)"),
     ("selection", "gumbel", "the selection rule does not combine with the Gumbel root search"),
 )
+# ... and the pairs candidate moves (az_set_candidates) add to it, read after SELECTION_CONFLICTS
+CANDIDATE_CONFLICTS = (
+    ("candidates", "subtree_reuse", "candidate moves do not combine with subtree_reuse: a retained root's priors were not made under the rule"),
+    ("candidates", "gumbel", "candidate moves do not combine with the Gumbel root search: its top-m and target are defined over the legal cells"),
+    ("candidates", "solver", "candidate moves do not combine with the solver (and so not with the threat search): no proof when moves were left out"),
+    ("candidates", "selection", "candidate moves do not combine with the selection rule yet"),
+    ("candidates", "evaluator", "candidate moves need the engine's own net: an outside evaluator returns priors, not logits"),
+)
 
 
 def switched_on(**options):
@@ -40,8 +49,8 @@ def switched_on(**options):
 
 
 def check_combination(on, of=None):
-    """ValueError for the first rule of CONFLICTS / NEEDS / SELECTION_CONFLICTS that the set `on` of option names breaks; of: only
-    the rules that speak of this option."""
+    """ValueError for the first rule of CONFLICTS / NEEDS / SELECTION_CONFLICTS / CANDIDATE_CONFLICTS that the set `on` of option
+    names breaks; of: only the rules that speak of this option."""
     for a, b, message in CONFLICTS:
         if a in on and b in on and of in (None, a, b):
             raise ValueError(message)
@@ -49,6 +58,9 @@ def check_combination(on, of=None):
         if a in on and b not in on and of in (None, a, b):
             raise ValueError(message)
     for a, b, message in SELECTION_CONFLICTS:
+        if a in on and b in on and of in (None, a, b):
+            raise ValueError(message)
+    for a, b, message in CANDIDATE_CONFLICTS:
         if a in on and b in on and of in (None, a, b):
             raise ValueError(message)
 
@@ -105,6 +117,21 @@ def bring_selection(eng, selection, before):
             eng.set_selection(on=False)
     elif selection is not None and not same:
         eng.set_selection(**selection)
+    return eng
+
+
+def bring_candidates(eng, candidates, before):
+    """Candidate moves of a new or cached engine (candidates: the checked dict, None = off), shaped like bring_selection and
+    called outside it: before=True, ahead of everything that may switch a refused partner on (the selection rule included),
+    takes the option off unless the engine already has exactly this radius; before=False, after everything that switches those
+    off, sets it."""
+    have = eng.candidates()
+    same = candidates is not None and have == candidates["radius"]
+    if before:
+        if have and not same:
+            eng.set_candidates(0)
+    elif candidates is not None and not same:
+        eng.set_candidates(candidates["radius"])
     return eng
 
 

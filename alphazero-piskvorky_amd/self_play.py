@@ -7,10 +7,10 @@ import torch
 
 from . import constants as _c
 from . import parallel
-from ._capi import check_selection, check_threat_search, AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine, playout_cap_permille, resign_permille, win_rule_name
+from ._capi import check_candidates, check_selection, check_threat_search, AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine, playout_cap_permille, resign_permille, win_rule_name
 from .controller import BatchPolicyValueFn, device_index, model_kind
 from .mcts import check_forced_playouts, check_gumbel, check_solver, numpy_log_table
-from .options import apply_options, bring_selection, check_combination, switched_on
+from .options import apply_options, bring_candidates, bring_selection, check_combination, switched_on
 
 
 def default_temperature_schedule(move: int) -> float:
@@ -116,7 +116,7 @@ class SelfPlayManager:
                  eval_cache: int = 0, virtual_loss: int = 1, trunk: str = "f32", leaf_symmetry: bool = False,
                  start_positions=None, resign: dict = None, evaluator: BatchPolicyValueFn = None,
                  playout_cap: dict = None, forced_playouts: dict = None, gumbel: dict = None, solver: bool = False,
-                 win_rule: str = None, threat_search: dict = None, selection: dict = None):
+                 win_rule: str = None, threat_search: dict = None, selection: dict = None, candidates: dict = None):
         self.controller = controller
         # which game is played: "freestyle" (constants.WIN_RULE's default, the reference's: a run of WIN_LENGTH or more wins) or
         # "exact" (standard Gomoku: exactly WIN_LENGTH, an overline wins nothing; az_set_win_rule).  Combines with every option.
@@ -160,6 +160,11 @@ class SelfPlayManager:
         # (az_set_selection).  Not with subtree_reuse, gumbel or solver.  Whether it trains a stronger net per GPU hour has not
         # been measured (tools/selection_gain.py measures throughput, game length and how wide the roots get).
         self.selection = selection
+        # opt-in candidate moves: dict(radius=r); every search expands, noises and selects only the empty cells within Chebyshev
+        # distance r of a stone (every cell on an empty board), the priors normalised over them (az_set_candidates).  Not with
+        # subtree_reuse, gumbel, solver, selection or an outside evaluator.  Whether it trains a stronger net per GPU hour has not
+        # been measured (tools/candidates_gain.py measures throughput and the shape of the searches).
+        self.candidates = candidates
         self.temperature_schedule = temperature_schedule
         self.concurrent_games = concurrent_games or _c.CONCURRENT_GAMES
         self.augmentation = augmentation      # 4 = the reference's rotations (self_play.py:94-108), 8 = full dihedral group, 1 = none
@@ -191,9 +196,11 @@ class SelfPlayManager:
         self.solver = check_solver(self.solver)
         self.threat_search = check_threat_search(self.threat_search)
         self.selection = check_selection(self.selection)
+        self.candidates = check_candidates(self.candidates)
         check_combination(switched_on(subtree_reuse=self.subtree_reuse, virtual_loss=self.virtual_loss, leaf_symmetry=self.leaf_symmetry,
                                       evaluator=self.evaluator, playout_cap=self.playout_cap, forced_playouts=self.forced_playouts,
-                                      gumbel=self.gumbel, solver=self.solver, threat_search=self.threat_search, selection=self.selection))
+                                      gumbel=self.gumbel, solver=self.solver, threat_search=self.threat_search, selection=self.selection,
+                                      candidates=self.candidates))
 
     def _eng(self, n, k, slots):
         p = self.mcts_params
@@ -268,6 +275,7 @@ class SelfPlayManager:
         eng = self._eng(n, k, max(1, min(self.concurrent_games, max(mine, 1))))
         if self.evaluator is None:
             eng.load_weights(self.controller.net.state_dict(), 0)
+        bring_candidates(eng, self.candidates, before=True)    # before the selection rule or any other refused partner may come on
         bring_selection(eng, self.selection, before=True)      # before subtree reuse, the solver or the Gumbel root may come on
         eng.set_subtree_reuse(self.subtree_reuse)
         if eng.trunk_mode() != self.trunk:
@@ -277,6 +285,7 @@ class SelfPlayManager:
                       playout_cap=self.playout_cap, forced_playouts=self.forced_playouts, gumbel=self.gumbel, solver=self.solver,
                       threat_search=self.threat_search)
         bring_selection(eng, self.selection, before=False)
+        bring_candidates(eng, self.candidates, before=False)
         self.last_resign_stats = self.last_playout_cap_stats = None
         if mine > 0:
             self.last_counters = eng.selfplay(mine, seed0=seed0 + lo, temperature_table=T)

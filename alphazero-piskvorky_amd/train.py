@@ -29,7 +29,7 @@ PROMOTION_THRESHOLD = 0.55          # promoter.py:19, strict ">" with draws coun
 
 def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=None, log=print, device_replay=False,
         subtree_reuse=False, trunk="f32", eval_sims=None, start_positions=None, resign=None, torch_eval=False,
-        playout_cap=None, forced_playouts=None, gumbel=None, solver=False, win_rule=None, threat_search=None, selection=None):
+        playout_cap=None, forced_playouts=None, gumbel=None, solver=False, win_rule=None, threat_search=None, selection=None, candidates=None):
     """eval_sims: simulations per move in the arena (evaluator.py:53-62 takes NUM_EVAL_SIMULATIONS = 200 whatever the
     self-play count is; main() passes that constant); None = as many as self-play, which keeps small test runs short.
     device_replay=True keeps the examples on the GPU from the episode-end gather to the optimizer step (packed records
@@ -57,6 +57,9 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
     selection: dict(fpu, fpu_root, cpuct_base, cpuct_factor) for the self-play searches (Engine.set_selection): an unvisited child is
     worth its parent's value less fpu * sqrt(visited prior mass) instead of 0, and c_puct grows with the parent's count.  Not with
     subtree_reuse, gumbel or solver.  The arena is untouched.  Whether it trains a stronger net per GPU hour is not measured.
+    candidates: dict(radius=r) for the self-play searches (Engine.set_candidates): they expand, noise and select only the empty cells
+    within Chebyshev distance r of a stone, the priors normalised over them.  Not with subtree_reuse, gumbel, solver, selection or
+    torch_eval.  The arena is untouched.  Whether it trains a stronger net per GPU hour is not measured.
     win_rule: "freestyle" (constants.WIN_RULE's default: a run of WIN_LENGTH or more wins) or "exact" (standard Gomoku: exactly
     WIN_LENGTH, overlines win nothing; Engine.set_win_rule).  It is the game itself, so self-play AND the arena play it, and it
     combines with every option.  Whether exact-rule self-play trains a stronger standard-rule net is not measured.
@@ -75,7 +78,7 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
                               seed=seed, subtree_reuse=subtree_reuse, gather_to=0 if world > 1 else None, trunk=trunk,
                               start_positions=start_positions, resign=resign, playout_cap=playout_cap,
                               forced_playouts=forced_playouts, gumbel=gumbel, solver=solver, win_rule=win_rule, threat_search=threat_search,
-                              selection=selection, evaluator=make_batch_policy_value_fn(candidate.net, device) if torch_eval else None)
+                              selection=selection, candidates=candidates, evaluator=make_batch_policy_value_fn(candidate.net, device) if torch_eval else None)
     evaluator = ModelEvaluator(game_class=Gomoku, print_games=False, device=device, seed=seed,
                                evaluators=True if torch_eval else None, win_rule=win_rule)
     promoter = ModelPromoter(model_dir, evaluator, lambda: GomokuNet(board_size=n), device, threshold=PROMOTION_THRESHOLD)
@@ -196,6 +199,9 @@ def main():
     ap.add_argument("--cpuct-factor", type=float, default=None, metavar="F",
                     help="selection rule in the self-play searches: c_puct + F x log((N + B + 1) / B) at a parent with N visits "
                          "(0 <= F <= 16; AlphaZero's rule is F = 1); unvisited children are scored as under --fpu (default R 0.2)")
+    ap.add_argument("--candidate-radius", type=int, default=None, metavar="R",
+                    help="candidate moves in the self-play searches: only the empty cells within Chebyshev distance R (1 .. n-1) of a "
+                         "stone are expanded, noised and selected, and the priors are normalised over them")
     ap.add_argument("--win-rule", choices=("freestyle", "exact"), default=None,
                     help="the game that self-play and the arena play: freestyle (default; a run of WIN_LENGTH or more wins) or "
                          "exact (standard Gomoku: exactly WIN_LENGTH, an overline wins nothing)")
@@ -226,6 +232,7 @@ def main():
     if threat_search is not None:
         a.solver = True
     selection = selection_from_flags(ap.error, a.fpu, a.fpu_root, a.cpuct_base, a.cpuct_factor)
+    candidates = None if a.candidate_radius is None else {"radius": a.candidate_radius}
     start_positions = None
     if a.start_positions:
         with np.load(a.start_positions) as z:
@@ -242,7 +249,8 @@ def main():
     run(a.episodes, a.games, a.sims, a.eval_games, a.device, model_dir=a.model_dir, device_replay=a.device_replay,
         subtree_reuse=a.subtree_reuse, trunk=a.trunk, eval_sims=C.NUM_EVAL_SIMULATIONS, start_positions=start_positions,
         resign=resign, torch_eval=a.torch_eval, playout_cap=playout_cap, forced_playouts=forced_playouts,
-        gumbel=gumbel, solver=a.solver, win_rule=a.win_rule, threat_search=threat_search, selection=selection)
+        gumbel=gumbel, solver=a.solver, win_rule=a.win_rule, threat_search=threat_search, selection=selection,
+        candidates=candidates)
     if world > 1:
         td.barrier()
         td.destroy_process_group()

@@ -678,6 +678,54 @@ int az_set_selection(az_engine *e, int on, double fpu, double fpu_root, double c
 int az_get_selection(const az_engine *e, int *on, double *fpu, double *fpu_root, double *cpuct_base, double *cpuct_factor);
 int az_selection_tables(double c_puct, double cpuct_base, double cpuct_factor, int S, double *cpuct, double *mass);
 
+/* Opt-in candidate moves: the search considers only the empty cells near the stones, and priors are normalised over them.
+ * Every node of the reference's tree has one selectable edge per empty cell, up to 225 at 15x15, and its priors are a softmax
+ * over all n^2 logits (controller.py:49), occupied cells included.  Whether this trains a stronger net per GPU hour has not
+ * been measured.
+ *
+ * Rule.  az_set_candidates(e, radius) takes radius 0 (off, the default) or 1 .. n-1.  The candidate set C(X) of a node X with
+ * position B (the stones of both colours, those placed along the descent included):
+ *   B empty: C(X) = all n^2 cells.
+ *   otherwise: C(X) = the empty cells whose Chebyshev distance to some stone of B is <= radius, max(|drow|, |dcol|) <= radius,
+ *   with no wrap across row ends.  A board that is neither empty nor full always has a candidate (the 8-neighbour grid is
+ *   connected), so radius = n-1 is "all legal cells": the legal-move-masked softmax on its own.
+ * C(X) depends on the position alone; it is not stored with the row.
+ * Expansion of X (root or leaf), x the logits in board order (after the leaf symmetry has been undone):
+ *   m   = max over c in C of x_c
+ *   e_c = expf_c (x_c - m)                     c in C; expf_c: the engine's canonical float32 exp (az_expf of csrc/az_device.h)
+ *   s   = canonical wave sum of e_c             float32: lane l adds its cells j = l (mod 64), j in C, in ascending order;
+ *                                               then v[l] = v[l] + v[l ^ msk] for msk = 32, 16, 8, 4, 2, 1
+ *   P_c = e_c / s  (c in C),   P_c = 0.0f exactly  (c not in C)
+ * i.e. the softmax of every expansion with "j < n^2" replaced by "j in C".  The value head is untouched.  The synthetic
+ * evaluator has no logits and is not normalised: candidates keep their prior, every other cell gets 0.
+ * Root noise, where the root is noised today; the tape and its offsets are unchanged.  nz_c = noise[legal_rank(c)], legal_rank
+ * the index among the empty cells as today:
+ *   t    = canonical wave sum over c in C of nz_c      float64, the same lane partials and butterfly
+ *   P'_c = (float)((double)((float)(1-w) * P_c) + w * (nz_c / t))      c in C; nothing is fused
+ * (a sub-vector of a Dirichlet(alpha) sample, renormalised, is Dirichlet(alpha) on the subset).  Non-candidates stay at 0.
+ * Selection, at every level and with or without virtual-loss batching: the argmax runs over C(X) instead of over the empty
+ * cells; the expression, the operation order and the tie-break (first maximum in cell order) do not change.  A non-candidate
+ * edge is never selected and keeps N = 0; pi gives it what it gives any legal cell with no visit.
+ * The terminal tests, backup, the move, the search value, resignation, the temperature schedule and the records' layout keep
+ * their definitions.  Forced playouts: a child with P = 0 is never forced (n^2 < (k P) total is false), and the pruning only
+ * touches children with a visit.
+ * az_candidate_mask(n, board, radius, mask) is the rule on the host (no engine needed): board uint8[n*n] 0 empty / 1 / 2,
+ * mask[j] = 1 for the cells of C; radius 0 gives the empty cells (the option off).  AZ_ERR_INVALID for n outside 3..15, radius
+ * outside 0 .. n-1, a cell value above 2 or a null pointer.
+ * Off -- never set, or set back to 0 -- the engine is the one without the option byte for byte, run by the kernels that run
+ * it without.  While the option is on every board size runs the lock-step kernels (az_get_persistent reports 0).
+ * Combines with the evaluation cache (entries hold logits: they serve both settings), leaf symmetry, virtual-loss batching,
+ * deep engines, both nets, the synthetic evaluator, start positions, resignation, the exact win rule, the playout cap, forced
+ * playouts, delta evaluation, az_search / az_search_batch and both step APIs.  Refused with AZ_ERR_INVALID, whichever is set
+ * first: subtree reuse (a retained root's priors and noise were not made under the rule for this position), the Gumbel root
+ * search (top-m and the completed-Q target are defined over the legal cells), the solver and with it the threat search
+ * ("every move loses" is no proof when moves were left out), the selection rule (its kernels do not carry this one yet), the
+ * external evaluator (it returns priors, not logits); az_search_callback refuses the option itself.
+ * AZ_ERR_INVALID for a radius outside 0 .. n-1 (the previous setting is kept); AZ_ERR_STATE while an episode is open. */
+int az_set_candidates(az_engine *e, int radius);
+int az_get_candidates(const az_engine *e, int *radius);
+int az_candidate_mask(int n, const uint8_t *board, int radius, uint8_t *mask);
+
 /* Opt-in Gumbel root search ("Policy improvement by planning with Gumbel", Danihelka et al., ICLR 2022): instead of Dirichlet
  * noise, PUCT at the root and the visit-count target, the root samples Gumbel-top-m candidates without replacement, spends a
  * fixed sequential-halving schedule on them and trains on softmax(logits + sigma(completed Q)).  Made for 16 to 64 simulations
