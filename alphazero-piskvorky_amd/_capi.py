@@ -44,6 +44,7 @@ EXPORTS = [
     "az_set_solver", "az_get_solver", "az_last_proof", "az_selfplay_proofs", "az_solver_counts", "az_solver_stops",
     "az_set_win_rule", "az_get_win_rule", "az_rules_winner",
     "az_set_threat_search", "az_get_threat_search", "az_threat_batch", "az_threat_solve", "az_selfplay_threats", "az_threat_stats",
+    "az_set_rng", "az_get_rng", "az_rng_philox4x32", "az_rng_log", "az_rng_exp", "az_rng_philox_tape", "az_rng_philox_tape_device",
     "az_set_delta_eval", "az_get_delta_eval", "az_delta_max_tiles", "az_delta_stats", "az_net_eval_delta", "az_delta_lists",
     "az_dist_unique_id", "az_dist_init", "az_dist_rank", "az_dist_world", "az_dist_counts", "az_dist_gather_records",
     "az_dist_allreduce_sum", "az_dist_broadcast",
@@ -216,6 +217,15 @@ def lib():
             L.az_delta_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 4 + [C.c_void_p]
             L.az_net_eval_delta.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
             L.az_delta_lists.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5
+        if hasattr(L, "az_set_rng"):
+            L.az_set_rng.argtypes = [C.c_void_p, C.c_int]
+            L.az_get_rng.argtypes = [C.c_void_p]
+            L.az_rng_philox4x32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+            L.az_rng_philox4x32.restype = None
+            L.az_rng_log.argtypes = L.az_rng_exp.argtypes = [C.c_double]
+            L.az_rng_log.restype = L.az_rng_exp.restype = C.c_double
+            L.az_rng_philox_tape.argtypes = [C.c_uint64, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+            L.az_rng_philox_tape_device.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -473,6 +483,53 @@ def selfplay_tape_gumbel(seed, n, max_plies=0):
     rc = lib().az_rng_selfplay_tape_gumbel(int(seed), n, int(max_plies), _p(noise), _p(u))
     if rc:
         raise AzError(f"az_rng_selfplay_tape_gumbel failed ({rc})")
+    return noise, u[:plies]
+
+
+RNG_MODES = ("numpy", "philox")                                # az_set_rng: AZ_RNG_NUMPY, AZ_RNG_PHILOX
+TAPE_KINDS = ("dirichlet", "gumbel")                           # AZ_TAPE_DIRICHLET, AZ_TAPE_GUMBEL
+
+
+def check_rng(rng):
+    """The name of an RNG mode as the seams keep it: "numpy" (None: the default) or "philox"."""
+    if rng is None:
+        return "numpy"
+    if rng not in RNG_MODES:
+        raise ValueError(f"rng must be one of {RNG_MODES}, got {rng!r}")
+    return rng
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10 of a counter of four and a key of two 32-bit words (az_rng_philox4x32; needs no GPU) -> uint32[4]."""
+    c = np.array([int(x) & 0xFFFFFFFF for x in counter], np.uint32)
+    k = np.array([int(x) & 0xFFFFFFFF for x in key], np.uint32)
+    if c.shape != (4,) or k.shape != (2,):
+        raise ValueError("philox4x32: a counter of four words and a key of two")
+    out = np.zeros(4, np.uint32)
+    lib().az_rng_philox4x32(_p(c), _p(k), _p(out))
+    return out
+
+
+def rng_log(x):
+    """The software float64 logarithm of the Philox stream (az_rng_log; needs no GPU)."""
+    return float(lib().az_rng_log(float(x)))
+
+
+def rng_exp(x):
+    """The float64 exp of the Philox stream, the engine's az_exp (az_rng_exp; needs no GPU)."""
+    return float(lib().az_rng_exp(float(x)))
+
+
+def philox_tape(seed, n, alpha=0.3, max_plies=0, kind="dirichlet"):
+    """One game's tape of the AZ_RNG_PHILOX stream made on the host (az_rng_philox_tape; needs no GPU) -> (noise, u) in
+    rng_selfplay_tape's layout.  kind "gumbel": Gumbel(0, 1) draws, the tape of the Gumbel root search."""
+    nn = n * n
+    plies = max_plies if 0 < max_plies < nn else nn
+    noise = np.zeros(sum(nn - m for m in range(plies)), np.float64)
+    u = np.zeros(nn, np.float64)
+    rc = lib().az_rng_philox_tape(int(seed) & (2 ** 64 - 1), n, float(alpha), int(max_plies), TAPE_KINDS.index(kind), _p(noise), _p(u))
+    if rc:
+        raise AzError(f"az_rng_philox_tape failed ({rc})")
     return noise, u[:plies]
 
 
@@ -1134,6 +1191,27 @@ class Engine:
         m, cv, cs = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
         self._check(lib().az_get_gumbel(self.h, C.byref(m), C.byref(cv), C.byref(cs)), "az_get_gumbel")
         return dict(m=int(m.value), c_visit=float(cv.value), c_scale=float(cs.value))
+
+    # ---- device RNG ----
+    def set_rng(self, mode):
+        """"philox": the engine fills its own tapes on the GPU from the counter-based stream of include/az_engine.h, with no host
+        tape thread; "numpy" (the default): numpy's RandomState streams made on the host, the reference's numbers (az_set_rng)."""
+        self._check(lib().az_set_rng(self.h, RNG_MODES.index(check_rng(mode))), "az_set_rng")
+
+    def rng(self):
+        """The RNG mode in force: "numpy" or "philox" (az_get_rng)."""
+        return RNG_MODES[lib().az_get_rng(self.h)]
+
+    def philox_tape_device(self, seed0, games, alpha=0.3, max_plies=0, kind="dirichlet"):
+        """The tape kernel on its own (az_rng_philox_tape_device): games seed0 + 0 .. games - 1 on the engine's board ->
+        (noise float64[games, tape length], u float64[games, plies]), each row what philox_tape gives for that seed."""
+        nn = self.nn
+        plies = max_plies if 0 < max_plies < nn else nn
+        noise = np.zeros((int(games), sum(nn - m for m in range(plies))), np.float64)
+        u = np.zeros((int(games), nn), np.float64)
+        self._check(lib().az_rng_philox_tape_device(self.h, int(seed0) & (2 ** 64 - 1), int(games), float(alpha), int(max_plies),
+                                                    TAPE_KINDS.index(kind), _p(noise), _p(u)), "az_rng_philox_tape_device")
+        return noise, u[:, :plies]
 
     def sims(self):
         """int32 simulations of every record of the last episode, in the order of records() (az_selfplay_sims)."""

@@ -197,7 +197,12 @@ struct az_engine {
     bool stream_tapes = true;      // AZ_TAPE_STREAM=0: generate every tape before the first ply
     int tape_threads = 4;          // AZ_TAPE_THREADS: host threads of the tape producer
     int host_cpus = 1;             // CPUs this process may run on (affinity mask and cgroup quota), what the thread counts are sized from
+    int rng_mode = AZ_RNG_NUMPY;   // az_set_rng: AZ_RNG_PHILOX fills the tapes with k_tape instead of the host producer
 };
+
+// az_philox.hip: k_tape over plies [m0, m1) of games seed0 + [0, G), on `stream`
+hipError_t az_tape_launch(hipStream_t stream, uint64_t seed0, int G, int nn, int m0, int m1, double alpha, int kind, const int *done,
+                          double *noise, int64_t noise_stride, double *u);
 
 static void stop_tapes(az_engine *e)
 {
@@ -1739,7 +1744,7 @@ static int read_counters(az_engine *e, az_counters &c)
         if (L.tape_wait_s > tape_wait) tape_wait = L.tape_wait_s;
     }
     c.tape_wait_seconds = tape_wait;
-    c.tape_threads = e->tapes || e->stream_tapes ? e->tape_threads : 0;
+    c.tape_threads = e->rng_mode != AZ_RNG_PHILOX && (e->tapes || e->stream_tapes) ? e->tape_threads : 0;
     c.host_cpus = e->host_cpus;
     e->run.reused_roots = reused;
     c.trunk_seconds = trunk_ms * 1e-3;
@@ -1847,6 +1852,11 @@ extern "C" int az_selfplay_begin(az_engine *e, const az_selfplay_args *a)
         HIPCHECK(e, hipMemcpy2DAsync(e->noise.p, (size_t)e->tape_len * 8, a->noise_tape, (size_t)a->tape_stride * 8,
                                      (size_t)std::min<int64_t>(a->tape_stride, e->tape_len) * 8, G, hipMemcpyHostToDevice, e->stream));
         HIPCHECK(e, hipMemcpyAsync(e->u.p, a->u_tape, (size_t)G * nn * 8, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, hipStreamSynchronize(e->stream));
+    } else if (e->rng_mode == AZ_RNG_PHILOX) {
+        // every ply of every game in one launch ahead of the first ply: no staging, no copy stream, no host thread
+        HIPCHECK(e, az_tape_launch(e->stream, a->seed0, G, nn, 0, plies, e->cfg.dirichlet_alpha, e->gumbel_m > 0 ? AZ_TAPE_GUMBEL : AZ_TAPE_DIRICHLET,
+                                   nullptr, (double *)e->noise.p, e->tape_len, (double *)e->u.p));
         HIPCHECK(e, hipStreamSynchronize(e->stream));
     } else if (e->stream_tapes) {
         e->tapes = new TapeProducer();
@@ -2325,6 +2335,46 @@ extern "C" int az_get_gumbel(const az_engine *e, int *m, double *c_visit, double
     if (c_visit) *c_visit = e->gumbel_cv;
     if (c_scale) *c_scale = e->gumbel_cs;
     return AZ_OK;
+}
+
+extern "C" int az_set_rng(az_engine *e, int mode)
+{
+    if (!e) return AZ_ERR_INVALID;
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_set_rng: an episode is open (az_selfplay_end first)");
+    if (mode != AZ_RNG_NUMPY && mode != AZ_RNG_PHILOX) return fail(e, AZ_ERR_INVALID, "az_set_rng: mode %d (AZ_RNG_NUMPY = 0, AZ_RNG_PHILOX = 1)", mode);
+    e->rng_mode = mode;
+    return AZ_OK;
+}
+
+extern "C" int az_get_rng(const az_engine *e) { return e ? e->rng_mode : AZ_ERR_INVALID; }
+
+// k_tape on its own: buffers of the call's own, the engine's stream, the result copied back
+extern "C" int az_rng_philox_tape_device(az_engine *e, uint64_t seed0, int games, double alpha, int max_plies, int kind, double *noise_out,
+                                         double *u_out)
+{
+    if (!e || games < 0) return fail(e, AZ_ERR_INVALID, "az_rng_philox_tape_device: bad argument");
+    if (kind != AZ_TAPE_DIRICHLET && kind != AZ_TAPE_GUMBEL) return fail(e, AZ_ERR_INVALID, "az_rng_philox_tape_device: kind %d (0 = Dirichlet, 1 = Gumbel)", kind);
+    if (noise_out && kind == AZ_TAPE_DIRICHLET && !(alpha > 0.0 && std::isfinite(alpha)))
+        return fail(e, AZ_ERR_INVALID, "az_rng_philox_tape_device: alpha %g (> 0)", alpha);
+    if (games == 0) return AZ_OK;
+    if (!u_out) return fail(e, AZ_ERR_INVALID, "az_rng_philox_tape_device: null argument");
+    if (e->run.open) return fail(e, AZ_ERR_STATE, "az_rng_philox_tape_device: a self-play episode is open on this engine");
+    DEVICE_GUARD(e);
+    const int nn = e->nn, plies = max_plies > 0 && max_plies < nn ? max_plies : nn;
+    int64_t len = 0;
+    for (int m = 0; m < plies; m++) len += nn - m;
+    DevBuf dn, du;
+    int rc = dev_alloc(e, du, (size_t)games * nn * sizeof(double), true);
+    if (!rc && noise_out) rc = dev_alloc(e, dn, (size_t)games * len * sizeof(double), false);
+    if (!rc) {
+        hipError_t h = az_tape_launch(e->stream, seed0, games, nn, 0, plies, noise_out ? alpha : 1.0, kind, nullptr, (double *)dn.p, len, (double *)du.p);
+        if (h == hipSuccess) h = hipStreamSynchronize(e->stream);
+        if (h == hipSuccess && noise_out) h = az_memcpy(e->stream, noise_out, dn.p, (size_t)games * len * sizeof(double), hipMemcpyDeviceToHost);
+        if (h == hipSuccess) h = az_memcpy(e->stream, u_out, du.p, (size_t)games * nn * sizeof(double), hipMemcpyDeviceToHost);
+        if (h != hipSuccess) rc = fail(e, AZ_ERR_HIP, "az_rng_philox_tape_device: %s", hipGetErrorString(h));
+    }
+    dev_free(dn); dev_free(du);
+    return rc;
 }
 
 // v_mix of one root row, as az_gumbel_target and k_move form it (NaN for a bad argument): the piece of the target whose
@@ -3186,10 +3236,16 @@ extern "C" int az_arena(az_engine *e, const az_arena_args *a, az_arena_result *o
     int rc = ensure_episode_buffers(e, G, false);
     if (rc) return rc;
     if ((rc = upload_T(e, a->temperature_table, true))) return rc;
-    std::vector<double> hu((size_t)G * nn);
-    if (a->u_tape) memcpy(hu.data(), a->u_tape, hu.size() * 8);
-    else for (int g = 0; g < G; g++) azrng::uniforms(a->seed0 + (uint64_t)g, nn, hu.data() + (size_t)g * nn);
-    HIPCHECK(e, az_memcpy(e->stream, e->u.p, hu.data(), hu.size() * 8, hipMemcpyHostToDevice));
+    if (!a->u_tape && e->rng_mode == AZ_RNG_PHILOX) {
+        // the move uniforms of the same stream as self-play's, and no noise
+        HIPCHECK(e, az_tape_launch(e->stream, a->seed0, G, nn, 0, nn, 1.0, AZ_TAPE_DIRICHLET, nullptr, nullptr, 0, (double *)e->u.p));
+        HIPCHECK(e, hipStreamSynchronize(e->stream));
+    } else {
+        std::vector<double> hu((size_t)G * nn);
+        if (a->u_tape) memcpy(hu.data(), a->u_tape, hu.size() * 8);
+        else for (int g = 0; g < G; g++) azrng::uniforms(a->seed0 + (uint64_t)g, nn, hu.data() + (size_t)g * nn);
+        HIPCHECK(e, az_memcpy(e->stream, e->u.p, hu.data(), hu.size() * 8, hipMemcpyHostToDevice));
+    }
     EpisodeSpec sp;
     sp.num_games = G; sp.max_plies = 0; sp.add_noise = false; sp.arena = true;
     sp.game_key0 = (unsigned)a->seed0;

@@ -7,7 +7,7 @@ import torch
 
 from . import constants as _c
 from . import parallel
-from ._capi import AZ_MAX_SIMULATIONS, Engine, check_candidates, check_selection, check_threat_search, win_rule_name
+from ._capi import AZ_MAX_SIMULATIONS, Engine, check_candidates, check_rng, check_selection, check_threat_search, win_rule_name
 from .controller import device_index, make_batch_policy_value_fn, merge_batch_evaluators, model_kind
 from .mcts import check_solver, numpy_log_table
 from .options import apply_options, bring_candidates, bring_selection, check_combination, switched_on
@@ -21,8 +21,10 @@ def temperature_schedule(move: int) -> float:
 class ModelEvaluator:
     def __init__(self, game_class=None, print_games=False, device=None, seed=None, virtual_loss=1, eval_cache=0,
                  start_positions=None, resign: dict = None, evaluators=None, solver: bool = False, win_rule: str = None,
-                 threat_search: dict = None, selection: dict = None, candidates: dict = None):
+                 threat_search: dict = None, selection: dict = None, candidates: dict = None, rng: str = None):
         self.game_class = game_class
+        # where the arena's move uniforms come from: "numpy" (the default) or "philox", made on the GPU (az_set_rng)
+        self.rng = check_rng(rng)
         # which game the arena plays: "freestyle" (constants.WIN_RULE's default) or "exact" (standard Gomoku; az_set_win_rule)
         self.win_rule = win_rule_name(_c.WIN_RULE if win_rule is None else win_rule)
         # opt-in: the arena's evaluations leave the engine (az_set_external_evaluator).  A (candidate, baseline) pair of
@@ -98,12 +100,14 @@ class ModelEvaluator:
         self.candidates = check_candidates(self.candidates)
         check_combination(switched_on(candidates=self.candidates, solver=self.solver, selection=self.selection,
                                       evaluator=self.evaluators), "candidates")
+        self.rng = check_rng(self.rng)
         # first=lo is even (parallel.arena_block): no pair of games from one start position is torn apart.  The arena has no
         # playout cap, forced playouts or Gumbel root search: its roots are not noised.
         bring_candidates(eng, self.candidates, before=True)
         bring_selection(eng, self.selection, before=True)
         apply_options(eng, win_rule=self.win_rule, start_positions=self.start_positions, first=lo, resign=self.resign,
-                      playout_cap=None, forced_playouts=None, gumbel=None, solver=self.solver, threat_search=self.threat_search)
+                      playout_cap=None, forced_playouts=None, gumbel=None, solver=self.solver, threat_search=self.threat_search,
+                      rng=self.rng)
         bring_selection(eng, self.selection, before=False)
         bring_candidates(eng, self.candidates, before=False)
         r = eng.arena(mine, seed0=seed0 + lo, temperature_table=T) if mine > 0 else {"wins": 0, "losses": 0, "draws": 0, "total": 0, "win_rate": 0.0}

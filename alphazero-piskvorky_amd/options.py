@@ -65,10 +65,13 @@ def check_combination(on, of=None):
             raise ValueError(message)
 
 
-def apply_options(eng, *, win_rule, start_positions, first, resign, playout_cap, forced_playouts, gumbel, solver, threat_search):
+def apply_options(eng, *, win_rule, start_positions, first, resign, playout_cap, forced_playouts, gumbel, solver, threat_search, rng=None):
     """Brings a new or cached engine to exactly these options (checked values as the seams keep them; None / False = off):
     each is set, or cleared if the engine still has it on.  Everything that goes off goes first, so that no option meets
-    the left-overs of the last configuration in the engine's conflict table."""
+    the left-overs of the last configuration in the engine's conflict table.  rng: "numpy" | "philox", the source of the engine's
+    own tapes (az_set_rng; it meets no row of the table); None leaves the engine's mode alone."""
+    if rng is not None and eng.rng() != rng:
+        eng.set_rng(rng)
     if eng.win_rule() != win_rule:
         if eng.start_positions():
             eng.clear_start_positions()                   # they were validated under the other rule

@@ -7,7 +7,7 @@ import torch
 
 from . import constants as _c
 from . import parallel
-from ._capi import check_candidates, check_selection, check_threat_search, AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine, playout_cap_permille, resign_permille, win_rule_name
+from ._capi import check_candidates, check_rng, check_selection, check_threat_search, AZ_AUG_REFERENCE4, AZ_MAX_SIMULATIONS, REUSE_MAX_SIMULATIONS, Engine, playout_cap_permille, resign_permille, win_rule_name
 from .controller import BatchPolicyValueFn, device_index, model_kind
 from .mcts import check_forced_playouts, check_gumbel, check_solver, numpy_log_table
 from .options import apply_options, bring_candidates, bring_selection, check_combination, switched_on
@@ -116,8 +116,13 @@ class SelfPlayManager:
                  eval_cache: int = 0, virtual_loss: int = 1, trunk: str = "f32", leaf_symmetry: bool = False,
                  start_positions=None, resign: dict = None, evaluator: BatchPolicyValueFn = None,
                  playout_cap: dict = None, forced_playouts: dict = None, gumbel: dict = None, solver: bool = False,
-                 win_rule: str = None, threat_search: dict = None, selection: dict = None, candidates: dict = None):
+                 win_rule: str = None, threat_search: dict = None, selection: dict = None, candidates: dict = None,
+                 rng: str = None):
         self.controller = controller
+        # where the engine's random numbers come from: "numpy" (the default; RandomState(seed + game) streams made on host cores,
+        # the reference's numbers) or "philox" (a counter-based stream made on the GPU with no host thread: throughput runs;
+        # az_set_rng).  Combines with every option.
+        self.rng = rng
         # which game is played: "freestyle" (constants.WIN_RULE's default, the reference's: a run of WIN_LENGTH or more wins) or
         # "exact" (standard Gomoku: exactly WIN_LENGTH, an overline wins nothing; az_set_win_rule).  Combines with every option.
         # Whether exact-rule self-play trains a stronger standard-rule net has not been measured.
@@ -197,6 +202,7 @@ class SelfPlayManager:
         self.threat_search = check_threat_search(self.threat_search)
         self.selection = check_selection(self.selection)
         self.candidates = check_candidates(self.candidates)
+        self.rng = check_rng(self.rng)
         check_combination(switched_on(subtree_reuse=self.subtree_reuse, virtual_loss=self.virtual_loss, leaf_symmetry=self.leaf_symmetry,
                                       evaluator=self.evaluator, playout_cap=self.playout_cap, forced_playouts=self.forced_playouts,
                                       gumbel=self.gumbel, solver=self.solver, threat_search=self.threat_search, selection=self.selection,
@@ -283,7 +289,7 @@ class SelfPlayManager:
         T = np.array([float(self.temperature_schedule(m)) for m in range(n * n + 1)], dtype=np.float64)
         apply_options(eng, win_rule=self.win_rule, start_positions=self.start_positions, first=lo, resign=self.resign,
                       playout_cap=self.playout_cap, forced_playouts=self.forced_playouts, gumbel=self.gumbel, solver=self.solver,
-                      threat_search=self.threat_search)
+                      threat_search=self.threat_search, rng=self.rng)
         bring_selection(eng, self.selection, before=False)
         bring_candidates(eng, self.candidates, before=False)
         self.last_resign_stats = self.last_playout_cap_stats = None

@@ -29,7 +29,8 @@ PROMOTION_THRESHOLD = 0.55          # promoter.py:19, strict ">" with draws coun
 
 def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=None, log=print, device_replay=False,
         subtree_reuse=False, trunk="f32", eval_sims=None, start_positions=None, resign=None, torch_eval=False,
-        playout_cap=None, forced_playouts=None, gumbel=None, solver=False, win_rule=None, threat_search=None, selection=None, candidates=None):
+        playout_cap=None, forced_playouts=None, gumbel=None, solver=False, win_rule=None, threat_search=None, selection=None, candidates=None,
+        rng=None):
     """eval_sims: simulations per move in the arena (evaluator.py:53-62 takes NUM_EVAL_SIMULATIONS = 200 whatever the
     self-play count is; main() passes that constant); None = as many as self-play, which keeps small test runs short.
     device_replay=True keeps the examples on the GPU from the episode-end gather to the optimizer step (packed records
@@ -63,6 +64,9 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
     win_rule: "freestyle" (constants.WIN_RULE's default: a run of WIN_LENGTH or more wins) or "exact" (standard Gomoku: exactly
     WIN_LENGTH, overlines win nothing; Engine.set_win_rule).  It is the game itself, so self-play AND the arena play it, and it
     combines with every option.  Whether exact-rule self-play trains a stronger standard-rule net is not measured.
+    rng: "numpy" (the default: RandomState streams made on host cores, the reference's numbers) or "philox": self-play's root
+    noise and move draws and the arena's move draws come from a counter-based stream made on the GPU (Engine.set_rng), with no
+    host tape thread.  Combines with every option.
     torch_eval=True: the searches of self-play and the arena are evaluated by the controllers' own torch modules on the GPU
     (controller.make_batch_policy_value_fn, az_set_external_evaluator) instead of the engine's net kernels -- the loop a
     changed net.py runs on before it has kernels of its own."""
@@ -78,9 +82,9 @@ def run(episodes, games, sims, eval_games, device="cuda:0", seed=0, model_dir=No
                               seed=seed, subtree_reuse=subtree_reuse, gather_to=0 if world > 1 else None, trunk=trunk,
                               start_positions=start_positions, resign=resign, playout_cap=playout_cap,
                               forced_playouts=forced_playouts, gumbel=gumbel, solver=solver, win_rule=win_rule, threat_search=threat_search,
-                              selection=selection, candidates=candidates, evaluator=make_batch_policy_value_fn(candidate.net, device) if torch_eval else None)
+                              selection=selection, candidates=candidates, rng=rng, evaluator=make_batch_policy_value_fn(candidate.net, device) if torch_eval else None)
     evaluator = ModelEvaluator(game_class=Gomoku, print_games=False, device=device, seed=seed,
-                               evaluators=True if torch_eval else None, win_rule=win_rule)
+                               evaluators=True if torch_eval else None, win_rule=win_rule, rng=rng)
     promoter = ModelPromoter(model_dir, evaluator, lambda: GomokuNet(board_size=n), device, threshold=PROMOTION_THRESHOLD)
     buffer = ReplayBuffer(capacity=C.BUFFER_CAPACITY)
     ring = None
@@ -205,6 +209,9 @@ def main():
     ap.add_argument("--win-rule", choices=("freestyle", "exact"), default=None,
                     help="the game that self-play and the arena play: freestyle (default; a run of WIN_LENGTH or more wins) or "
                          "exact (standard Gomoku: exactly WIN_LENGTH, an overline wins nothing)")
+    ap.add_argument("--rng", choices=("numpy", "philox"), default=None,
+                    help="where the engine's random numbers come from: numpy (default; RandomState streams made on host cores, the "
+                         "reference's numbers) or philox (a counter-based stream made on the GPU, no host tape threads)")
     ap.add_argument("--torch-eval", action="store_true",
                     help="evaluate the searches with the controller's own torch module as a batched external evaluator "
                          "(any net; no HIP trunk needed) instead of the engine's net kernels")
@@ -250,7 +257,7 @@ def main():
         subtree_reuse=a.subtree_reuse, trunk=a.trunk, eval_sims=C.NUM_EVAL_SIMULATIONS, start_positions=start_positions,
         resign=resign, torch_eval=a.torch_eval, playout_cap=playout_cap, forced_playouts=forced_playouts,
         gumbel=gumbel, solver=a.solver, win_rule=a.win_rule, threat_search=threat_search, selection=selection,
-        candidates=candidates)
+        candidates=candidates, rng=a.rng)
     if world > 1:
         td.barrier()
         td.destroy_process_group()

@@ -381,6 +381,63 @@ int az_rng_uniforms(uint64_t seed, int count, double *u);
  * then one uniform, in az_rng_selfplay_tape's layout */
 int az_rng_selfplay_tape_gumbel(uint64_t seed, int board_size, int max_plies, double *noise, double *u);
 
+/* ---- device RNG: counter-based Philox tapes made on the GPU (opt-in; throughput runs) ----
+ * az_set_rng(e, AZ_RNG_PHILOX) replaces the host tape producer above: az_selfplay_begin fills noise[G][tape_len] and
+ * u[G][n*n] with one launch of k_tape before the first ply, az_arena its u alone; no pinned staging is allocated, no host
+ * tape thread runs (az_counters.tape_threads and tape_wait_seconds read 0).  AZ_RNG_NUMPY (0), the default, is the numpy
+ * stream of az_rng_selfplay_tape, and with it the engine equals the reference.  An explicit noise_tape / u_tape is taken
+ * as given in either mode; az_search* with a caller's noise are untouched; every consumer kernel reads the same buffers in
+ * the same layout, so the mode combines with every option.  az_set_rng returns AZ_ERR_STATE while an episode is open and
+ * AZ_ERR_INVALID for another mode; az_get_rng returns the mode.
+ *
+ * The stream.  Every draw is a pure function of (game seed, ply m, legal rank j, attempt t, purpose): nothing depends on
+ * max_plies, on the order of generation or on which other games are generated.
+ *   Generator.  Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11): ten rounds of
+ *       (c0, c1, c2, c3) <- (hi(M1 * c2) ^ c1 ^ k0,  lo(M1 * c2),  hi(M0 * c0) ^ c3 ^ k1,  lo(M0 * c0)),
+ *   M0 = 0xD2511F53, M1 = 0xCD9E8D57, hi / lo the halves of the 64-bit product; after each round k0 += 0x9E3779B9,
+ *   k1 += 0xBB67AE85 (mod 2^32).  az_rng_philox4x32 is this function.
+ *   Key.  seed = seed0 + g (mod 2^64), the per-game seed of the numpy tapes: key = (seed & 0xffffffff, seed >> 32).
+ *   Counter.  (c0, c1, c2, c3) = (attempt t, rank j, ply m, purpose).
+ *   Words to doubles.  One call's words (w0, w1, w2, w3) give Ua = ((w0 >> 5) * 2^26 + (w1 >> 6)) / 2^53 and
+ *   Ub = ((w2 >> 5) * 2^26 + (w3 >> 6)) / 2^53, both in [0, 1) and exact.
+ *   Purposes.  0 move uniform: u[m] = Ua of (t 0, j 0, m, 0).  1 normal pair: (Ua, Ub) of (t, j, m, 1).  2 acceptance
+ *   uniform: Ua of (t, j, m, 2).  3 boost uniform: Ua of (0, j, m, 3).  4 Gumbel: Ua of (0, j, m, 4).
+ *   log and exp.  log is az_rng_log, a software float64 logarithm (argument reduction to [sqrt(1/2), sqrt(2)) and one fma
+ *   polynomial; log(0) = -inf), exp is az_rng_exp, the float64 exp the engine's softmax uses, which gives 0 below -708.  Everything else is a separately
+ *   rounded float64 + - * / sqrt in the order written here, left to right.
+ *   Gamma(alpha) of (m, j).  Marsaglia and Tsang with shape a = alpha if alpha >= 1, else alpha + 1: d = a - 1/3,
+ *   c = 1 / sqrt(9 * d).  Attempt t = 0, 1, ..: x1 = 2 * Ua - 1, x2 = 2 * Ub - 1 of the normal pair, r2 = x1 * x1 + x2 * x2;
+ *   the attempt fails if r2 >= 1 or r2 == 0; x = x1 * sqrt(-2 * log(r2) / r2) (the polar method; its second normal is not
+ *   used); v = 1 + c * x; the attempt fails if v <= 0; v = v * v * v; U the attempt's acceptance uniform, xx = x * x; the
+ *   attempt succeeds if U < 1 - 0.0331 * xx * xx, or else if log(U) < 0.5 * xx + d * (1 - v + log(v)); the draw is d * v.
+ *   After AZ_RNG_PHILOX_ATTEMPTS (64) failed attempts the draw is d (v = 1, the value at x = 0; probability below 1e-38
+ *   per draw), so no input keeps a lane in the loop.  For alpha < 1 the draw is then multiplied by exp(log(U) / alpha), U the
+ *   boost uniform.
+ *   Dirichlet.  Ply m holds k = n*n - m entries, entry j = gamma_j / sum, or 1 / k each if sum == 0.  The sum has one order:
+ *   64 partial sums p[l] = 0 + gamma_l + gamma_(l+64) + ... by rising rank, then p[l] = p[l] + p[l + h] for every l < h, for
+ *   h = 32, 16, 8, 4, 2, 1; sum = p[0].
+ *   Gumbel kind (AZ_TAPE_GUMBEL; the engine's choice under az_set_gumbel).  Entry j = -log(-log(1 - U)).
+ *   Layout.  az_rng_selfplay_tape's: per game, ply m holds its k doubles at offset sum_{i<m} (n*n - i); u[m] is the move
+ *   uniform of ply m.
+ *
+ * az_rng_philox_tape (host, needs no GPU) writes one game's tape with that sampler compiled for the host: plies
+ * 0 .. max_plies - 1 (all n*n for max_plies <= 0 or >= n*n); noise may be NULL (the uniforms alone).  AZ_ERR_INVALID for a
+ * board size outside 1..15, a kind other than the two, a null u, or an alpha that is not positive and finite.
+ * az_rng_philox_tape_device runs the kernel on its own for games seed0 + 0 .. games - 1 on the engine's board size and copies
+ * the result back: noise_out[games][sum_{m<plies} (n*n - m)] (may be NULL), u_out[games][n*n] (entries from max_plies on
+ * are 0).  AZ_ERR_STATE while an episode is open. */
+enum { AZ_RNG_NUMPY = 0, AZ_RNG_PHILOX = 1 };
+enum { AZ_TAPE_DIRICHLET = 0, AZ_TAPE_GUMBEL = 1 };
+#define AZ_RNG_PHILOX_ATTEMPTS 64
+int az_set_rng(az_engine *e, int mode);
+int az_get_rng(const az_engine *e);
+void az_rng_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+double az_rng_log(double x);
+double az_rng_exp(double x);
+int az_rng_philox_tape(uint64_t seed, int board_size, double alpha, int max_plies, int kind, double *noise, double *u);
+int az_rng_philox_tape_device(az_engine *e, uint64_t seed0, int games, double alpha, int max_plies, int kind, double *noise_out,
+                              double *u_out);
+
 /* Opt-in search upgrade the reference lists as a TODO (mcts.py:17-22 "subtree reuse", mcts.py:106 builds a new root
  * every run): after a self-play move the chosen child's subtree becomes the next ply's tree.  The retained root keeps
  * its priors and visit statistics, receives the ply's fresh Dirichlet sample with the arithmetic of a new root
