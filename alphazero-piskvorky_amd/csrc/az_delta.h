@@ -13,8 +13,10 @@
 //                  three lists of 16-cell tiles; the windows of the base images those tiles read are copied into LDS, the
 //                  layers run on the listed tiles only (conv_layer's subset mode, no border-tap skipping), and the feature
 //                  row is the base row with the conv3-region cells replaced.  A board with too many changed cells or conv3
-//                  tiles is left to
-//   k_trunk_rest   k_trunk's code (trunk_group) for the boards k_trunk_delta did not do.
+//                  tiles is evaluated in full by the same workgroup with the same code: its lists are the whole board
+//                  (delta_lists_full: 15 tiles per layer), its images start as zeros and nothing is read from the base.
+//                  One trunk launch per batch (5h): the separate launch of trunk_group for those boards cost every batch a
+//                  whole-CU slot per board only to read a flag.
 // Which tile and lane computes an element does not enter (az_net.h, BorderSkip): results are bit-identical to k_trunk's.
 #pragma once
 #include "az_net.h"
@@ -91,8 +93,39 @@ __host__ __device__ inline void delta_lists_serial(const unsigned char *changed,
     for (int l = 0; l < 3; l++)
         for (int i = 0; i < 16; i++) L.junk(l, i);
 }
+// The lists of a board evaluated in full (more changed cells than DELTA_MAX_CHANGED, or more conv3 tiles than the threshold):
+// every layer computes all N x N cells in ascending position -- a cell's place in lists 0 - 2 is its cell index --, and no
+// window is read: the images start as zeros, ring included, and every cell the layers read has been computed.
+template <int N>
+__host__ __device__ inline void delta_full_put(DeltaLists<N> &L, int pr, int pc)        // one padded position's part
+{
+    if (pr < 1 || pr > N || pc < 1 || pc > N) return;
+    for (int l = 0; l < 3; l++) L.put(l, (pr - 1) * N + (pc - 1), pr, pc);
+}
+template <int N>
+__host__ __device__ inline void delta_full_cnt(DeltaLists<N> &L, int l) { L.cnt[l] = l < 3 ? N * N : 0; }
+template <int N>
+__host__ __device__ inline void delta_lists_full(DeltaLists<N> &L)
+{
+    typedef DeltaGeo<N> G;
+    for (int p = 0; p < G::PP; p++) delta_full_put<N>(L, p / G::PW, p % G::PW);
+    for (int l = 0; l < 5; l++) delta_full_cnt<N>(L, l);
+    for (int l = 0; l < 3; l++)
+        for (int i = 0; i < 16; i++) L.junk(l, i);
+}
 
 #ifdef __HIPCC__
+// diagnostic builds only (-DAZ_STAMPS): k_trunk_delta's phase stamps (s_memtime), 16 u64 per workgroup in k_trunk's rows of the
+// debug buffer.  0 entry, 1 lists done, 2 windows in LDS, 3 conv1, 4 conv2, 5 + 2 i / 6 + 2 i conv3 chunk i / its heads pass
+// (zero where the leaf has no such chunk), 13 the conv3 tile count, 14 / 15 s_memrealtime at entry / at the last heads pass
+#ifdef AZ_STAMPS
+#define AZ_DSTAMP(k) do { if (threadIdx.x == 0 && dbg) dbg[(size_t)blockIdx.x * 16 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
+#define AZ_DSTAMP_VAL(k, v) do { if (threadIdx.x == 0 && dbg) dbg[(size_t)blockIdx.x * 16 + (k)] = (unsigned long long)(v); } while (0)
+#else
+#define AZ_DSTAMP(k) do { } while (0)
+#define AZ_DSTAMP_VAL(k, v) do { } while (0)
+#endif
+
 // policy_conv / value_conv of one chunk of conv3 tiles (trunk_heads' arithmetic: one k-ordered chain on v_mfma_f32_4x4x1): wave w
 // takes chunk cells 32 w .. 32 w + 31 of the cell-major image out3; frow = the board's feature row
 template <class G>
@@ -129,6 +162,13 @@ __device__ __forceinline__ void delta_heads(const NetWeights &w, float *__restri
             }
         }
     }
+}
+
+// f(0), f(1), ... f(E - 1) with the round as a compile-time value: the fragment arrays below are indexed by constants only
+template <int K, int E, class F>
+__device__ __forceinline__ void delta_rounds(F &&f)
+{
+    if constexpr (K < E) { f(std::integral_constant<int, K>{}); delta_rounds<K + 1, E>(f); }
 }
 
 // Base evaluation: blockIdx.x = slot, blockIdx.y = parity.  trunk_group's phases on the root's stones; the two packed images
@@ -198,11 +238,11 @@ __global__ __launch_bounds__(NetGeo<N>::NW * 64) void k_trunk_base(DevState d, N
     if (tid == 0 && par == 0) cnt[(size_t)b * DELTA_CNT + 3] += 2ull;
 }
 
-// done[b]: 0 = left to k_trunk_rest, 1 + conv3 tiles = evaluated here (or nothing to evaluate)
+// done[b]: 0 = evaluated in full, 1 + conv3 tiles = evaluated as a delta (or nothing to evaluate)
 template <int N>
 __global__ __launch_bounds__(NetGeo<N>::NW * 64) void k_trunk_delta(DevState d, NetWeights w, int net_id, float *__restrict__ feat,
                                                                      const float *__restrict__ base, unsigned char *done,
-                                                                     unsigned long long *cnt, int max_tiles)
+                                                                     unsigned long long *cnt, int max_tiles, unsigned long long *dbg)
 {
     typedef DeltaGeo<N> G;
     constexpr int NT = G::NW * 64;
@@ -214,13 +254,17 @@ __global__ __launch_bounds__(NetGeo<N>::NW * 64) void k_trunk_delta(DevState d, 
     __shared__ __attribute__((aligned(16))) float hdq_lds[1024];
     __shared__ DeltaLists<N> L;
     __shared__ unsigned char changed[DELTA_MAX_CHANGED];
-    __shared__ unsigned char s_dist[G::PP];
     __shared__ int s_nch;
     __shared__ int s_wc[5][5];                                          // [wave][list] members among the wave's 64 positions
     const int b = blockIdx.x;
     if (b >= d.B) return;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    AZ_DSTAMP(0);
+    AZ_DSTAMP_VAL(14, __builtin_amdgcn_s_memrealtime());
+#ifdef AZ_STAMPS
+    for (int k = 1; k < 14; k++) AZ_DSTAMP_VAL(k, 0);
+#endif
     {
         const int kind = d.leaf_kind[b];
         if (!((kind == LEAF_ROOT || kind == LEAF_EXPAND) && d.s_status[b] == SLOT_ACTIVE && d.s_net[b] == net_id)) {
@@ -260,84 +304,126 @@ __global__ __launch_bounds__(NetGeo<N>::NW * 64) void k_trunk_delta(DevState d, 
     }
     __syncthreads();
     const int nch = s_nch;
-    if (nch > DELTA_MAX_CHANGED) {
-        if (tid == 0) { done[b] = 0; cnt[(size_t)b * DELTA_CNT + 1] += 1ull; }
-        return;
-    }
-    // the five lists, one thread per padded position: a member's place is the number of members in front of it
-    int dist = 255, pr = 0, pc = 0;
-    u64 bal[5] = {0, 0, 0, 0, 0};
-    if (wave < 5) {
-        const bool in_img = tid < G::PP;
-        if (in_img) {
-            pr = tid / G::PW; pc = tid - pr * G::PW;
-            dist = delta_dist(N, pr, pc, changed, nch);
-            s_dist[tid] = (unsigned char)dist;
-        }
+    // full: the board is evaluated in full by this workgroup (delta_lists_full), uniform over the workgroup
+    bool full = nch > DELTA_MAX_CHANGED;
+    const int pr = tid / G::PW, pc = tid - pr * G::PW;
+    int dist = 255;
+    if (!full) {
+        // the five lists, one thread per padded position: a member's place is the number of members in front of it
+        u64 bal[5] = {0, 0, 0, 0, 0};
+        if (wave < 5) {
+            const bool in_img = tid < G::PP;
+            if (in_img) dist = delta_dist(N, pr, pc, changed, nch);
 #pragma unroll
-        for (int l = 0; l < 5; l++) {
-            bal[l] = __ballot(in_img && delta_member(N, l, pr, pc, dist));
-            if (lane == 0) s_wc[wave][l] = __popcll(bal[l]);
+            for (int l = 0; l < 5; l++) {
+                bal[l] = __ballot(in_img && delta_member(N, l, pr, pc, dist));
+                if (lane == 0) s_wc[wave][l] = __popcll(bal[l]);
+            }
         }
-    }
-    __syncthreads();
-    if (wave < 5 && tid < G::PP) {
+        __syncthreads();
+        if (wave < 5 && tid < G::PP) {
 #pragma unroll
-        for (int l = 0; l < 5; l++) {
-            if (!((bal[l] >> lane) & 1ull)) continue;
-            int at = __popcll(bal[l] & ((1ull << lane) - 1ull));
-            for (int v = 0; v < wave; v++) at += s_wc[v][l];
-            L.put(l, at, pr, pc);
+            for (int l = 0; l < 5; l++) {
+                if (!((bal[l] >> lane) & 1ull)) continue;
+                int at = __popcll(bal[l] & ((1ull << lane) - 1ull));
+                for (int v = 0; v < wave; v++) at += s_wc[v][l];
+                L.put(l, at, pr, pc);
+            }
         }
-    }
-    if (tid < 5) L.cnt[tid] = s_wc[0][tid] + s_wc[1][tid] + s_wc[2][tid] + s_wc[3][tid] + s_wc[4][tid];
-    __syncthreads();
-    const int t1 = L.tiles(0), t2 = L.tiles(1), t3 = L.tiles(2);
-    if (t3 > max_tiles) {
-        if (tid == 0) { done[b] = 0; cnt[(size_t)b * DELTA_CNT + 1] += 1ull; }
-        return;
-    }
-    if (tid < 48) L.junk(tid >> 4, tid & 15);
-    if (tid == 0) {
-        done[b] = (unsigned char)(1 + t3);
-        cnt[(size_t)b * DELTA_CNT + 0] += 1ull;
-        cnt[(size_t)b * DELTA_CNT + 2] += (unsigned long long)t3;
-        cnt[(size_t)b * DELTA_CNT + 4 + t3] += 1ull;
+        if (tid < 5) L.cnt[tid] = s_wc[0][tid] + s_wc[1][tid] + s_wc[2][tid] + s_wc[3][tid] + s_wc[4][tid];
+        __syncthreads();
+        full = L.tiles(2) > max_tiles;
+        if (full) __syncthreads();          // every thread has read the count before the lists are written again
     }
     float *inA = lds, *inB = lds + 32 * G::CS;
-    const float *brow = base + ((size_t)b * 2 + par) * G::STRIDE;
-    {
-        // the windows of the base images: 8 float4 planes of conv1's output at list 3, 16 of conv2's at list 4
-        const float4 *g4 = reinterpret_cast<const float4 *>(brow);
-        float4 *l4 = reinterpret_cast<float4 *>(lds);
-        const int n3 = L.cnt[3], n4 = L.cnt[4];
-        for (int i = tid; i < 8 * n3; i += NT) {
-            const int pl = i / n3, at = pl * G::CS + L.halo[0][i - pl * n3];
-            l4[at] = g4[at];
-        }
-        for (int i = tid; i < 16 * n4; i += NT) {
-            const int pl = i / n4, at = (8 + pl) * G::CS + L.halo[1][i - pl * n4];
-            l4[at] = g4[at];
-        }
-        // the feature row: the base's, without the cells the heads below write
-        const float *bf = brow + G::IMG;
-        float *frow = feat + (size_t)b * G::FROW;
-        for (int i = tid; i < 6 * G::nn; i += NT) {
-            const int p = i % G::nn, r = p / N, c = p - r * N;
-            if (s_dist[(r + 1) * G::PW + (c + 1)] > 3) frow[i] = bf[i];
+    if (full) {
+        // too many changed cells or conv3 tiles: all 225 cells at every layer, 15 tiles through the same chunk loops below
+        if (tid < G::PP) delta_full_put<N>(L, pr, pc);
+        if (tid < 5) delta_full_cnt<N>(L, tid);
+        // no window is read: conv1 and conv2 write every board cell of their images, the ring has to be zero
+        float4 *z = reinterpret_cast<float4 *>(lds);
+        for (int i = tid; i < G::IMG / 4; i += NT) z[i] = float4{0.f, 0.f, 0.f, 0.f};
+        __syncthreads();
+    }
+    const int t1 = L.tiles(0), t2 = L.tiles(1), t3 = L.tiles(2);
+    AZ_DSTAMP(1);
+    AZ_DSTAMP_VAL(13, t3);
+    if (tid < 48) L.junk(tid >> 4, tid & 15);
+    if (tid == 0) {
+        if (full) { done[b] = 0; cnt[(size_t)b * DELTA_CNT + 1] += 1ull; }
+        else {
+            done[b] = (unsigned char)(1 + t3);
+            cnt[(size_t)b * DELTA_CNT + 0] += 1ull;
+            cnt[(size_t)b * DELTA_CNT + 2] += (unsigned long long)t3;
+            cnt[(size_t)b * DELTA_CNT + 4 + t3] += 1ull;
         }
     }
+    // The windows of the base images and the base feature row: every global load is issued before the first store.  Plane =
+    // wave, list positions over the lanes, so no index is divided: the 8 float4 planes of conv1's image at list 3, planes w and
+    // 8 + w of conv2's 16 at list 4, in WR rounds of 64 positions (a list holds at most PP positions: WR + 2 WR fragments per
+    // thread bound what stays in registers, nothing is left over).  conv1's windows are stored in front of conv1.  conv2's
+    // stay in registers through conv1, which reads neither image, and are stored in front of conv2: BEFORE conv2's epilogue
+    // writes its cells of the same image, so no position has to be skipped.  The feature row: the thread of an in-board
+    // position further than 3 from every changed cell copies the cell's 6 values (the heads write the others), each once.
+    constexpr int WR = (G::PP + 63) / 64;
+    static_assert(WR * 64 >= G::PP && G::NW == 8, "the rounds reach the longest list; one conv1 plane and two conv2 planes per wave");
+    f32x4 w1[WR], w2[2][WR];
+    float fr[6];
+    f32x4 *l4 = reinterpret_cast<f32x4 *>(lds);
+    float *frow = feat + (size_t)b * G::FROW;
+    const bool keep = !full && tid < G::PP && delta_member(N, 2, pr, pc, 0) && dist > 3;      // (distance 0: is the position a board cell)
+    const int fcell = (pr - 1) * N + (pc - 1);
+    const int n3 = full ? 0 : L.cnt[3], n4 = full ? 0 : L.cnt[4];
+    {
+        const float *brow = base + ((size_t)b * 2 + par) * G::STRIDE;
+        const f32x4 *g4 = reinterpret_cast<const f32x4 *>(brow);
+        const float *bf = brow + G::IMG;
+        delta_rounds<0, WR>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            if (j * 64 + lane < n3) w1[j] = g4[wave * G::CS + L.halo[0][j * 64 + lane]];
+        });
+        delta_rounds<0, WR>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            if (j * 64 + lane < n4) {
+                const int pos = L.halo[1][j * 64 + lane];
+                w2[0][j] = g4[(8 + wave) * G::CS + pos];
+                w2[1][j] = g4[(16 + wave) * G::CS + pos];
+            }
+        });
+        if (keep) {
+#pragma unroll
+            for (int i = 0; i < 6; i++) fr[i] = bf[i * G::nn + fcell];
+        }
+        delta_rounds<0, WR>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            if (j * 64 + lane < n3) l4[wave * G::CS + L.halo[0][j * 64 + lane]] = w1[j];
+        });
+    }
     __syncthreads();
+    AZ_DSTAMP(2);
     for (int t0 = 0; t0 < t1; t0 += 4)
         conv_layer<G, 4, 32, CONV_OUT_PACKED, 4>(planes, inA, w.c1, w.c1b, L.wpos[0], L.cell[0], wave, lane, t0, t1 - t0 < 4 ? t1 - t0 : 4);
+    delta_rounds<0, WR>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        if (j * 64 + lane < n4) {
+            const int pos = L.halo[1][j * 64 + lane];
+            l4[(8 + wave) * G::CS + pos] = w2[0][j];
+            l4[(16 + wave) * G::CS + pos] = w2[1][j];
+        }
+    });
+    if (keep) {
+#pragma unroll
+        for (int i = 0; i < 6; i++) frow[i * G::nn + fcell] = fr[i];
+    }
     __syncthreads();
+    AZ_DSTAMP(3);
     for (int t0 = 0; t0 < t2;) {
         const int c = t2 - t0;
         if (c > 2) { conv_layer<G, 32, 64, CONV_OUT_PACKED, 4>(inA, inB, w.c2, w.c2b, L.wpos[1], L.cell[1], wave, lane, t0, c < 4 ? c : 4); t0 += 4; }
         else { conv_layer<G, 32, 64, CONV_OUT_PACKED, 2>(inA, inB, w.c2, w.c2b, L.wpos[1], L.cell[1], wave, lane, t0, c); t0 += 2; }
     }
     __syncthreads();
-    float *frow = feat + (size_t)b * G::FROW;
+    AZ_DSTAMP(4);
     for (int t0 = 0; t0 < t3; t0 += G::C3) {
         const int c = t3 - t0 < G::C3 ? t3 - t0 : G::C3;
         // conv_layer counts the cell-major rows from tile 0 of the list: the chunk's first row is lds
@@ -347,25 +433,11 @@ __global__ __launch_bounds__(NetGeo<N>::NW * 64) void k_trunk_delta(DevState d, 
         else if (c == 2) conv_layer<G, 64, 128, CONV_OUT3_CM, 2>(inB, o3, w.c3, w.c3b, L.wpos[2], L.cell[2], wave, lane, t0, 2);
         else conv_layer<G, 64, 128, CONV_OUT3_CM, 1>(inB, o3, w.c3, w.c3b, L.wpos[2], L.cell[2], wave, lane, t0, 1);
         __syncthreads();
+        AZ_DSTAMP(5 + 2 * (t0 / G::C3));
         delta_heads<G>(w, frow, lds, hdq_lds, L.cell[2] + t0 * 16, c * 16, wave, lane);
         __syncthreads();
+        AZ_DSTAMP(6 + 2 * (t0 / G::C3));
+        AZ_DSTAMP_VAL(15, __builtin_amdgcn_s_memrealtime());
     }
-}
-
-// k_trunk's work for the boards k_trunk_delta left: the same trunk_group, behind the per-board flag
-template <int N>
-__global__ __launch_bounds__(NetGeo<N>::NW * 64) void k_trunk_rest(DevState d, NetWeights w, int net_id, float *__restrict__ feat,
-                                                                    const unsigned char *done)
-{
-    typedef FusedGeo<N> G;
-    static_assert(G::G == 1, "one board per workgroup");
-    __shared__ __attribute__((aligned(16))) float lds[G::LDSF];
-    __shared__ __attribute__((aligned(16))) float hdq_lds[1024];
-    __shared__ unsigned short wpos[G::MR];
-    __shared__ unsigned short cellof[G::MR];
-    __shared__ int any_active;
-    const int grp = blockIdx.x;
-    if (grp >= d.B || done[grp]) return;
-    trunk_group<N>(d, w, net_id, feat, nullptr, grp, lds, hdq_lds, wpos, cellof, &any_active, threadIdx.x);
 }
 #endif  // __HIPCC__

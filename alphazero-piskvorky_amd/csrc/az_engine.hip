@@ -2696,6 +2696,22 @@ extern "C" int az_delta_lists(int n, int count, const uint8_t *changed, uint16_t
     return AZ_OK;
 }
 
+// ... and of a position the delta kernel evaluates in full (delta_lists_full)
+extern "C" int az_delta_lists_full(int n, uint16_t *wpos, uint16_t *cell, uint16_t *halo, int32_t *cnt)
+{
+    if (n != 15 || !wpos || !cell || !halo || !cnt) return AZ_ERR_INVALID;
+    static DeltaLists<15> L;
+    static std::mutex m;
+    std::lock_guard<std::mutex> lock(m);
+    memset(&L, 0xEE, sizeof L);
+    delta_lists_full<15>(L);
+    memcpy(wpos, L.wpos, sizeof L.wpos);
+    memcpy(cell, L.cell, sizeof L.cell);
+    memcpy(halo, L.halo, sizeof L.halo);
+    for (int l = 0; l < 5; l++) cnt[l] = L.cnt[l];
+    return AZ_OK;
+}
+
 extern "C" int az_net_eval_delta(az_engine *e, int slot, const uint8_t *root, int root_player, int count, const uint8_t *boards,
                                  const uint8_t *players, const int16_t *lasts, float *logits, float *policy, float *value, int32_t *path)
 {
@@ -3308,7 +3324,8 @@ extern "C" int az_rules_replay(az_engine *e, int games, int max_len, const int16
     return rc;
 }
 
-// diagnostic builds (-DAZ_STAMPS): per-workgroup phase stamps of the last k_trunk launch, 16 u64 per workgroup
+// diagnostic builds (-DAZ_STAMPS): per-workgroup phase stamps of the last k_trunk or k_trunk_delta launch (az_delta.h, AZ_DSTAMP:
+// other slots), 16 u64 per workgroup
 extern "C" int az_debug_stamps(az_engine *e, unsigned long long *out, int max_groups)
 {
     if (!e || !out || !e->lanes[0].dbg.p) return AZ_ERR_STATE;

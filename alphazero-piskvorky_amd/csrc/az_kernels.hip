@@ -309,8 +309,7 @@ void trunk_delta(const LaunchCtx &c, int net_id)
     if constexpr (HAS_DELTA) {
         const dim3 g(c.dv.B), b(NetGeo<N>::NW * 64);
         hipLaunchKernelGGL(k_trunk_delta<N>, g, b, 0, c.stream, c.dv, c.w[net_id], net_id, c.feat, (const float *)c.delta_base, c.delta_done,
-                           c.delta_cnt, c.delta_tiles);
-        hipLaunchKernelGGL(k_trunk_rest<N>, g, b, 0, c.stream, c.dv, c.w[net_id], net_id, c.feat, (const unsigned char *)c.delta_done);
+                           c.delta_cnt, c.delta_tiles, c.dbg);
     }
 }
 

@@ -27,7 +27,7 @@ struct LaunchCtx {
     unsigned char *inflight;   // deep search (S > DEFAULT_MAX_S) with virtual-loss batching: in-flight count per edge [B][R][RW], else null
     // delta evaluation (az_delta.h, az_set_delta_eval; part of the graph key): null = off, every board through SizeOps::trunk
     float *delta_base;              // [slots][2] base images and feature rows of the running ply
-    unsigned char *delta_done;      // [slots] which boards the delta kernel evaluated in the running batch
+    unsigned char *delta_done;      // [slots] the path of each board in the running batch: 0 in full, 1 + conv3 tiles as a delta
     unsigned long long *delta_cnt;  // [slots][DELTA_CNT] (az_delta.h)
     int delta_tiles;                // a board with more conv3 tiles than this is evaluated in full
 };

@@ -502,6 +502,9 @@ int az_delta_stats(const az_engine *e, int64_t *delta, int64_t *full, int64_t *t
  * tile lane of conv1 / conv2 / conv3, cell 0xFFFF = a junk lane -- the two window lists halo [2][289] (positions of the base
  * conv1 / conv2 images copied) and the five counts; entries behind a list's last tile read 0xEEEE. */
 int az_delta_lists(int n, int count, const uint8_t *changed, uint16_t *wpos, uint16_t *cell, uint16_t *halo, int32_t *cnt);
+/* ... and the lists of a position evaluated in full by the delta kernel (more changed cells, or more conv3 tiles than
+ * az_delta_max_tiles): every board cell in ascending position at all three layers, no window positions.  Same arrays. */
+int az_delta_lists_full(int n, uint16_t *wpos, uint16_t *cell, uint16_t *halo, int32_t *cnt);
 int az_net_eval_delta(az_engine *e, int slot, const uint8_t *root, int root_player, int count, const uint8_t *boards,
                       const uint8_t *players, const int16_t *lasts, float *logits, float *policy, float *value, int32_t *path);
 
