@@ -46,6 +46,7 @@ EXPORTS = [
     "az_set_threat_search", "az_get_threat_search", "az_threat_batch", "az_threat_solve", "az_selfplay_threats", "az_threat_stats",
     "az_set_rng", "az_get_rng", "az_rng_philox4x32", "az_rng_log", "az_rng_exp", "az_rng_philox_tape", "az_rng_philox_tape_device",
     "az_set_delta_eval", "az_get_delta_eval", "az_delta_max_tiles", "az_delta_stats", "az_net_eval_delta", "az_delta_lists", "az_delta_lists_full",
+    "az_delta_changed",
     "az_dist_unique_id", "az_dist_init", "az_dist_rank", "az_dist_world", "az_dist_counts", "az_dist_gather_records",
     "az_dist_allreduce_sum", "az_dist_broadcast",
 ]
@@ -219,6 +220,8 @@ def lib():
             L.az_delta_lists.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5
         if hasattr(L, "az_delta_lists_full"):
             L.az_delta_lists_full.argtypes = [C.c_int] + [C.c_void_p] * 4
+        if hasattr(L, "az_delta_changed"):
+            L.az_delta_changed.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3
         if hasattr(L, "az_set_rng"):
             L.az_set_rng.argtypes = [C.c_void_p, C.c_int]
             L.az_get_rng.argtypes = [C.c_void_p]

@@ -1,4 +1,4 @@
-// az_delta.h -- delta evaluation of the plain float32 trunk at n = 15 (DESIGN.md 5g).
+// az_delta.h -- delta evaluation of the plain float32 trunk at n = 15 (DESIGN.md 5g, 5h, 5i).
 //
 // Within one ply a game's root position does not change across its S + 1 evaluations, and a leaf is the root plus `depth`
 // stones.  Seen from the leaf's side to move, the net's input differs from one of two per-ply BASE inputs -- the root's stones
@@ -10,9 +10,10 @@
 //                  the packed conv1 / conv2 images exactly as they lie in LDS (padding ring included) and the head feature
 //                  row in HBM: DeltaGeo::STRIDE floats per (slot, parity)
 //   k_trunk_delta  in k_trunk's place, one workgroup per board: changed cells = leaf XOR base, dilated by 1 / 2 / 3 cells into
-//                  three lists of 16-cell tiles; the windows of the base images those tiles read are copied into LDS, the
-//                  layers run on the listed tiles only (conv_layer's subset mode, no border-tap skipping), and the feature
-//                  row is the base row with the conv3-region cells replaced.  A board with too many changed cells or conv3
+//                  three lists of 16-cell tiles; conv1 is recomputed from the leaf's own planes on the widest list (5i: 4 input
+//                  planes, nearly free, and nothing to wait for), the window of the base conv2 image that conv3's tiles read is
+//                  copied into LDS, conv2 and conv3 run on their listed tiles only (conv_layer's subset mode, no border-tap
+//                  skipping), and the feature row is the base row with the conv3-region cells replaced.  A board with too many changed cells or conv3
 //                  tiles is evaluated in full by the same workgroup with the same code: its lists are the whole board
 //                  (delta_lists_full: 15 tiles per layer), its images start as zeros and nothing is read from the base.
 //                  One trunk launch per batch (5h): the separate launch of trunk_group for those boards cost every batch a
@@ -49,15 +50,18 @@ __host__ __device__ inline int delta_dist(int n, int pr, int pc, const unsigned 
     return best;
 }
 // The five position lists of a delta evaluation, each in ascending padded position:
-//   list 0 / 1 / 2  board cells within 1 / 2 / 3 of a changed cell: the cells conv1 / conv2 / conv3 + heads compute
-//   list 3 / 4      padded positions (ring included) within 3 / 4: the windows of the base conv1 / conv2 images the layers read
+//   list 0 / 1 / 2  board cells within 1 / 2 / 3 of a changed cell: the 3x3 / 5x5 / 7x7 footprints.  conv2 computes list 1, conv3
+//                   and the heads list 2 -- and so does conv1 (5i), in place of copying its window; list 0 is only reported
+//   list 3          padded positions (ring included) within 3: the region conv1 computes (its board cells ARE list 2, in order)
+//                   plus the ring positions the kernel zeroes; the kernel does not build it
+//   list 4          padded positions within 4: the window of the base conv2 image that conv3 reads
 __host__ __device__ inline bool delta_member(int n, int list, int pr, int pc, int dist)
 {
     const bool inb = pr >= 1 && pr <= n && pc >= 1 && pc <= n;
     return list < 3 ? (inb && dist <= list + 1) : dist <= list;
 }
 // Tile lists as conv_layer addresses them: lane m of a list computes the cell at padded position wpos[m]; the lanes behind the
-// last cell, up to a whole tile, repeat the last cell's position (inside the copied windows at every tap) and are marked junk.
+// last cell, up to a whole tile, repeat the last cell's position (inside the computed / copied region at every tap) and are marked junk.
 template <int N>
 struct DeltaLists {
     typedef DeltaGeo<N> G;
@@ -76,9 +80,14 @@ struct DeltaLists {
         const int c = cnt[list], at = c + i;
         if (c > 0 && at < tiles(list) * 16) { wpos[list][at] = wpos[list][c - 1]; cell[list][at] = 0xFFFF; }
     }
+    __host__ __device__ void junk_at(int list, int c, int i, int pos)   // ... of a list of c cells whose last one lies at pos
+    {
+        const int at = c + i;
+        if (i >= 0 && i < 16 && at < ((c + 15) >> 4) * 16) { wpos[list][at] = (unsigned short)pos; cell[list][at] = 0xFFFF; }
+    }
 };
 // The lists of a set of changed cells, one position after the other: what k_trunk_delta builds with one thread per position
-// (same members, same order), here so that the integer logic can be checked on the CPU.
+// (same members, same order; the kernel leaves out list 3 and cnt[]), here so that the integer logic can be checked on the CPU.
 template <int N>
 __host__ __device__ inline void delta_lists_serial(const unsigned char *changed, int nch, DeltaLists<N> &L)
 {
@@ -114,10 +123,62 @@ __host__ __device__ inline void delta_lists_full(DeltaLists<N> &L)
         for (int i = 0; i < 16; i++) L.junk(l, i);
 }
 
+// The changed cells of a leaf against its base evaluation, a pure function of the 16 board words (5i): leaf = the pending leaf's
+// planes (words 0-3 side to move, 4-7 opponent), board = the root's (words 0-3 X, 4-7 O), player = the root's mover (1 / 2),
+// last = the leaf's last move or -1.  The leaf's parity is the number of stones beyond the root's, mod 2: even means the root's
+// mover is to move, and the base of that parity shows the root's stones from that side with an empty last-move plane.  A cell
+// is changed where either plane differs from the base's or where the last move lies.  Returns the k-th changed cell in
+// ascending order (0xFF where there are not that many), their number in *count.  The 16 words are the same in every lane and
+// cost scalar arithmetic once; only the walk to the k-th set bit depends on k, so in the kernel lane k finds cell k and the
+// wave reads the first DELTA_MAX_CHANGED of them back (extracting them one after the other in every wave cost 600 scalar
+// instructions per wave on the one scalar unit of the CU).
+template <int N>
+__host__ __device__ inline __attribute__((always_inline)) int delta_changed(const u64 *leaf, const u64 *board, int player, int last, int k, int *count, int *parity)
+{
+    static_assert(N * N > 192 && N * N <= 256, "four words of cells, the last one in part");
+    int stones = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) stones += __builtin_popcountll(leaf[i]) - __builtin_popcountll(board[i]);
+    const int par = stones & 1;
+    const bool me_is_x = (player == 1) != (par == 1);
+    u64 v = 0;
+    int total = 0, wi = 0, kk = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const u64 bme = me_is_x ? board[i] : board[4 + i], bop = me_is_x ? board[4 + i] : board[i];
+        u64 dw = (leaf[i] ^ bme) | (leaf[4 + i] ^ bop);
+        if (last >= 0 && last < N * N && (last >> 6) == i) dw |= 1ull << (last & 63);
+        if (i == 3 && N * N < 256) dw &= (1ull << ((N * N) & 63)) - 1ull;             // only board cells count
+        const int c = __builtin_popcountll(dw);
+        if (k >= total && k < total + c) { v = dw; wi = i; kk = k - total; }         // the word that holds the k-th changed cell
+        total += c;
+    }
+#pragma unroll
+    for (int j = 0; j < DELTA_MAX_CHANGED - 1; j++)
+        if (j < kk) v &= v - 1ull;
+    *count = total;
+    *parity = par;
+    return (k >= 0 && k < total && k < DELTA_MAX_CHANGED && v) ? wi * 64 + __builtin_ctzll(v) : 0xFF;
+}
+
 #ifdef __HIPCC__
+// a per-slot counter of the delta kernel: one workgroup per slot and launch, so the add needs no result and no round trip
+__device__ __forceinline__ void delta_count(unsigned long long *p, unsigned long long v)
+{
+    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// a board word, the same in every lane, moved to scalar registers: what delta_changed makes of it is scalar arithmetic
+__device__ __forceinline__ u64 delta_uniform(u64 v)
+{
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return ((u64)hi << 32) | lo;
+}
+
 // diagnostic builds only (-DAZ_STAMPS): k_trunk_delta's phase stamps (s_memtime), 16 u64 per workgroup in k_trunk's rows of the
-// debug buffer.  0 entry, 1 lists done, 2 windows in LDS, 3 conv1, 4 conv2, 5 + 2 i / 6 + 2 i conv3 chunk i / its heads pass
-// (zero where the leaf has no such chunk), 13 the conv3 tile count, 14 / 15 s_memrealtime at entry / at the last heads pass
+// debug buffer.  0 entry, 1 lists done, 2 window loads issued, 3 conv1 and the window stores, 4 conv2, 5 + 2 i / 6 + 2 i conv3
+// chunk i / its heads pass (zero where the leaf has no such chunk), 13 the conv3 tile count (bits 0-7) and the conv2 tile count
+// (bits 8-15), 14 / 15 s_memrealtime at entry / at the last heads pass
 #ifdef AZ_STAMPS
 #define AZ_DSTAMP(k) do { if (threadIdx.x == 0 && dbg) dbg[(size_t)blockIdx.x * 16 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
 #define AZ_DSTAMP_VAL(k, v) do { if (threadIdx.x == 0 && dbg) dbg[(size_t)blockIdx.x * 16 + (k)] = (unsigned long long)(v); } while (0)
@@ -239,6 +300,10 @@ __global__ __launch_bounds__(NetGeo<N>::NW * 64) void k_trunk_base(DevState d, N
 }
 
 // done[b]: 0 = evaluated in full, 1 + conv3 tiles = evaluated as a delta (or nothing to evaluate)
+// Prologue (5i): every entry load is issued before the early-exit test; the changed cells come from delta_changed on the 16
+// board words every wave holds (no LDS atomic, no barrier of their own); each padded position's thread writes its planes once,
+// builds its part of lists 0, 1, 2 and 4 and, on the ring within 3 of a changed cell, zeroes conv1's image; the first lanes
+// of the wave that puts a list's last cell write the junk lanes behind it.  Two barriers lie between entry and the window loads.
 template <int N>
 __global__ __launch_bounds__(NetGeo<N>::NW * 64) void k_trunk_delta(DevState d, NetWeights w, int net_id, float *__restrict__ feat,
                                                                      const float *__restrict__ base, unsigned char *done,
@@ -246,16 +311,14 @@ __global__ __launch_bounds__(NetGeo<N>::NW * 64) void k_trunk_delta(DevState d, 
 {
     typedef DeltaGeo<N> G;
     constexpr int NT = G::NW * 64;
-    static_assert(G::G == 1 && NT >= G::PP && NT == 512, "one board per workgroup, one thread per padded position");
+    static_assert(G::G == 1 && NT >= G::CS && NT == 512, "one board per workgroup, one thread per padded position");
     static_assert(G::C3 * 16 * OUT3_CM_STRIDE <= 32 * G::CS, "a chunk's conv3 image fits the dead conv1 image");
     static_assert(G::STRIDE % 4 == 0, "16-byte rows");
     __shared__ __attribute__((aligned(16))) float lds[G::IMG];          // conv1 image, conv2 image; a conv3 chunk overlays the first
     __shared__ __attribute__((aligned(16))) float planes[4 * G::CS];    // me, opponent, last move, zeros
     __shared__ __attribute__((aligned(16))) float hdq_lds[1024];
-    __shared__ DeltaLists<N> L;
-    __shared__ unsigned char changed[DELTA_MAX_CHANGED];
-    __shared__ int s_nch;
-    __shared__ int s_wc[5][5];                                          // [wave][list] members among the wave's 64 positions
+    __shared__ DeltaLists<N> L;                                         // (cnt[] is the host's: the kernel keeps the counts in registers)
+    __shared__ __attribute__((aligned(16))) int s_wc[5][4];                                       // [wave][list 0, 1, 2, 4] members among the wave's 64 positions
     const int b = blockIdx.x;
     if (b >= d.B) return;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -265,123 +328,131 @@ __global__ __launch_bounds__(NetGeo<N>::NW * 64) void k_trunk_delta(DevState d, 
 #ifdef AZ_STAMPS
     for (int k = 1; k < 14; k++) AZ_DSTAMP_VAL(k, 0);
 #endif
-    {
-        const int kind = d.leaf_kind[b];
-        if (!((kind == LEAF_ROOT || kind == LEAF_EXPAND) && d.s_status[b] == SLOT_ACTIVE && d.s_net[b] == net_id)) {
-            if (tid == 0) done[b] = 1;
-            return;
-        }
-    }
-    const float2 hq = reinterpret_cast<const float2 *>(w.hdq)[tid];
-    const u64 *lf = d.leaf + (size_t)b * 8, *bd = d.board + (size_t)b * 8;
-    const int last = d.leaf_last[b];
-    // parity of the leaf: an even number of stones beyond the root's means the root's mover is to move
-    int stones = 0;
+    // every entry load at once (all indices are in bounds for b < d.B), conv1's weights with them
+    const int kind = d.leaf_kind[b], status = d.s_status[b], snet = d.s_net[b], last = d.leaf_last[b], player = d.s_player[b];
+    u64 lf[8], bd[8];
 #pragma unroll
-    for (int i = 0; i < 8; i++) stones += __popcll(lf[i]) - __popcll(bd[i]);
-    const int par = stones & 1;
-    bool e_me = false, e_op = false, e_last = false;
-    int e_pos = G::PW + 1;
-    if (tid == 0) s_nch = 0;
-    for (int i = tid; i < 4 * G::CS; i += NT) planes[i] = 0.0f;
-    reinterpret_cast<float2 *>(hdq_lds)[tid] = hq;
-    __syncthreads();
-    if (tid < G::nn) {
-        const int r = tid / N, c = tid - r * N;
-        e_pos = (r + 1) * G::PW + (c + 1);
-        e_me = (lf[tid >> 6] >> (tid & 63)) & 1ull;
-        e_op = (lf[4 + (tid >> 6)] >> (tid & 63)) & 1ull;
-        e_last = last == tid;
-        const bool x = (bd[tid >> 6] >> (tid & 63)) & 1ull, o = (bd[4 + (tid >> 6)] >> (tid & 63)) & 1ull;
-        const bool me_is_x = (d.s_player[b] == 1) != (par == 1);
-        if (e_me != (me_is_x ? x : o) || e_op != (me_is_x ? o : x) || e_last) {
-            const int k = atomicAdd(&s_nch, 1);
-            if (k < DELTA_MAX_CHANGED) changed[k] = (unsigned char)tid;
-        }
-        if (e_me) planes[e_pos] = 1.0f;
-        if (e_op) planes[G::CS + e_pos] = 1.0f;
-        if (e_last) planes[2 * G::CS + e_pos] = 1.0f;
+    for (int i = 0; i < 8; i++) { lf[i] = delta_uniform(d.leaf[(size_t)b * 8 + i]); bd[i] = delta_uniform(d.board[(size_t)b * 8 + i]); }
+    const float2 hq = reinterpret_cast<const float2 *>(w.hdq)[tid];
+    const ConvPre<4> pre1 = conv_prefetch<G, 4, 32>(w.c1, wave, lane);
+    if (!((kind == LEAF_ROOT || kind == LEAF_EXPAND) && status == SLOT_ACTIVE && snet == net_id)) {
+        if (tid == 0) done[b] = 1;
+        return;
     }
-    __syncthreads();
-    const int nch = s_nch;
+    int ch[DELTA_MAX_CHANGED], par, nch;
+    {
+        // lane k finds the k-th changed cell; every wave reads the first eight back into scalar registers
+        const int mine = delta_changed<N>(lf, bd, player, last, lane & (DELTA_MAX_CHANGED - 1), &nch, &par);
+#pragma unroll
+        for (int i = 0; i < DELTA_MAX_CHANGED; i++) ch[i] = __builtin_amdgcn_readlane(mine, i);
+    }
     // full: the board is evaluated in full by this workgroup (delta_lists_full), uniform over the workgroup
     bool full = nch > DELTA_MAX_CHANGED;
     const int pr = tid / G::PW, pc = tid - pr * G::PW;
+    const bool in_img = tid < G::PP, inb = in_img && pr >= 1 && pr <= N && pc >= 1 && pc <= N;
+    const int fcell = (pr - 1) * N + (pc - 1);
+    f32x4 *l4 = reinterpret_cast<f32x4 *>(lds);
+    if (tid < G::CS) {
+        // the input planes, each position once: the position's own cell, zeros on the ring and behind the image
+        const int cp = inb ? fcell : 0, wi = cp >> 6;
+        const u64 me = wi == 0 ? lf[0] : wi == 1 ? lf[1] : wi == 2 ? lf[2] : lf[3];
+        const u64 op = wi == 0 ? lf[4] : wi == 1 ? lf[5] : wi == 2 ? lf[6] : lf[7];
+        planes[tid] = inb && ((me >> (cp & 63)) & 1ull) ? 1.0f : 0.0f;
+        planes[G::CS + tid] = inb && ((op >> (cp & 63)) & 1ull) ? 1.0f : 0.0f;
+        planes[2 * G::CS + tid] = inb && last == cp ? 1.0f : 0.0f;
+        planes[3 * G::CS + tid] = 0.0f;
+    }
     int dist = 255;
+    u64 bal[4] = {0, 0, 0, 0};
+    if (!full && wave < 5) {
+        // lists 0, 1, 2 and 4, one thread per padded position: a member's place is the number of members in front of it
+        if (in_img) {
+#pragma unroll
+            for (int i = 0; i < DELTA_MAX_CHANGED; i++) {
+                if (i < nch) {
+                    const int cr = ch[i] / N, cc = ch[i] - cr * N;
+                    const int dr = pr - 1 - cr < 0 ? cr - (pr - 1) : pr - 1 - cr, dc = pc - 1 - cc < 0 ? cc - (pc - 1) : pc - 1 - cc;
+                    const int dd = dr > dc ? dr : dc;
+                    dist = dd < dist ? dd : dist;
+                }
+            }
+        }
+#pragma unroll
+        for (int l = 0; l < 4; l++) {
+            bal[l] = __ballot(in_img && delta_member(N, l < 3 ? l : 4, pr, pc, dist));
+            if (lane == 0) s_wc[wave][l] = __popcll(bal[l]);
+        }
+        // conv1 runs on list 2 and conv2 reads one position further: the ring positions within 3 are zeros of conv1's image
+        if (in_img && !inb && dist <= 3) {
+#pragma unroll
+            for (int k = 0; k < 8; k++) l4[k * G::CS + tid] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+    __syncthreads();
+    int c[4] = {G::nn, G::nn, G::nn, 0}, front[4] = {0, 0, 0, 0};        // a list's members, and those of the waves in front of this one
     if (!full) {
-        // the five lists, one thread per padded position: a member's place is the number of members in front of it
-        u64 bal[5] = {0, 0, 0, 0, 0};
-        if (wave < 5) {
-            const bool in_img = tid < G::PP;
-            if (in_img) dist = delta_dist(N, pr, pc, changed, nch);
+        c[0] = c[1] = c[2] = 0;
 #pragma unroll
-            for (int l = 0; l < 5; l++) {
-                bal[l] = __ballot(in_img && delta_member(N, l, pr, pc, dist));
-                if (lane == 0) s_wc[wave][l] = __popcll(bal[l]);
-            }
-        }
-        __syncthreads();
-        if (wave < 5 && tid < G::PP) {
+        for (int v = 0; v < 5; v++) {
+            const int4 r = reinterpret_cast<const int4 *>(&s_wc[0][0])[v];
+            const int rv[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
-            for (int l = 0; l < 5; l++) {
-                if (!((bal[l] >> lane) & 1ull)) continue;
-                int at = __popcll(bal[l] & ((1ull << lane) - 1ull));
-                for (int v = 0; v < wave; v++) at += s_wc[v][l];
-                L.put(l, at, pr, pc);
-            }
+            for (int l = 0; l < 4; l++) { c[l] += rv[l]; front[l] += v < wave ? rv[l] : 0; }
         }
-        if (tid < 5) L.cnt[tid] = s_wc[0][tid] + s_wc[1][tid] + s_wc[2][tid] + s_wc[3][tid] + s_wc[4][tid];
-        __syncthreads();
-        full = L.tiles(2) > max_tiles;
-        if (full) __syncthreads();          // every thread has read the count before the lists are written again
+        full = ((c[2] + 15) >> 4) > max_tiles;
+        if (full) { c[0] = c[1] = c[2] = G::nn; c[3] = 0; }
     }
-    float *inA = lds, *inB = lds + 32 * G::CS;
-    if (full) {
+    if (!full) {
+        if (wave < 5 && in_img) {
+#pragma unroll
+            for (int l = 0; l < 4; l++) {
+                if ((bal[l] >> lane) & 1ull) L.put(l < 3 ? l : 4, front[l] + __popcll(bal[l] & ((1ull << lane) - 1ull)), pr, pc);
+                // the junk lanes, by the first lanes of the wave that holds the list's last cell: a padded position is its
+                // thread's index, so the last cell's position is the wave's base plus the highest member lane
+                if (l < 3 && bal[l] && front[l] + __popcll(bal[l]) == c[l])
+                    L.junk_at(l, c[l], lane, wave * 64 + 63 - __builtin_clzll(bal[l]));
+            }
+        }
+    } else {
         // too many changed cells or conv3 tiles: all 225 cells at every layer, 15 tiles through the same chunk loops below
-        if (tid < G::PP) delta_full_put<N>(L, pr, pc);
-        if (tid < 5) delta_full_cnt<N>(L, tid);
+        if (in_img) delta_full_put<N>(L, pr, pc);
+#pragma unroll
+        for (int l = 0; l < 3; l++) L.junk_at(l, G::nn, tid, N * G::PW + N);
         // no window is read: conv1 and conv2 write every board cell of their images, the ring has to be zero
-        float4 *z = reinterpret_cast<float4 *>(lds);
-        for (int i = tid; i < G::IMG / 4; i += NT) z[i] = float4{0.f, 0.f, 0.f, 0.f};
-        __syncthreads();
+        for (int i = tid; i < G::IMG / 4; i += NT) l4[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    const int t1 = L.tiles(0), t2 = L.tiles(1), t3 = L.tiles(2);
+    __syncthreads();
+    const int t2 = (c[1] + 15) >> 4, t3 = (c[2] + 15) >> 4, n4 = c[3];
     AZ_DSTAMP(1);
-    AZ_DSTAMP_VAL(13, t3);
-    if (tid < 48) L.junk(tid >> 4, tid & 15);
+    AZ_DSTAMP_VAL(13, t3 | (t2 << 8));
     if (tid == 0) {
-        if (full) { done[b] = 0; cnt[(size_t)b * DELTA_CNT + 1] += 1ull; }
+        // counters off the path: adds that return nothing, so that wave 0 does not wait for them in front of its window loads
+        unsigned long long *cb = cnt + (size_t)b * DELTA_CNT;
+        if (full) { done[b] = 0; delta_count(cb + 1, 1ull); }
         else {
             done[b] = (unsigned char)(1 + t3);
-            cnt[(size_t)b * DELTA_CNT + 0] += 1ull;
-            cnt[(size_t)b * DELTA_CNT + 2] += (unsigned long long)t3;
-            cnt[(size_t)b * DELTA_CNT + 4 + t3] += 1ull;
+            delta_count(cb + 0, 1ull);
+            delta_count(cb + 2, (unsigned long long)t3);
+            delta_count(cb + 4 + t3, 1ull);
         }
     }
-    // The windows of the base images and the base feature row: every global load is issued before the first store.  Plane =
-    // wave, list positions over the lanes, so no index is divided: the 8 float4 planes of conv1's image at list 3, planes w and
-    // 8 + w of conv2's 16 at list 4, in WR rounds of 64 positions (a list holds at most PP positions: WR + 2 WR fragments per
-    // thread bound what stays in registers, nothing is left over).  conv1's windows are stored in front of conv1.  conv2's
-    // stay in registers through conv1, which reads neither image, and are stored in front of conv2: BEFORE conv2's epilogue
-    // writes its cells of the same image, so no position has to be skipped.  The feature row: the thread of an in-board
-    // position further than 3 from every changed cell copies the cell's 6 values (the heads write the others), each once.
+    // The windows of the base conv2 image and the base feature row: every global load is issued before the first store.  Plane =
+    // wave, list positions over the lanes, so no index is divided: planes w and 8 + w of conv2's 16 float4 planes at list 4, in
+    // WR rounds of 64 positions (a list holds at most PP positions: 2 WR fragments per thread bound what stays in registers,
+    // nothing is left over).  They stay in registers through conv1, which reads neither image, and are stored in front of conv2:
+    // BEFORE conv2's epilogue writes its cells of the same image, so no position has to be skipped.  Nothing is loaded for
+    // conv1 (5i): it recomputes the cells of list 2 from the planes.  The feature row: the thread of an in-board position
+    // further than 3 from every changed cell copies the cell's 6 values (the heads write the others), each once.
     constexpr int WR = (G::PP + 63) / 64;
-    static_assert(WR * 64 >= G::PP && G::NW == 8, "the rounds reach the longest list; one conv1 plane and two conv2 planes per wave");
-    f32x4 w1[WR], w2[2][WR];
+    static_assert(WR * 64 >= G::PP && G::NW == 8, "the rounds reach the longest list; two conv2 planes per wave");
+    f32x4 w2[2][WR];
     float fr[6];
-    f32x4 *l4 = reinterpret_cast<f32x4 *>(lds);
     float *frow = feat + (size_t)b * G::FROW;
-    const bool keep = !full && tid < G::PP && delta_member(N, 2, pr, pc, 0) && dist > 3;      // (distance 0: is the position a board cell)
-    const int fcell = (pr - 1) * N + (pc - 1);
-    const int n3 = full ? 0 : L.cnt[3], n4 = full ? 0 : L.cnt[4];
+    const bool keep = !full && inb && dist > 3;
     {
         const float *brow = base + ((size_t)b * 2 + par) * G::STRIDE;
         const f32x4 *g4 = reinterpret_cast<const f32x4 *>(brow);
         const float *bf = brow + G::IMG;
-        delta_rounds<0, WR>([&](auto jc) {
-            constexpr int j = decltype(jc)::value;
-            if (j * 64 + lane < n3) w1[j] = g4[wave * G::CS + L.halo[0][j * 64 + lane]];
-        });
         delta_rounds<0, WR>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             if (j * 64 + lane < n4) {
@@ -394,15 +465,16 @@ __global__ __launch_bounds__(NetGeo<N>::NW * 64) void k_trunk_delta(DevState d, 
 #pragma unroll
             for (int i = 0; i < 6; i++) fr[i] = bf[i * G::nn + fcell];
         }
-        delta_rounds<0, WR>([&](auto jc) {
-            constexpr int j = decltype(jc)::value;
-            if (j * 64 + lane < n3) l4[wave * G::CS + L.halo[0][j * 64 + lane]] = w1[j];
-        });
     }
-    __syncthreads();
+    // conv2's first weight fragments fly under conv1, conv3's under conv2; they are the same for every chunk of a layer and stay
+    // in registers, so no chunk starts with a weight fetch
+    const ConvPre<32> pre2 = conv_prefetch<G, 32, 64>(w.c2, wave, lane);
     AZ_DSTAMP(2);
-    for (int t0 = 0; t0 < t1; t0 += 4)
-        conv_layer<G, 4, 32, CONV_OUT_PACKED, 4>(planes, inA, w.c1, w.c1b, L.wpos[0], L.cell[0], wave, lane, t0, t1 - t0 < 4 ? t1 - t0 : 4);
+    float *inA = lds, *inB = lds + 32 * G::CS;
+    for (int t0 = 0; t0 < t3; t0 += 4)
+        conv_layer<G, 4, 32, CONV_OUT_PACKED, 4>(planes, inA, w.c1, w.c1b, L.wpos[2], L.cell[2], wave, lane, t0, t3 - t0 < 4 ? t3 - t0 : 4,
+                                                 0, nullptr, nullptr, &pre1);
+    reinterpret_cast<float2 *>(hdq_lds)[tid] = hq;
     delta_rounds<0, WR>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         if (j * 64 + lane < n4) {
@@ -417,24 +489,27 @@ __global__ __launch_bounds__(NetGeo<N>::NW * 64) void k_trunk_delta(DevState d, 
     }
     __syncthreads();
     AZ_DSTAMP(3);
-    for (int t0 = 0; t0 < t2;) {
-        const int c = t2 - t0;
-        if (c > 2) { conv_layer<G, 32, 64, CONV_OUT_PACKED, 4>(inA, inB, w.c2, w.c2b, L.wpos[1], L.cell[1], wave, lane, t0, c < 4 ? c : 4); t0 += 4; }
-        else { conv_layer<G, 32, 64, CONV_OUT_PACKED, 2>(inA, inB, w.c2, w.c2b, L.wpos[1], L.cell[1], wave, lane, t0, c); t0 += 2; }
+    // exact tile counts: a chunk of c tiles runs the c-tile instantiation, no surplus chain (5i)
+    for (int t0 = 0; t0 < t2; t0 += 4) {
+        const int c2 = t2 - t0 < 4 ? t2 - t0 : 4;
+        if (c2 == 4) conv_layer<G, 32, 64, CONV_OUT_PACKED, 4>(inA, inB, w.c2, w.c2b, L.wpos[1], L.cell[1], wave, lane, t0, 4, 0, nullptr, nullptr, &pre2);
+        else if (c2 == 3) conv_layer<G, 32, 64, CONV_OUT_PACKED, 3>(inA, inB, w.c2, w.c2b, L.wpos[1], L.cell[1], wave, lane, t0, 3, 0, nullptr, nullptr, &pre2);
+        else if (c2 == 2) conv_layer<G, 32, 64, CONV_OUT_PACKED, 2>(inA, inB, w.c2, w.c2b, L.wpos[1], L.cell[1], wave, lane, t0, 2, 0, nullptr, nullptr, &pre2);
+        else conv_layer<G, 32, 64, CONV_OUT_PACKED, 1>(inA, inB, w.c2, w.c2b, L.wpos[1], L.cell[1], wave, lane, t0, 1, 0, nullptr, nullptr, &pre2);
     }
     __syncthreads();
     AZ_DSTAMP(4);
     for (int t0 = 0; t0 < t3; t0 += G::C3) {
-        const int c = t3 - t0 < G::C3 ? t3 - t0 : G::C3;
+        const int c3 = t3 - t0 < G::C3 ? t3 - t0 : G::C3;
         // conv_layer counts the cell-major rows from tile 0 of the list: the chunk's first row is lds
         float *o3 = lds - t0 * 16 * OUT3_CM_STRIDE;
-        if (c == 4) conv_layer<G, 64, 128, CONV_OUT3_CM, 4>(inB, o3, w.c3, w.c3b, L.wpos[2], L.cell[2], wave, lane, t0, 4);
-        else if (c == 3) conv_layer<G, 64, 128, CONV_OUT3_CM, 3>(inB, o3, w.c3, w.c3b, L.wpos[2], L.cell[2], wave, lane, t0, 3);
-        else if (c == 2) conv_layer<G, 64, 128, CONV_OUT3_CM, 2>(inB, o3, w.c3, w.c3b, L.wpos[2], L.cell[2], wave, lane, t0, 2);
+        if (c3 == 4) conv_layer<G, 64, 128, CONV_OUT3_CM, 4>(inB, o3, w.c3, w.c3b, L.wpos[2], L.cell[2], wave, lane, t0, 4);
+        else if (c3 == 3) conv_layer<G, 64, 128, CONV_OUT3_CM, 3>(inB, o3, w.c3, w.c3b, L.wpos[2], L.cell[2], wave, lane, t0, 3);
+        else if (c3 == 2) conv_layer<G, 64, 128, CONV_OUT3_CM, 2>(inB, o3, w.c3, w.c3b, L.wpos[2], L.cell[2], wave, lane, t0, 2);
         else conv_layer<G, 64, 128, CONV_OUT3_CM, 1>(inB, o3, w.c3, w.c3b, L.wpos[2], L.cell[2], wave, lane, t0, 1);
         __syncthreads();
         AZ_DSTAMP(5 + 2 * (t0 / G::C3));
-        delta_heads<G>(w, frow, lds, hdq_lds, L.cell[2] + t0 * 16, c * 16, wave, lane);
+        delta_heads<G>(w, frow, lds, hdq_lds, L.cell[2] + t0 * 16, c3 * 16, wave, lane);
         __syncthreads();
         AZ_DSTAMP(6 + 2 * (t0 / G::C3));
         AZ_DSTAMP_VAL(15, __builtin_amdgcn_s_memrealtime());

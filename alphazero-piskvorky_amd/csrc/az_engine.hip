@@ -2712,6 +2712,21 @@ extern "C" int az_delta_lists_full(int n, uint16_t *wpos, uint16_t *cell, uint16
     return AZ_OK;
 }
 
+// ... and the changed cells and the parity of a leaf against its root, with the function the kernel uses (delta_changed)
+extern "C" int az_delta_changed(int n, const uint64_t *leaf, const uint64_t *board, int player, int last, uint8_t *changed,
+                                int32_t *count, int32_t *parity)
+{
+    if (n != 15 || !leaf || !board || !changed || !count || !parity || (player != 1 && player != 2) || last < -1 || last >= 15 * 15)
+        return AZ_ERR_INVALID;
+    u64 lf[8], bd[8];
+    for (int i = 0; i < 8; i++) { lf[i] = leaf[i]; bd[i] = board[i]; }
+    int par = 0, cnt = 0;
+    for (int k = 0; k < DELTA_MAX_CHANGED; k++) changed[k] = (uint8_t)delta_changed<15>(lf, bd, player, last, k, &cnt, &par);
+    *count = cnt;
+    *parity = par;
+    return AZ_OK;
+}
+
 extern "C" int az_net_eval_delta(az_engine *e, int slot, const uint8_t *root, int root_player, int count, const uint8_t *boards,
                                  const uint8_t *players, const int16_t *lasts, float *logits, float *policy, float *value, int32_t *path)
 {

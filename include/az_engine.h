@@ -499,12 +499,22 @@ int az_delta_max_tiles(az_engine *e, int tiles);
 int az_delta_stats(const az_engine *e, int64_t *delta, int64_t *full, int64_t *tiles, int64_t *base, int64_t *by_tiles);
 /* The integer logic of the delta path on the host (no GPU needed), n = 15 and at most 8 changed cells (AZ_ERR_INVALID
  * otherwise): the three tile lists -- wpos / cell [3][240]: padded-image position (r + 1) * 17 + c + 1 and board cell of every
- * tile lane of conv1 / conv2 / conv3, cell 0xFFFF = a junk lane -- the two window lists halo [2][289] (positions of the base
- * conv1 / conv2 images copied) and the five counts; entries behind a list's last tile read 0xEEEE. */
+ * tile lane of the 3x3 / 5x5 / 7x7 regions, cell 0xFFFF = a junk lane -- the two position lists halo [2][289] and the five
+ * counts; entries behind a list's last tile read 0xEEEE.  conv2 runs on list 1, conv3 and the heads on list 2; conv1 is
+ * recomputed on list 2 as well, so list 0 is only reported.  halo[0] (list 3) = the region conv1 computes plus
+ * the ring positions it zeroes (nothing is copied there any more), halo[1] (list 4) = the positions of the base conv2 image
+ * that are copied. */
 int az_delta_lists(int n, int count, const uint8_t *changed, uint16_t *wpos, uint16_t *cell, uint16_t *halo, int32_t *cnt);
 /* ... and the lists of a position evaluated in full by the delta kernel (more changed cells, or more conv3 tiles than
  * az_delta_max_tiles): every board cell in ascending position at all three layers, no window positions.  Same arrays. */
 int az_delta_lists_full(int n, uint16_t *wpos, uint16_t *cell, uint16_t *halo, int32_t *cnt);
+/* The changed cells of a leaf against its root, as the kernel finds them from the 16 board words: leaf[8] = the leaf's planes
+ * (words 0-3 side to move, 4-7 opponent, bit c of word c / 64 = cell c), board[8] = the root's (words 0-3 X, 4-7 O), player =
+ * the root's side to move (1 / 2), last = the leaf's last move or -1.  *count = changed cells (more than 8: the position is
+ * evaluated in full), changed[8] = the first 8 in ascending order, 0xFF behind them, *parity = 0 where the root's mover is
+ * to move at the leaf.  AZ_ERR_INVALID for n != 15, a NULL pointer, another player or a last move off the board. */
+int az_delta_changed(int n, const uint64_t *leaf, const uint64_t *board, int player, int last, uint8_t *changed,
+                     int32_t *count, int32_t *parity);
 int az_net_eval_delta(az_engine *e, int slot, const uint8_t *root, int root_player, int count, const uint8_t *boards,
                       const uint8_t *players, const int16_t *lasts, float *logits, float *policy, float *value, int32_t *path);
 

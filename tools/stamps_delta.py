@@ -31,7 +31,7 @@ for _ in range(readings):
 e.close()
 t = np.concatenate(rows)
 # a workgroup that evaluated: five rising stamps up to conv2, a tile count, and as many chunk stamps as the count asks for
-tiles = t[:, 13]
+tiles = t[:, 13] & 0xFF          # (bits 8-15: the conv2 tile count)
 ok = (np.diff(t[:, :5], axis=1) > 0).all(axis=1) & (tiles >= 1) & (tiles <= 15) & (t[:, 15] > t[:, 14]) & (t[:, 15] - t[:, 14] < 100000)
 # k_trunk_delta stamps the rows of the launch's boards only, and k_fc's stamps follow them (az_kernels.hip): with fewer live
 # slots than B (games ended and none left to start) the rows behind them hold k_fc's words and fail the conditions above
@@ -40,7 +40,7 @@ print("rows:", len(t), " entry only (no evaluation in this launch):", int(((t[:,
 t, tiles = t[ok], tiles[ok]
 nchunk = np.count_nonzero(t[:, 5:13:2], axis=1)
 print("workgroups with a complete set of stamps:", len(t), "of", B * readings)
-names = ["lists", "windows", "conv1", "conv2", "conv3", "heads", "total"]
+names = ["lists", "windows", "conv1", "conv2", "conv3", "heads", "total"]    # since 5i "windows" is the issue of the loads, their wait is in conv1
 table = {}
 print(f"{'tiles':>5s} {'count':>6s} {'chunks':>6s} " + " ".join(f"{x:>8s}" for x in names))
 for k in list(range(1, 16)) + [0]:
